@@ -9,8 +9,8 @@
 // Switch: -DUSE_HIP next to the reference's own USE_CUDA (CMakeLists.txt:5-9, visualOdometry.cpp:112-118); see
 // adapters/USE_HIP.cmake and INTEGRATION.md.  OpenCV is needed for the TYPES of the existing signatures only (cv::Mat,
 // cv::Point2f): no OpenCV algorithm is called.  Where the OpenCV headers are not installed (this repository's test build)
-// the same file compiles against a type-only stand-in that the include path provides (tests/ref_dropin/Makefile:
-// -I oracle/ref_shim); tests/ref_dropin compiles THIS file with the reference's unmodified sources and
+// the same file compiles against a type-only stand-in that the include path provides (oracle/ref_dropin/Makefile:
+// -I oracle/ref_shim); oracle/ref_dropin compiles THIS file with the reference's unmodified sources and
 // tests/test_gpu_parity.py::test_reference_sources_run_on_libvo_hip runs the result on the GPU.
 #pragma once
 

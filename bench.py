@@ -20,10 +20,13 @@ from what frame k left (visualOdometry.cpp:127).  --ingest device: the new pairs
 Multi-GPU = replicas: each rank runs its own batch / its own sequences on its own GPU, no data-path collective
 (SURVEY.md 8e); value = frames of all ranks / max-over-ranks time.
 
-Prints ONE JSON line on rank 0 with the `roofline` (dominant kernel = fused LK, HBM-bound model, algorithmic bytes
-of SURVEY.md 8d / launch duration from HIP events on the launch stream), `cpu_baseline` (the oracle, a scalar C port
-with OpenMP, on a bounded sample of the same frames), `sustained` (a >= 5 s leg of the same loop) and
-`validated_frames` (frames pulled back after the timed loop and held to the oracle, outside the timer).
+Prints ONE JSON line on rank 0 with the headline (`value`, `ms_per_step` of the --steps timed steps) and the `roofline`
+(dominant kernel = fused LK, HBM-bound model, algorithmic bytes of SURVEY.md 8d / launch duration from HIP events on the
+launch stream).  A plain run does only that.  --full adds `cpu_baseline` (the oracle, a scalar C port with OpenMP, on a
+bounded sample of the same frames), `sustained` (a >= 5 s leg of the same loop), `validated_frames` (frames pulled back
+after the timed loop and held to the oracle, outside the timer), `exact_replay` and `configs` (every other BASELINE
+configuration and the latency leg; config 5 at N > 1).  --dump-outputs DIR writes what the last timed step computed as
+.npy files (inputs are seeded: the same arguments give the same inputs, so two builds compare output for output).
 """
 import argparse
 import json
@@ -59,6 +62,19 @@ WORKLOADS = {
 
 
 _RENDERED = {}  # (w, h, seed, n_quads) -> rendered sequence: the legs of one run share their images
+_POOL = []
+
+
+def _pool():
+    """threads for rendering the inputs (numpy releases the GIL): this rank's cores, at most 16"""
+    if not _POOL:
+        from concurrent.futures import ThreadPoolExecutor
+        try:
+            n = len(os.sched_getaffinity(0))
+        except AttributeError:
+            n = os.cpu_count() or 1
+        _POOL.append(ThreadPoolExecutor(max_workers=max(1, min(n, 16))))
+    return _POOL[0]
 
 
 def build_inputs(workload, n_quads, seed):
@@ -71,17 +87,22 @@ def build_inputs(workload, n_quads, seed):
         else:
             world = synth.StereoWorld(seed=seed, width=w, height=h, fx=synth.KITTI_FX * w / synth.KITTI_W,
                                       cx=w / 2.0 - 0.5, cy=h / 2.0 - 0.5, bf=synth.KITTI_BF * w / synth.KITTI_W)
-        lefts, rights, poses, _ = world.render_sequence(n_quads + 1)
+        # world.render_sequence(n_quads + 1), one image per thread: every image has its own seeded noise, so the
+        # images are those of the serial loop, bit for bit
+        poses = world.poses(n_quads + 1)
+        jobs = [(k, right) for k in range(n_quads + 1) for right in (False, True)]
+        imgs = list(_pool().map(lambda j: world.render(poses[j[0]], j[1], j[0])[0], jobs))
+        lefts, rights = imgs[0::2], imgs[1::2]
         _RENDERED[key] = (world, lefts, rights, {})
     world, lefts, rights, pts_cache = _RENDERED[key]
     if (workload.startswith("hd4000"), per_bucket) in pts_cache:
         return world, lefts, rights, pts_cache[(workload.startswith("hd4000"), per_bucket)], max_level
     bucket = h // 10
     if workload.startswith("hd4000"):
-        pts = [synth.select_keypoints(lefts[k], bucket=bucket, per_bucket=per_bucket, min_dist=3)[:4000]
-               for k in range(n_quads + 1)]
+        pts = list(_pool().map(lambda img: synth.select_keypoints(img, bucket=bucket, per_bucket=per_bucket, min_dist=3)[:4000],
+                               lefts))
     else:
-        pts = [synth.select_keypoints(lefts[k], bucket=bucket, per_bucket=per_bucket) for k in range(n_quads + 1)]
+        pts = list(_pool().map(lambda img: synth.select_keypoints(img, bucket=bucket, per_bucket=per_bucket), lefts))
     pts_cache[(workload.startswith("hd4000"), per_bucket)] = pts
     return world, lefts, rights, pts, max_level
 
@@ -219,10 +240,19 @@ def main(argv=None):
     ap.add_argument("--mono-rotation", action="store_true",
                     help="also run findEssentialMat + recoverPose per frame (trackingFrame2Frame's mono_rotation = true; "
                          "the reference's main loop passes false)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cpu_baseline, the sustained leg, validation against the oracle, "
+                         "the exact-replay leg and the `configs` legs (a plain run only sets up, warms up, times --steps "
+                         "steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, <= 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=6)
-    ap.add_argument("--sustain", type=float, default=5.0, help="seconds of the additional sustained leg (0 = off)")
-    ap.add_argument("--validate", type=int, default=3, help="frames held to the oracle after the timed loop (0 = off)")
+    ap.add_argument("--sustain", type=float, default=None,
+                    help="seconds of the additional sustained leg (0 = off; default 5 with --full, else 0)")
+    ap.add_argument("--validate", type=int, default=None,
+                    help="frames held to the oracle after the timed loop (0 = off; default 3 with --full, else 0)")
     ap.add_argument("--no-replay-leg", action="store_true",
                     help="batch mode: skip the additional exact-replay leg (`exact_replay` in the JSON line: the same workload "
                          "through --mode sequences with 256 sequences, reported next to `value`, never instead of it)")
@@ -237,6 +267,13 @@ def main(argv=None):
                     help="pin the pose-chain schedule instead of letting the library probe it: pose_waves,pose_streams,prepare "
                          "(vo_set_schedule: 0 / 0 / -1 = probe); tools/schedule_sweep.py uses it to hold the probe to every candidate")
     args = ap.parse_args(argv)
+    # a plain run times the headline and nothing else; what moved behind --full keeps today's defaults there
+    if args.sustain is None:
+        args.sustain = 5.0 if args.full else 0.0
+    if args.validate is None:
+        args.validate = 3 if args.full else 0
+    if not args.full:
+        args.no_cpu_baseline = args.no_replay_leg = args.no_configs = True
 
     # --gpus N is a promise about the line that gets printed: n_gpus = N ranks, one per GPU.  Launched by
     # torch.distributed.run the environment says the same thing; launched bare with N > 1 this process starts the N ranks
@@ -325,9 +362,10 @@ def main(argv=None):
         not args.mono_rotation and not args.no_configs
     kept = [] if (replay_leg or config_legs or config5_leg) else None
     if args.mode == "sequences":
-        out = run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas)
+        out = run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, dump=args.dump_outputs)
     else:
-        out = run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, keep_ctx=kept)
+        out = run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, keep_ctx=kept,
+                        dump=args.dump_outputs)
     if replay_leg:
         # the same workload as an EXACT replay of the reference's frame loop (features carried from frame to frame on the
         # device, FAST + bucketing every frame): reported beside the headline, with its own validation
@@ -436,7 +474,7 @@ def main(argv=None):
     return out
 
 
-def run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, keep_ctx=None, ctx=None):
+def run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, keep_ctx=None, ctx=None, dump=None):
     from visual_odom_amd import _lib
     B, S = args.frames, min(args.quads, args.frames)
     # every rank renders its own sequence (seed by rank) = independent sequences, one per GPU
@@ -478,6 +516,8 @@ def run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, repl
     elapsed, frames_total = replicas.aggregate(dist, elapsed, B * K, dev)
     if dist is not None:
         dist.barrier()
+    if dump and rank == 0:
+        dump_batch(ctx, B, args.stages != "lk", dump)
 
     # per-stage kernel time from the HIP events recorded on the launch stream during the timed steps
     stage_ms = np.mean([ctx.batch_slot_times(k % _lib.EVENT_SLOTS) for k in range(max(0, K - _lib.EVENT_SLOTS), K)],
@@ -563,7 +603,7 @@ def run_batch(args, rank, world_size, local_dev, dev, dist, barrier, torch, repl
     return out
 
 
-def run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, ctx=None, per_rank=False):
+def run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, replicas, ctx=None, per_rank=False, dump=None):
     """exact replay: S sequences x 1 frame per step, feature state carried on the device"""
     from visual_odom_amd import _lib
     S, Q = args.seqs, args.quads
@@ -614,7 +654,14 @@ def run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, 
     while ctx.get_schedule()["settling"] and extra < 520:
         one_step(W + 1 + extra)
         extra += 1
-    W += extra
+    if extra:
+        # how many steps settling takes depends on timing: the sequences start over (the settled schedule stays) and warm
+        # up again, so the timed steps see the same frames and the same carried state in every run with these arguments
+        ctx.seq_sync()
+        ctx.seq_reset(-1)
+        for k in range(W + 1):
+            one_step(k)
+    warmed = W + extra + (W + 1 if extra else 0)
     barrier(ctx)
     t0 = time.perf_counter()
     for k in range(W + 1, W + 1 + K):
@@ -626,6 +673,8 @@ def run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, 
     elapsed, frames_total = replicas.aggregate(dist, elapsed, S * K, dev)
     if dist is not None:
         dist.barrier()
+    if dump and rank == 0:
+        dump_sequences(ctx, S, W + K, dump)
     steps_done = W + 1 + K
     stage_ms = np.mean([ctx.batch_slot_times(k % _lib.EVENT_SLOTS) for k in range(max(W + 1, steps_done - _lib.EVENT_SLOTS), steps_done)],
                        axis=0)
@@ -646,7 +695,7 @@ def run_sequences(args, rank, world_size, local_dev, dev, dist, barrier, torch, 
     if rank == 0:
         out = {
             "metric": "stereo frames/sec on KITTI-00 1241x376 @ ~2000 features",
-            "value": frames_total / elapsed, "unit": "frames/s", "n_gpus": N_GPUS, "ranks": world_size, "steps": K, "warmup": W,
+            "value": frames_total / elapsed, "unit": "frames/s", "n_gpus": N_GPUS, "ranks": world_size, "steps": K, "warmup": warmed,
             "ms_per_step": 1e3 * elapsed / K, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u8/int32 LK (f32 2x2 solve), f64 pose solve", "data": "synthetic",
             "validated_frames": validated, "per_rank_value": rank_fps,
@@ -785,6 +834,60 @@ def pyramid_roofline(ctx, w, h, n_images, stage_ms, profiled_workload=None):
                         "frac_designed": moved / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS if ms > 0 else 0.0,
                         # HBM bytes of the stage from the PMC passes (imported, like roofline.traffic): against designed_bytes
                         "traffic": measured_pyramid_traffic(profiled_workload, n_images) if profiled_workload else None}}
+
+
+DUMP_BYTES = 60 << 20  # --dump-outputs stays under 64 MB in all
+
+
+def _save_dump(dump, arrays):
+    os.makedirs(dump, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dump, name + ".npy"), a)
+
+
+def dump_batch(ctx, B, with_pose, dump):
+    """--dump-outputs, batch mode: what a caller of the batch path receives for every frame of the last timed step
+    (vo_batch_get_filtered; its triangulation and vo_batch_get_pose unless --stages lk).  Per-point arrays are concatenated
+    over the frames; `counts` holds each frame's circular-matching survivors, filtered tracks and RANSAC inliers to split
+    them.  When all frames would exceed the size bound, a seeded sample of them is written; `frames` lists the frames written."""
+    recs = []
+    for b in range(B):
+        r = ctx.batch_get_filtered(b)
+        if with_pose:
+            r.update(ctx.batch_get_pose(b))
+        else:
+            del r["xyz"]
+        recs.append(r)
+    nbytes = np.array([sum(8 * v.size for v in r.values() if isinstance(v, np.ndarray)) for r in recs])
+    frames = np.arange(B)
+    if nbytes.sum() > DUMP_BYTES:
+        order = np.random.default_rng(0).permutation(B)
+        frames = np.sort(order[np.cumsum(nbytes[order]) <= DUMP_BYTES])
+    recs = [recs[b] for b in frames]
+    out = {"frames": frames.astype(np.float64),
+           "counts": np.array([(len(r["keep_idx_circ"]), len(r["l0"]), len(r.get("inliers", ()))) for r in recs], np.float64)}
+    for name in ("keep_idx_circ", "keep_idx"):
+        out[name] = np.concatenate([r[name] for r in recs]).astype(np.float64)
+    for name in ("l0", "r0", "l1", "r1"):
+        out[name] = np.concatenate([r[name] for r in recs]).astype(np.float32)
+    if with_pose:
+        out["xyz"] = np.concatenate([r["xyz"] for r in recs]).astype(np.float32)
+        out["inliers"] = np.concatenate([r["inliers"] for r in recs]).astype(np.float64)
+        for name in ("rvec", "tvec", "R"):
+            out[name] = np.stack([r[name] for r in recs]).astype(np.float64)
+        out["pose_status"] = np.array([[r[k] for k in ("status", "niters", "best_iter", "max_good", "lm_iters")] for r in recs],
+                                      np.float64)
+    _save_dump(dump, out)
+
+
+def dump_sequences(ctx, S, step, dump):
+    """--dump-outputs, sequence mode: every sequence's trajectory row and info row of the last timed step
+    (vo_seq_get_trajectory: frame_pose 3x4 | rvec | tvec | rotation 3x3, and SEQ_INFO_NAMES), and `step`, that step's index
+    in the loop since the sequences started (run_sequences restarts them once the schedule has settled)."""
+    last = [ctx.seq_get_trajectory(s) for s in range(S)]
+    _save_dump(dump, {"trajectory": np.stack([rows[-1] for rows, _ in last]).astype(np.float64),
+                      "info": np.stack([info[-1] for _, info in last]).astype(np.float64),
+                      "step": np.array([step], np.float64)})
 
 
 def spawn_ranks(args, argv):

@@ -419,7 +419,7 @@ class RefFrameLoop:
     oracle's OpenCV-algorithm restatement.  State as in main.cpp:81-94."""
 
     def __init__(self, fx, cx, cy, bf, mono_rotation=False, cap=65536, lib=None, entry="ref_frame_step"):
-        # lib: another library with the same ref_frame_step entry point (tests/ref_dropin: the same reference sources
+        # lib: another library with the same ref_frame_step entry point (oracle/ref_dropin: the same reference sources
         # over libvo_hip instead of over this oracle; its ref_frame_step_adapter also replaces main.cpp:169-171,181 by
         # the shipped adapter's triangulate_hip / trackingFrame2Frame_hip)
         self.lib = lib if lib is not None else ref_lib()

@@ -687,13 +687,13 @@ def test_product_frame_loop_against_the_reference_sources(gpu_ctx, orc, small_wo
 def test_reference_sources_run_on_libvo_hip(orc, small_world, mono, entry):
     """THE DROP-IN: the reference's unmodified matchingFeatures() / trackingFrame2Frame() / integrateOdometryStereo()
     (compiled where they lie; visualOdometry.cpp's circularMatching call reaches the SHIPPED adapter adapters/feature_hip.cpp,
-    the OpenCV entry points reach the C ABI: tests/ref_dropin) driving the MI355X, against the same reference code over
+    the OpenCV entry points reach the C ABI: oracle/ref_dropin) driving the MI355X, against the same reference code over
     the CPU oracle (oracle/_ref), frame after frame.  ref_frame_step_adapter: main.cpp:169-171,181 edited as INTEGRATION.md
     says -- the adapter's triangulate_hip / trackingFrame2Frame_hip instead of the OpenCV calls."""
     import ctypes
-    so = os.path.join(ROOT, "tests", "_build", "libvo_ref_dropin.so")
+    so = os.path.join(ROOT, "oracle", "_ref", "libvo_ref_dropin.so")
     if orc.ref_lib() is None or not os.path.exists(so):
-        pytest.skip("built only where /root/reference exists (make -C tests/ref_dropin) and shipped with the snapshot")
+        pytest.skip("oracle/_ref/libvo_ref_dropin.so is built only where the reference tree exists (make -C oracle/ref_dropin)")
     hip = ctypes.CDLL(so)
     keep = entry.endswith("+keep_pair")   # the adapter's opt-in: circularMatching_hip names the kept pair instead of its t0 images
     entry = entry.split("+")[0]

@@ -529,9 +529,9 @@ def test_shipped_adapter_detect_and_bucket(orc, small_seq):
     reference's OWN appendNewFeatures + bucketingFeatures compiled where they lie (oracle/_ref): first frame (empty set),
     a carried set with ages longer than points (quirk B3), a set that is large enough to skip re-detection"""
     import ctypes as C
-    so = os.path.join(ROOT, "tests", "_build", "libvo_ref_dropin.so")
+    so = os.path.join(ROOT, "oracle", "_ref", "libvo_ref_dropin.so")
     if orc.ref_lib() is None or not os.path.exists(so):
-        pytest.skip("built only where /root/reference exists (make -C tests/ref_dropin) and shipped with the snapshot")
+        pytest.skip("oracle/_ref/libvo_ref_dropin.so is built only where the reference tree exists (make -C oracle/ref_dropin)")
     hip = C.CDLL(so)
     img = np.ascontiguousarray(small_seq["L"][0])
     h, w = img.shape
@@ -785,7 +785,7 @@ def test_one_rank_over_rccl():
     env.pop("VO_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--frames", "16", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--sustain", "0", "--no-replay-leg", "--validate", "2"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain", "0", "--no-replay-leg", "--validate", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -813,7 +813,7 @@ def test_eight_ranks_of_bench_share_gpu_zero():
     env = dict(os.environ, VO_ALLOW_SHARED_GPU="1", VO_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--frames", "32", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--sustain", "0", "--no-replay-leg", "--validate", "2"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--sustain", "0", "--no-replay-leg", "--validate", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -7,8 +7,8 @@ run() {
     touch visual_odom_amd/csrc/lk.hip
     VO_LK_ATTRS="$2" python -m visual_odom_amd.build > "$OUT/build_$1.log" 2>&1 || { echo "build $1 failed"; tail -3 "$OUT/build_$1.log"; return; }
     for i in 1 2; do
-        VO_SERIAL_POSE=1 timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline > "$OUT/serial_$1_$i.json" 2>/dev/null
-        timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline > "$OUT/overlap_$1_$i.json" 2>/dev/null
+        VO_SERIAL_POSE=1 timeout 300 python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline > "$OUT/serial_$1_$i.json" 2>/dev/null
+        timeout 300 python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline > "$OUT/overlap_$1_$i.json" 2>/dev/null
     done
     python - "$OUT" "$1" <<'PY'
 import json, sys, glob

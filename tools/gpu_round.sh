@@ -43,8 +43,8 @@ if has timeline; then
     tail -40 "$OUT/timeline.txt"
 fi
 if has bench; then
-    stamp "bench (default: headline + exact replay + configs)"
-    timeout 900 python bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+    stamp "bench --full: headline + exact replay + configs"
+    timeout 900 python bench.py --steps 20 --warmup 3 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
     tail -c 600 "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 fi
 if has prof; then
@@ -116,7 +116,7 @@ if has posepmc; then  # counters of every kernel behind LK in the config-4 legs 
 fi
 if has ranks8; then   # eight REAL ranks on this one GPU (gloo): the N > 1 code path incl. the config-5 leg
     stamp "bench --gpus 8 on GPU 0"
-    VO_ALLOW_SHARED_GPU=1 VO_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 8 --frames 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain 0 > "$OUT/bench_ranks8.json" 2> "$OUT/bench_ranks8.err"
+    VO_ALLOW_SHARED_GPU=1 VO_DIST_BACKEND=gloo timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 8 --frames 32 --steps 3 --warmup 1 --full --no-cpu-baseline --sustain 0 > "$OUT/bench_ranks8.json" 2> "$OUT/bench_ranks8.err"
     tail -c 1500 "$OUT/bench_ranks8.json"; tail -3 "$OUT/bench_ranks8.err"
 fi
 if has quads; then   # the headline against the number of distinct rendered quadruples and the world seed (one process: tools/quads_table.py)

@@ -8,8 +8,8 @@ mkdir -p "$OUT"
 cd "$ROOT" || exit 1
 export TMPDIR=/tmp
 timeout 300 python -m pytest tests -m gpu -x -q 2>&1 | tail -1
-for i in 1 2; do timeout 300 python bench.py --steps 12 --warmup 2 --no-cpu-baseline > "$OUT/bench_$i.json" 2>/dev/null; done
-(cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d "$OUT/pmc" -- python "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
+for i in 1 2; do timeout 300 python bench.py --steps 12 --warmup 2 --full --no-cpu-baseline > "$OUT/bench_$i.json" 2>/dev/null; done
+(cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS GRBM_GUI_ACTIVE SQ_WAVES --output-format csv -d "$OUT/pmc" -- python "$ROOT/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline > /dev/null 2>&1)
 python - <<PY
 import glob, json, csv
 from collections import defaultdict

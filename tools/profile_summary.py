@@ -4,7 +4,7 @@
 
 What it takes from the session (each part of gpu_round.sh that ran):
     tests     pytest.log                      -> <prefix>_pytest_gpu.txt   (the summary tail)
-    bench     bench.json                      -> <prefix>_bench.json       (the ONE line `python bench.py` printed)
+    bench     bench.json                      -> <prefix>_bench.json       (the ONE line `python bench.py --full` printed)
     prof      kernel_stats_batch.csv          -> <prefix>_kernel_stats_batch.csv  (rocprofv3 --kernel-trace --stats of the headline)
     latency   latency.log                     -> <prefix>_latency_mode.txt
     timeline  timeline.txt                    -> <prefix>_track_frame_timeline.txt
