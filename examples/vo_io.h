@@ -23,7 +23,8 @@ namespace voio {
 
 struct Image {
     int w = 0, h = 0;
-    std::vector<uint8_t> px; // 8-bit gray, row-major, stride = w
+    std::vector<uint8_t> px; // 8-bit gray, row-major, stride = w -- or, with rgb = true, 3 bytes per pixel, stride = 3 w
+    bool rgb = false;        // in: keep an RGB(A) file's colour (the library converts: VO_FMT_RGB8); gray files are replicated
 };
 
 inline bool read_file(const std::string &path, std::vector<uint8_t> &buf)
@@ -151,9 +152,19 @@ inline bool decode_png(const std::vector<uint8_t> &buf, Image &im)
     }
     im.w = w;
     im.h = h;
-    im.px.resize((size_t)w * h);
+    im.px.resize((size_t)w * h * (im.rgb ? 3 : 1));
     for (int y = 0; y < h; y++) {
         const uint8_t *s = &raw[(row + 1) * (size_t)y + 1];
+        if (im.rgb) { // the decoded RGB rows as they are (alpha dropped; a gray file replicated like imread(IMREAD_COLOR))
+            uint8_t *d = &im.px[(size_t)3 * w * y];
+            for (int x = 0; x < w; x++) {
+                const uint8_t *q = s + (size_t)x * ch;
+                d[3 * x] = q[0];
+                d[3 * x + 1] = ch <= 2 ? q[0] : q[1];
+                d[3 * x + 2] = ch <= 2 ? q[0] : q[2];
+            }
+            continue;
+        }
         uint8_t *d = &im.px[(size_t)w * y];
         if (ch <= 2) { // gray (+ alpha)
             for (int x = 0; x < w; x++)
@@ -177,7 +188,16 @@ inline bool read_frame(const std::string &dir, int cam, int id, Image &im)
     if (read_file(dir + name, buf))
         return decode_png(buf, im);
     snprintf(name, sizeof(name), "/image_%d/%06d.pgm", cam, id);
-    return read_file(dir + name, buf) && decode_pgm(buf, im);
+    if (!read_file(dir + name, buf) || !decode_pgm(buf, im))
+        return false;
+    if (im.rgb) { // (a PGM has no colour to keep: replicated)
+        std::vector<uint8_t> g;
+        g.swap(im.px);
+        im.px.resize(g.size() * 3);
+        for (size_t i = 0; i < g.size(); i++)
+            im.px[3 * i] = im.px[3 * i + 1] = im.px[3 * i + 2] = g[i];
+    }
+    return true;
 }
 
 class ThreadPool {
@@ -247,11 +267,14 @@ struct FrameSet {
     std::mutex mu;
     std::condition_variable cv;
     int outstanding = 0;
-    void decode(ThreadPool &pool, const std::vector<std::string> &dirs, const std::vector<char> &live, int id, int w, int h)
+    void decode(ThreadPool &pool, const std::vector<std::string> &dirs, const std::vector<char> &live, int id, int w, int h,
+                bool keep_rgb = false)
     {
         const size_t S = dirs.size();
         left.resize(S);
         right.resize(S);
+        for (size_t s = 0; s < S; s++)
+            left[s].rgb = right[s].rgb = keep_rgb;
         ok.assign(S, 0);
         for (size_t s = 0; s < S; s++) {
             if (!live[s])

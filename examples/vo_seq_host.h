@@ -33,8 +33,10 @@ struct WorkerResult {
     std::vector<std::vector<int32_t>> info;  // per sequence: n x VO_SEQ_INFO
 };
 
+// device_convert: the decoded RGB rows go to the library as they are (vo_params.input_format = VO_FMT_RGB8, the colour
+// conversion runs in the ingest kernel) instead of being folded to gray by the decoder threads
 inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs, const Calib &cal, int max_frames,
-                               int features_per_bucket, int decode_threads)
+                               int features_per_bucket, int decode_threads, bool device_convert = false)
 {
     WorkerResult out;
     out.device = device;
@@ -65,6 +67,14 @@ inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs,
         return out;
     };
     int rc;
+    if (device_convert) {
+        vo_params prm;
+        if ((rc = vo_get_params(ctx, &prm)) < 0)
+            return fail("vo_get_params", rc);
+        prm.input_format = VO_FMT_RGB8;
+        if ((rc = vo_set_params(ctx, &prm)) < 0)
+            return fail("vo_set_params", rc);
+    }
     vo_detect_params dp;
     vo_default_detect_params(&dp);
     dp.features_per_bucket = features_per_bucket;
@@ -83,7 +93,7 @@ inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs,
     std::vector<char> live(S, 1);
     const auto t0 = std::chrono::steady_clock::now();
     for (int k = 0; k <= depth && k < max_frames; k++)
-        sets[k % (depth + 1)].decode(pool, dirs, live, k, w, h);
+        sets[k % (depth + 1)].decode(pool, dirs, live, k, w, h, device_convert);
     for (int id = 0; id < max_frames; id++) {
         voio::FrameSet &cur = sets[id % (depth + 1)];
         const auto tw = std::chrono::steady_clock::now();
@@ -112,12 +122,12 @@ inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs,
                 lp.push_back(cur.left[s].px.data());
                 rp.push_back(cur.right[s].px.data());
             }
-        if ((rc = vo_seq_push_pairs(ctx, (int)ids.size(), ids.data(), lp.data(), rp.data(), w, /*kind: pageable*/ 0)) < 0)
+        if ((rc = vo_seq_push_pairs(ctx, (int)ids.size(), ids.data(), lp.data(), rp.data(), device_convert ? 3 * w : w, /*kind: pageable*/ 0)) < 0)
             return fail("vo_seq_push_pairs", rc);
         if ((rc = vo_seq_step(ctx)) < 0)
             return fail("vo_seq_step", rc);
         if (id + depth + 1 < max_frames) // this slot is free again: the frame `depth + 1` ahead goes into it
-            cur.decode(pool, dirs, live, id + depth + 1, w, h);
+            cur.decode(pool, dirs, live, id + depth + 1, w, h, device_convert);
     }
     pool.wait();
     if ((rc = vo_seq_sync(ctx)) < 0)

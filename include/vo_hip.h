@@ -12,6 +12,14 @@
  * GPU; a ctx is not thread-safe.  Points are interleaved float32 (x, y) like cv::Point2f, images
  * are 8-bit gray row-major with a byte stride, like the continuous CV_8UC1 cv::Mat the reference
  * passes around (utils.cpp:179).
+ *
+ * INPUT FORMATS: that is the default, vo_params.input_format = VO_FMT_GRAY8.  A context may be set to ONE other format
+ * (VO_FMT_* below); it then governs EVERY image pointer of this header -- vo_track_frame, vo_circular_match,
+ * vo_fast_detect, vo_detect_bucket (an image of its own), vo_batch_upload_image(_dev), vo_seq_push_pair(_dev),
+ * vo_seq_push_pairs (all kinds) -- and the library converts to gray on the GPU, in the kernel that moves the image anyway; the
+ * host only copies raw bytes.  `w`, `h` stay in pixels, `stride` stays "bytes from one row to the next"; its minimum becomes
+ * w * bytes per pixel (1, 2, 3, 3, 4, 4), below it VO_ERR_ARG.  Everything downstream (kept pair, pyramids, results) is
+ * that of the gray call with the converted image, bit for bit.
  */
 #ifndef VO_HIP_H
 #define VO_HIP_H
@@ -39,6 +47,21 @@ extern "C" {
 
 typedef struct vo_ctx vo_ctx;
 
+/* vo_params.input_format: what an image pointer points at.
+ * The reference's two input modes: files are imread(IMREAD_COLOR) + cvtColor(BGR2GRAY) on every frame (main.cpp:107-114,
+ * 135-141 -> utils.cpp:172-190) -- such a CV_8UC3 cv::Mat goes in as it is with VO_FMT_BGR8; the sensor mode delivers ONE
+ * buffer of 16-bit words per frame, left pixel = low byte, right pixel = high byte (rgbd_standalone.cpp:178-196: `% 256` is
+ * the byte at 2x, `/ 256` the byte at 2x + 1) -- with VO_FMT_GRAY8_X2 it goes in without a copy as left = buf, right = buf + 1,
+ * same stride, and the library reads the buffer ONCE for both planes (it recognises right == left + 1).  The same format
+ * takes the luma of a YUYV frame.  A SIDE-BY-SIDE frame needs no format at all: two pointers into one buffer, one stride.
+ * Colour: Y = (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14, cvtColor's integer form. */
+#define VO_FMT_GRAY8    0   /* pixel x of a row at byte x (the default)                                           */
+#define VO_FMT_GRAY8_X2 1   /* pixel x at byte 2x of the pointer given: ONE plane of a two-byte interleave        */
+#define VO_FMT_BGR8     2   /* 3 bytes per pixel, cvtColor(BGR2GRAY)                                              */
+#define VO_FMT_RGB8     3
+#define VO_FMT_BGRA8    4   /* 4 bytes per pixel, alpha ignored                                                   */
+#define VO_FMT_RGBA8    5
+
 /* LK / RANSAC parameters; vo_default_params() fills the reference's literals
  * (feature.cpp:127-128,136: win 21 (fixed), maxLevel 3, COUNT+EPS 30 / 0.01, minEig 1e-3;
  *  visualOdometry.cpp:168-172: 500 iterations, 0.5 px, confidence 0.999f;
@@ -65,6 +88,9 @@ typedef struct vo_params {
     int mono_rotation;
     double em_prob;      /* 0.999 */
     double em_threshold; /* 1.0 px */
+    /* VO_FMT_* (default VO_FMT_GRAY8): the format of every image this context is given; anything else is VO_ERR_ARG.  Like
+     * lk_max_level it takes effect with the next configure -- a context has one input format at a time. */
+    int input_format;
 } vo_params;
 
 void vo_default_params(vo_params *p);
@@ -162,6 +188,7 @@ int vo_get_params(const vo_ctx *ctx, vo_params *p);
  * apply_consistency != 0 additionally applies checkValidMatch(thr) + removeInvalidPoints
  * (visualOdometry.cpp:44-77,119-125) so the outputs are the K points that reach triangulation.
  * img_l0 == img_r0 == NULL: the t0 pair is the previous call's t1 pair (see vo_track_frame, THE KEPT PAIR).
+ * Images in vo_params.input_format, stride >= w * its bytes per pixel (INPUT FORMATS above).
  * VALUES (round 6; tests/adversarial.py, tests/test_gpu_round6.py): a start point with a NaN coordinate, +-inf or a value
  * beyond int32 fails its first hop with status 0 exactly as in calcOpticalFlowPyrLK (x86's cvFloor(NaN) is INT_MIN: "left of
  * the window"), its reported positions are the propagated (NaN / huge) values, and deleteUnmatchFeaturesCircle drops it;
@@ -200,7 +227,7 @@ int vo_essential_pose(vo_ctx *ctx, const float *pts0_xy, const float *pts1_xy, i
                       double ppy, double prob, double threshold, double *E, double *R, double *t, uint8_t *mask,
                       int *n_good);
 /* Replaces cv::FAST as called by featureDetectionFast() -- feature.cpp:39-47: TYPE_9_16 corners of an
- * 8-bit image in row-major order.  pts_out [2 * cap]; *n_out = corners found (may exceed cap, in which
+ * 8-bit image (given in vo_params.input_format) in row-major order.  pts_out [2 * cap]; *n_out = corners found (may exceed cap, in which
  * case only the first cap are written).  VO_ERR_OVERFLOW when the corners exceed the context's own corner-list
  * capacity max(4 * max_pts, 16384, max_w * max_h / 16) although the caller's cap would have held them. */
 int vo_fast_detect(vo_ctx *ctx, const uint8_t *img, int w, int h, int stride, int threshold, int nonmax,
@@ -211,7 +238,8 @@ int vo_fast_detect(vo_ctx *ctx, const uint8_t *img, int w, int h, int stride, in
  * (feature.cpp:206-253, bucket.cpp:14-51, quirks of SURVEY.md App. B1-B3 reproduced).
  * pts_io [2 * cap] / ages_io [cap]: in: *n_pts points and *n_ages ages (n_ages >= n_pts allowed, as in
  * the reference after a consistency filter); out: the bucketed set (*n_pts == *n_ages).
- * img == NULL (also vo_fast_detect): the left image of the pair vo_track_frame kept (see there).
+ * img == NULL (also vo_fast_detect): the left image of the pair vo_track_frame kept (see there); an image of its own is
+ * given in vo_params.input_format.
  * A carried point whose bucket index the reference would read outside its bucket vector (NaN / infinite / huge / far
  * negative coordinates: undefined behaviour in feature.cpp:233-236) is IGNORED here (quotients beyond +-32768 or an index
  * outside the (rows/bs + 1) x (cols/bs + 1) buckets); every in-image point takes the reference's path. */
@@ -230,7 +258,8 @@ int vo_integrate_odometry(double *pose16, const double *R9, const double *t3, fl
  * one download.  out_l0/out_r0/out_l1/out_r1 [2n] and xyz_out [3n] are compacted to *n_out (= K).
  * keep_idx (optional, [n]) -> input index of each of the K points; keep_idx_circ/n_circ (optional)
  * -> survivors of deleteUnmatchFeaturesCircle alone (what `ages` is compacted with, quirk B3).
- * Images and points are pageable host memory; the caller's buffers are free on return.  (Inside: each image is
+ * Images (in vo_params.input_format: the slot receives the raw rows, the pull converts) and points are pageable host memory;
+ * the caller's buffers are free on return.  (Inside: each image is
  * repacked into a page-locked slot and read by the GPU over PCIe while the host repacks the next one, nothing
  * synchronises before the results -- 0.65-0.68 ms per KITTI frame at ~2000 points on an MI355X)
  *
@@ -273,7 +302,8 @@ int64_t vo_kept_pair_id(const vo_ctx *ctx);
 #define VO_NUM_STAGES 6      /* timing order: PYRAMID, DETECT, LK, FILTER, TRIANGULATE, PNP */
 
 int vo_batch_configure(vo_ctx *ctx, int n_images, int w, int h, int n_frames);
-/* host -> device copy of one level-0 image */
+/* host -> device copy of one level-0 image (both calls: given in vo_params.input_format, stride >= w * bytes per pixel;
+ * level 0 receives the gray image) */
 int vo_batch_upload_image(vo_ctx *ctx, int image_idx, const uint8_t *host_pixels, int stride);
 /* device -> device copy (e.g. from a torch uint8 tensor's data_ptr()) */
 int vo_batch_upload_image_dev(vo_ctx *ctx, int image_idx, const void *dev_pixels, int stride);
@@ -377,7 +407,8 @@ int vo_seq_configure(vo_ctx *ctx, int n_seq, int w, int h, int ring, int max_ste
  * pair builds pyramids only: one frame is not processed) and the frame after it carries VO_SEQ_F_GAP -- a pair is never
  * matched against the pair from two pushes ago.  To lose no frame, size max_steps for the run or reset between runs. */
 int vo_seq_reset(vo_ctx *ctx, int seq);
-/* the next stereo pair of sequence `seq` (8-bit gray, byte stride).  host_pinned = 0: pageable memory, staged
+/* the next stereo pair of sequence `seq` (in vo_params.input_format -- 8-bit gray by default -- with a byte stride >= w * bytes
+ * per pixel; the ingest kernel converts; a VO_FMT_GRAY8_X2 pair with right == left + 1 crosses the link once).  host_pinned = 0: pageable memory, staged
  * through the library's pinned buffers (the call returns when the images have been copied out of the caller's
  * memory; vo_seq_push_pairs spreads a step's copies over up to 8 host threads; from 32 sequences on, a step whose pairs
  * are ALL pageable crosses the link as one contiguous copy-engine transfer -- the fastest way in: 256 KITTI sequences at

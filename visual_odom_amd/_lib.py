@@ -23,6 +23,9 @@ STAGE_DETECT = 32
 EVENT_SLOTS = 256
 STAGE_NAMES = ("pyramid", "detect", "lk", "filter", "triangulate", "pnp")
 NUM_STAGES = len(STAGE_NAMES)
+# vo_params.input_format (VO_FMT_* of include/vo_hip.h) and the source bytes per pixel
+FMT_GRAY8, FMT_GRAY8_X2, FMT_BGR8, FMT_RGB8, FMT_BGRA8, FMT_RGBA8 = 0, 1, 2, 3, 4, 5
+FMT_BPP = (1, 2, 3, 3, 4, 4)
 
 # every symbol include/vo_hip.h declares (checked by the CPU test-suite against the built .so)
 EXPORTS = (
@@ -44,7 +47,7 @@ class VoParams(C.Structure):
                 ("lk_min_eig_threshold", C.c_double), ("lk_full_chain", C.c_int), ("consistency_threshold", C.c_int),
                 ("ransac_iterations", C.c_int), ("ransac_reproj_error", C.c_float),
                 ("ransac_confidence", C.c_double), ("mono_rotation", C.c_int), ("em_prob", C.c_double),
-                ("em_threshold", C.c_double)]
+                ("em_threshold", C.c_double), ("input_format", C.c_int)]
 
 
 class VoDetectParams(C.Structure):
@@ -140,10 +143,43 @@ def _p(a):
         return a.ctypes.data_as(C.c_void_p)
 
 
-def _imgs(*arrays):
+def _imgs_fmt(arrays, fmt):
+    """_imgs for a context whose input format is not gray: nothing is converted here, the arrays' own bytes go to the library.
+      FMT_BGR8 / RGB8 / BGRA8 / RGBA8   (h, w, 3 | 4) uint8; pixel-contiguous views with a common row stride are passed as they
+                                        are, anything else of that shape is made contiguous
+      FMT_GRAY8_X2                      (h, w) uint8 views with an ELEMENT stride of 2 -- one plane of a two-byte interleave, e.g.
+                                        buf.view(np.uint8).reshape(h, w, 2)[..., 0] -- passed as they are (the pointer is the
+                                        view's first byte, so [..., 1] is buf + 1); they must share their row stride
+    A shape that does not fit the format raises ValueError before any C call."""
+    if fmt not in (FMT_GRAY8_X2, FMT_BGR8, FMT_RGB8, FMT_BGRA8, FMT_RGBA8):
+        raise ValueError("input format %r is not one of FMT_*" % (fmt,))
+    bpp = FMT_BPP[fmt]
+    arrs = [np.asarray(a) for a in arrays]
+    if len({a.shape for a in arrs}) != 1:
+        raise ValueError("the images of one call must have one shape")
+    if fmt == FMT_GRAY8_X2:
+        for a in arrs:
+            if a.dtype != np.uint8 or a.ndim != 2 or a.strides[1] != 2 or a.strides[0] < 2 * a.shape[1]:
+                raise ValueError("FMT_GRAY8_X2 takes (h, w) uint8 views with an element stride of 2 (one plane of a two-byte "
+                                 "interleave), not shape %s strides %s %s" % (a.shape, a.strides, a.dtype))
+        if len({a.strides[0] for a in arrs}) != 1:
+            raise ValueError("FMT_GRAY8_X2: the planes of one call must share their row stride")
+        return arrs, int(arrs[0].strides[0])
+    for a in arrs:
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != bpp:
+            raise ValueError("this context's input format takes (h, w, %d) uint8 images, not shape %s %s" % (bpp, a.shape, a.dtype))
+    ok = all(a.strides[2] == 1 and a.strides[1] == bpp and a.strides[0] >= a.shape[1] * bpp for a in arrs)
+    if not ok or len({a.strides[0] for a in arrs}) != 1:
+        arrs = [np.ascontiguousarray(a) for a in arrs]
+    return arrs, int(arrs[0].strides[0])
+
+
+def _imgs(*arrays, fmt=FMT_GRAY8):
     """8-bit gray images as the ABI takes them: a base pointer + one byte stride for all of them.  Row-contiguous views (a
     padded buffer, an ROI of a bigger image: strides (stride, 1)) are passed AS THEY ARE with their stride -- no copy --
-    when they all share it; anything else is made contiguous (stride = width)."""
+    when they all share it; anything else is made contiguous (stride = width).  fmt: the context's input format (_imgs_fmt)."""
+    if fmt != FMT_GRAY8:
+        return _imgs_fmt(arrays, fmt)
     arrs = [np.asarray(a) for a in arrays]
     ok = all(a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1 and a.strides[0] >= a.shape[1] for a in arrs)
     if not ok or len({a.strides[0] for a in arrs}) != 1 or len({a.shape for a in arrs}) != 1:
@@ -151,9 +187,9 @@ def _imgs(*arrays):
     return arrs, int(arrs[0].strides[0])
 
 
-def _imgs_opt(*arrays):
+def _imgs_opt(*arrays, fmt=FMT_GRAY8):
     """_imgs over the images that are given; None stays None (the C ABI's NULL: vo_hip.h, THE KEPT PAIR)"""
-    arrs, stride = _imgs(*[a for a in arrays if a is not None])
+    arrs, stride = _imgs(*[a for a in arrays if a is not None], fmt=fmt)
     it = iter(arrs)
     return [None if a is None else next(it) for a in arrays], stride
 
@@ -193,6 +229,7 @@ class Context:
         self.max_pts, self.max_frames = max_pts, max_frames
         self.n_frames = 0
         self._kept_shape = (0, 0)   # (h, w) of the pair the last track_frame kept on the device
+        self.input_format = FMT_GRAY8   # vo_params.input_format: what the image helpers expect (set_params keeps it current)
 
     def close(self):
         if getattr(self, "h", None):
@@ -223,6 +260,7 @@ class Context:
                 raise KeyError(k)
             setattr(p, k, v)
         self._chk(self.lib.vo_set_params(self.h, C.byref(p)))
+        self.input_format = int(p.input_format)
 
     def set_schedule(self, pose_waves=0, pose_streams=0, prepare=-1, epnp_wide_frames=0):
         """pin knobs of the pose-chain schedule (0 / 0 / -1 / 0 = probe, the default); see vo_schedule in vo_hip.h"""
@@ -251,8 +289,8 @@ class Context:
 
     # ---- drop-in calls ------------------------------------------------------------------
     def circular_match(self, l0, r0, l1, r1, pts_l0, apply_consistency=False):
-        imgs, stride = _imgs_opt(l0, r0, l1, r1)   # (l0 = r0 = None: the pair the previous call kept, see track_frame)
-        h, w = imgs[2].shape
+        imgs, stride = _imgs_opt(l0, r0, l1, r1, fmt=self.input_format)   # (l0 = r0 = None: the pair the previous call kept, see track_frame)
+        h, w = imgs[2].shape[:2]
         self._kept_shape = (h, w)
         pts = _f32(pts_l0, (-1, 2))
         n = pts.shape[0]
@@ -319,8 +357,8 @@ class Context:
         if img is None:   # the left image of the pair the last track_frame kept
             (h, w), stride = self._kept_shape, self._kept_shape[1]
         else:
-            (img,), stride = _imgs(img)
-            h, w = img.shape
+            (img,), stride = _imgs(img, fmt=self.input_format)
+            h, w = img.shape[:2]
         pts = np.zeros((cap, 2), np.float32)
         n = C.c_int(0)
         self._chk(self.lib.vo_fast_detect(self.h, _pn(img), w, h, stride, int(threshold), int(bool(nonmax)), _p(pts), cap,
@@ -336,8 +374,8 @@ class Context:
         if img is None:
             (h, w), stride = self._kept_shape, self._kept_shape[1]
         else:
-            (img,), stride = _imgs(img)
-            h, w = img.shape
+            (img,), stride = _imgs(img, fmt=self.input_format)
+            h, w = img.shape[:2]
         pts = _f32(pts, (-1, 2))
         ages = np.ascontiguousarray(ages, np.int32).reshape(-1)
         cap = max(self.max_pts, len(ages), 1)
@@ -354,8 +392,8 @@ class Context:
     def track_frame(self, l0, r0, l1, r1, pts_l0, P_l, P_r, rvec=None, tvec=None):
         """l0 is None and r0 is None: the t0 pair is the pair the previous call received as (l1, r1) -- kept on the device
         with its pyramids (vo_hip.h, THE KEPT PAIR; main.cpp:157-158)"""
-        imgs, stride = _imgs_opt(l0, r0, l1, r1)
-        h, w = imgs[2].shape
+        imgs, stride = _imgs_opt(l0, r0, l1, r1, fmt=self.input_format)
+        h, w = imgs[2].shape[:2]
         self._kept_shape = (h, w)
         pts = _f32(pts_l0, (-1, 2))
         n = pts.shape[0]
@@ -386,7 +424,7 @@ class Context:
         self.n_frames = n_frames
 
     def batch_upload_image(self, idx, img):
-        (img,), stride = _imgs(img)
+        (img,), stride = _imgs(img, fmt=self.input_format)
         self._chk(self.lib.vo_batch_upload_image(self.h, idx, _p(img), stride))
 
     def batch_upload_image_dev(self, idx, dev_ptr, stride):
@@ -488,9 +526,9 @@ class Context:
         self._chk(self.lib.vo_seq_reset(self.h, seq))
 
     def seq_push_pair(self, seq, left, right, pinned=False):
-        """left / right: uint8 (h, w) numpy arrays (pinned=True: views of page-locked memory that stay untouched
-        until the step has run)"""
-        (left, right), stride = _imgs(left, right)
+        """left / right: uint8 (h, w) numpy arrays -- (h, w, 3 | 4) or element-stride-2 views with a colour / interleaved input
+        format, _imgs_fmt -- (pinned=True: views of page-locked memory that stay untouched until the step has run)"""
+        (left, right), stride = _imgs(left, right, fmt=self.input_format)
         self._chk(self.lib.vo_seq_push_pair(self.h, seq, _p(left), _p(right), stride, int(bool(pinned))))
 
     def seq_push_pair_dev(self, seq, left_ptr, right_ptr, stride):

@@ -184,6 +184,7 @@ void vo_default_params(vo_params *p)
     p->mono_rotation = 0;                  // main.cpp:181 passes false
     p->em_prob = 0.999;                    // visualOdometry.cpp:152
     p->em_threshold = 1.0;                 // visualOdometry.cpp:152
+    p->input_format = VO_FMT_GRAY8;
 }
 
 void vo_default_detect_params(vo_detect_params *p)
@@ -420,6 +421,28 @@ int vo_set_params(vo_ctx *c, const vo_params *p)
         p->ransac_iterations > c->ransac_cap || !(p->ransac_confidence > 0 && p->ransac_confidence < 1) ||
         (p->mono_rotation && (!(p->em_prob > 0 && p->em_prob < 1) || !(p->em_threshold > 0))))
         return fail(c, VO_ERR_ARG, "vo_set_params: parameter out of range");
+    if (p->input_format < VO_FMT_GRAY8 || p->input_format > VO_FMT_RGBA8)
+        return fail(c, VO_ERR_ARG, "vo_set_params: input_format is not one of VO_FMT_*");
+    // the staging slots of the synchronous calls hold RAW rows of a non-gray format: they grow when such a format is
+    // configured (a gray context keeps what vo_create allocated) and never shrink
+    const size_t raw = ((size_t)c->max_w * fmt_bpp(p->input_format) * c->max_h + 255) / 256 * 256;
+    if (p->input_format != VO_FMT_GRAY8 && raw > c->stage_slot) {
+        VO_HIP_TRY(c, hipSetDevice(c->device));
+        int rcs = sync_all(c); // a queued pull may still read the old slots
+        if (rcs != VO_OK)
+            return rcs;
+        uint8_t *h_new = nullptr, *d_new = nullptr;
+        VO_HIP_TRY(c, hipHostMalloc((void **)&h_new, raw * VO_STAGE_SLOTS, hipHostMallocMapped));
+        if (hipHostGetDevicePointer((void **)&d_new, h_new, 0) != hipSuccess) {
+            (void)hipHostFree(h_new);
+            return fail(c, VO_ERR_HIP, "vo_set_params: no device address for the staging slots");
+        }
+        (void)hipHostFree(c->h_stage);
+        c->h_stage = h_new;
+        c->d_stage = d_new;
+        c->stage_slot = raw;
+        c->stage_next = 0;
+    }
     c->prm = *p;
     c->n_images = 0; // pyramid plan depends on lk_max_level: force re-configure
     return VO_OK;
@@ -516,8 +539,9 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
         return VO_ERR_ARG;
     if (c->n_images == 0)
         return fail(c, VO_ERR_STATE, "upload before vo_batch_configure");
-    if (idx < 0 || idx >= c->n_images || !src || stride < c->w)
-        return fail(c, VO_ERR_ARG, "vo_batch_upload_image: bad index / stride");
+    const int fmt = c->prm.input_format;
+    if (idx < 0 || idx >= c->n_images || !src || stride < c->w * fmt_bpp(fmt))
+        return fail(c, VO_ERR_ARG, "vo_batch_upload_image: bad index / stride (at least w * bytes per pixel of vo_params.input_format)");
     if (c->seq.on)
         return fail(c, VO_ERR_STATE, "vo_batch_upload_image inside the sequence loop: use vo_seq_push_pair");
     VO_HIP_TRY(c, hipSetDevice(c->device));
@@ -526,6 +550,33 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
     // refuse to read it until VO_STAGE_PYRAMID has covered it again (the contiguous host copy below also
     // overwrites the level-0 border columns with staging bytes)
     c->img_stale[idx] = 1;
+    if (fmt != VO_FMT_GRAY8) {
+        // any other format: the RAW rows go into the page-locked slot (tight, fmt_row_bytes each) and the converting pull kernel
+        // (ingest_fmt.hip) writes the gray rows at the device pitch -- for the synchronous calls and the batch upload alike; a
+        // device source is converted where it lies
+        const void *from = src;
+        int from_stride = stride;
+        const bool with_pts = kind == hipMemcpyHostToDevice && idle && n_pts >= 0;
+        if (kind == hipMemcpyHostToDevice) {
+            const size_t rb = fmt_row_bytes(fmt, c->w);
+            if (c->stage_next == 0 && !idle)
+                VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+            uint8_t *slot = c->h_stage + c->stage_slot * (size_t)c->stage_next;
+            c->stage_next = (c->stage_next + 1) % VO_STAGE_SLOTS;
+            for (int y = 0; y < c->h; y++)
+                memcpy(slot + (size_t)y * rb, (const uint8_t *)src + (size_t)y * stride, rb);
+            if (with_pts && n_pts > 0)
+                memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n_pts);
+            from = c->d_stage + (slot - c->h_stage);
+            from_stride = (int)rb;
+        }
+        hipStream_t st = idle && on ? on : c->stream;
+        if (launch_pull_image_fmt(fmt, from, from_stride, dst, c->lstride[0], c->w, c->h, st, with_pts ? c->d_pts_stage : nullptr,
+                                  with_pts ? c->d_pts : nullptr, with_pts ? n_pts : 0, with_pts ? c->d_npts : nullptr) != 0)
+            return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
+        VO_HIP_TRY(c, hipGetLastError());
+        return VO_OK;
+    }
     if (kind == hipMemcpyHostToDevice) {
         // repack to the device pitch in pinned memory, then one contiguous copy from pixel (0, 0) to the
         // last interior pixel.  The bytes between two rows land in border columns, which the pyramid

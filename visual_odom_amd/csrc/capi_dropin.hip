@@ -36,8 +36,8 @@ int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const ui
         return fail(c, VO_ERR_ARG, "null image / points");
     if (n > c->cap)
         return fail(c, VO_ERR_ARG, "more points than max_pts given to vo_create");
-    if (stride < w) // (before anything changes: a refused call leaves the kept pair as it is)
-        return fail(c, VO_ERR_ARG, "stride smaller than the width");
+    if (stride < w * fmt_bpp(c->prm.input_format)) // (before anything changes: a refused call leaves the kept pair as it is)
+        return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
     if (keep && (c->tf_base < 0 || c->seq.on || c->n_images != 4 || c->n_frames != 1 || c->w != w || c->h != h ||
                  c->img_stale[c->tf_base] || c->img_stale[c->tf_base + 1])) // (stale: the call that uploaded the pair failed before its pyramids were built)
         return fail(c, VO_ERR_STATE, "no t0 images given, and the context does not hold the t1 pair of a previous call of this "
@@ -261,8 +261,8 @@ namespace vo_capi {
 // An image that is given goes to the slot pair that does not hold that t1 pair, which stays valid.
 int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride)
 {
-    if (img && stride < w)
-        return fail(c, VO_ERR_ARG, "stride smaller than the width");
+    if (img && c && stride < w * fmt_bpp(c->prm.input_format))
+        return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
     if (!img && (c->tf_base < 0 || c->seq.on || c->n_images != 4 || c->n_frames != 1 || c->w != w || c->h != h ||
                  c->img_stale[c->tf_base] || c->img_stale[c->tf_base + 1]))
         return fail(c, VO_ERR_STATE, "no image given, and the context does not hold the t1 pair of a previous vo_track_frame "

@@ -170,8 +170,12 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
             q.detect_pending = false;
         }
         VO_HIP_TRY(c, hipMemcpyAsync(d_tab, h_tab, sizeof(SeqIngest) * q.n_ing, hipMemcpyHostToDevice, q.copy));
-        launch_seq_ingest(d_tab, q.n_ing, c->w, c->h, c->lstride[0],
-                          c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, q.copy);
+        if (c->prm.input_format == VO_FMT_GRAY8)
+            launch_seq_ingest(d_tab, q.n_ing, c->w, c->h, c->lstride[0],
+                              c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, q.copy);
+        else if (launch_seq_ingest_fmt(c->prm.input_format, d_tab, q.n_ing, c->w, c->h, c->lstride[0], // (ingest_fmt.hip: converts on the way)
+                                       c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, q.copy) != 0)
+            return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
         if (!dry && q.staged) {
             const int g = (int)(q.step & 1);
             VO_HIP_TRY(c, hipEventRecord(q.ev_stage[g], q.copy));

@@ -273,9 +273,16 @@ struct StageCopy {
     uint8_t *dst;
     const uint8_t *src;
     int stride;
+    int row_bytes = 0; // raw rows of a non-gray input format: bytes copied per row (0: gray, w) and the staging row pitch
+    int dst_pitch = 0;
 };
 static void stage_copy(const StageCopy &k, int w, int h)
 {
+    if (k.row_bytes) {
+        for (int y = 0; y < h; y++)
+            memcpy(k.dst + (size_t)y * k.dst_pitch, k.src + (size_t)y * k.stride, (size_t)k.row_bytes);
+        return;
+    }
     if (k.stride == w)
         memcpy(k.dst, k.src, (size_t)w * h);
     else
@@ -292,8 +299,9 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
         return fail(c, VO_ERR_STATE, "vo_seq_push_pair before vo_seq_configure");
     if (q.broken)
         return fail(c, VO_ERR_STATE, "vo_seq_push_pair: a previous vo_seq_step failed half-way; vo_seq_reset(ctx, -1) first");
-    if (seq < 0 || seq >= q.S || !left || !right || stride < c->w)
-        return fail(c, VO_ERR_ARG, "vo_seq_push_pair: bad sequence / image / stride");
+    const int fmt = c->prm.input_format, bpp = fmt_bpp(fmt);
+    if (seq < 0 || seq >= q.S || !left || !right || stride < c->w * bpp)
+        return fail(c, VO_ERR_ARG, "vo_seq_push_pair: bad sequence / image / stride (at least w * bytes per pixel of vo_params.input_format)");
     if (q.pushed[seq])
         return fail(c, VO_ERR_STATE, "vo_seq_push_pair: this sequence already has a pair for the pending step");
     VO_HIP_TRY(c, hipSetDevice(c->device));
@@ -306,7 +314,7 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
     e.image0 = (r * q.S + seq) * 2;
     if (mode == 0) {
         const int g = (int)(q.step & 1);
-        const size_t img = (size_t)c->w * c->h;
+        const size_t img = (size_t)c->w * c->h * bpp; // (raw bytes: the ingest kernel converts)
         if (!q.h_stage || q.stage_img != img) {
             if (q.h_stage) {
                 VO_HIP_TRY(c, hipStreamSynchronize(q.copy));
@@ -318,7 +326,9 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
             }
             q.stage_img = img;
             VO_HIP_TRY(c, hipHostMalloc((void **)&q.h_stage, img * 2 * 2 * (size_t)q.S, hipHostMallocDefault));
-            if (hipMalloc((void **)&q.d_stage, img * 2 * 2 * (size_t)q.S) != hipSuccess) { // (optional: without it the kernel reads h_stage over PCIe)
+            // the device twin serves the one-transfer path alone (seq_enqueue_inputs: from 32 sequences on); optional even
+            // there: without it the kernel reads h_stage over PCIe
+            if (q.S >= 32 && hipMalloc((void **)&q.d_stage, img * 2 * 2 * (size_t)q.S) != hipSuccess) {
                 (void)hipGetLastError();
                 q.d_stage = nullptr;
             }
@@ -330,16 +340,22 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
         uint8_t *sl = q.h_stage + (((size_t)g * q.S + seq) * 2) * img, *sr = sl + img;
         const uint8_t *srcs[2] = {(const uint8_t *)left, (const uint8_t *)right};
         uint8_t *dsts[2] = {sl, sr};
-        for (int side = 0; side < 2; side++) {
-            const StageCopy k{dsts[side], srcs[side], stride};
+        // an interleaved pair (VO_FMT_GRAY8_X2, right == left + 1) is ONE buffer: staged once, and still a pair the kernel reads once
+        const bool one = fmt == VO_FMT_GRAY8_X2 && srcs[1] == srcs[0] + 1;
+        for (int side = 0; side < (one ? 1 : 2); side++) {
+            StageCopy k{dsts[side], srcs[side], stride};
+            if (fmt != VO_FMT_GRAY8) {
+                k.row_bytes = one ? 2 * c->w : (int)fmt_row_bytes(fmt, c->w);
+                k.dst_pitch = c->w * bpp;
+            }
             if (defer)
                 defer->push_back(k); // (the caller copies the whole step's images at once, in parallel)
             else
                 stage_copy(k, c->w, c->h);
         }
         e.left = sl;
-        e.right = sr;
-        e.stride = c->w;
+        e.right = one ? sl + 1 : sr;
+        e.stride = c->w * bpp;
         q.staged = true;
     } else if (mode == 1) {
         void *dl = nullptr, *dr = nullptr;

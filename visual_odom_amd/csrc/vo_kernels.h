@@ -158,6 +158,12 @@ void launch_bucket(const float2 *d_feat, const float2 *d_corners, const int *d_a
                    int *d_out_n, int out_cap, const int *d_active, int *d_overflow, int n_frames, hipStream_t stream);
 void launch_seq_ingest(const SeqIngest *tab, int n_pairs, int w, int h, int pitch, uint8_t *pix0, size_t img_bytes,
                        bool over_pcie, hipStream_t stream);
+// ingest_fmt.hip: the converting twins of the two calls above for vo_params.input_format != VO_FMT_GRAY8 (src_stride / the
+// table's strides: source bytes per row); -1 = no kernel for this format (nothing was launched)
+int launch_seq_ingest_fmt(int fmt, const SeqIngest *tab, int n_pairs, int w, int h, int pitch, uint8_t *pix0, size_t img_bytes,
+                          bool over_pcie, hipStream_t stream);
+int launch_pull_image_fmt(int fmt, const void *src, int src_stride, void *dst, int pitch, int w, int h, hipStream_t stream,
+                          const void *pts_pinned_dev = nullptr, void *pts_dst = nullptr, int n_pts = 0, int *count_dst = nullptr);
 void launch_seq_prepare(const int *active, const int *n_tracked, int redetect_below, int *detect,
                         const int *n_corners, int *n_new, int n_seq, hipStream_t stream);
 void launch_seq_carry(const int *active, const float2 *outB, const int *nB, const int *idxA, const int *nA,

@@ -25,7 +25,7 @@ class StereoOdometry:
     frame) -- the slowest of the three since round 5 (tools/latency_mode.py: 1.10 / 0.81 / 0.75 ms per frame).  Same results."""
 
     def __init__(self, P_l, P_r, device=0, max_w=1241, max_h=376, max_pts=4096, ctx=None, streaming=False,
-                 mono_rotation=False, keep_pair=True, **detect_kw):
+                 mono_rotation=False, keep_pair=True, input_format=0, **detect_kw):
         self.P_l = np.ascontiguousarray(P_l, np.float32).reshape(3, 4)
         self.P_r = np.ascontiguousarray(P_r, np.float32).reshape(3, 4)
         self.ctx = ctx if ctx is not None else _lib.Context(device, max_w, max_h, max_pts, 1)
@@ -35,7 +35,10 @@ class StereoOdometry:
         self.keep_pair, self._kept, self._kept_id = bool(keep_pair), False, 0
         # trackingFrame2Frame's `mono_rotation` (visualOdometry.h:42; main.cpp:181 passes false)
         self.mono_rotation = bool(mono_rotation)
-        self.ctx.set_params(mono_rotation=int(self.mono_rotation))
+        # _lib.FMT_*: what process() is given -- (h, w) gray by default, (h, w, 3 | 4) colour, or the element-stride-2 planes of
+        # an interleaved frame; the library converts on the device (vo_params.input_format)
+        self.input_format = int(input_format)
+        self.ctx.set_params(mono_rotation=int(self.mono_rotation), input_format=self.input_format)
         self._n_pairs = 0
         # main.cpp:81-94
         self.points = np.zeros((0, 2), np.float32)   # currentVOFeatures.points
@@ -53,7 +56,10 @@ class StereoOdometry:
 
     def process(self, left, right):
         """feed the next stereo pair; returns the per-frame record (None for the very first pair)"""
-        cur = (np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8))
+        if self.input_format == _lib.FMT_GRAY8:
+            cur = (np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8))
+        else:   # as given: the image helpers of _lib check the shape (interleaved planes are views of the caller's buffer, which
+            cur = (np.asarray(left), np.asarray(right))   # must stay unchanged until the next call when keep_pair is off)
         if self.streaming:
             pts, ages, out = self._stream_step(cur)
             if out is None:
@@ -102,7 +108,7 @@ class StereoOdometry:
     def _stream_step(self, cur):
         """device-resident ring of two stereo pairs: slots (0, 1) and (2, 3) of the image table"""
         ctx = self.ctx
-        h, w = cur[0].shape
+        h, w = cur[0].shape[:2]
         slot = 2 * (self._n_pairs % 2)
         if self._n_pairs == 0:
             ctx.batch_configure(4, w, h, 1)
@@ -145,11 +151,11 @@ class MultiSequenceOdometry:
     and, when asked for, the trajectories."""
 
     def __init__(self, P_l, P_r, n_seq, width, height, device=0, max_pts=4096, ring=3, max_steps=1024, ctx=None,
-                 mono_rotation=False, **detect_kw):
+                 mono_rotation=False, input_format=0, **detect_kw):
         self.ctx = ctx if ctx is not None else _lib.Context(device, width, height, max_pts, n_seq)
         self._own = ctx is None
         self.n_seq = n_seq
-        self.ctx.set_params(mono_rotation=int(bool(mono_rotation)))
+        self.ctx.set_params(mono_rotation=int(bool(mono_rotation)), input_format=int(input_format))   # (_lib.FMT_*: what push() is given)
         self.ctx.batch_set_detect_params(**detect_kw)   # before configure: they decide how a step is scheduled
         self.ctx.seq_configure(n_seq, width, height, ring, max_steps)
         self.ctx.batch_set_projection(P_l, P_r)

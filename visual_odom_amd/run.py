@@ -74,6 +74,17 @@ def read_gray(path):
     return bgr_to_gray(rgb[..., ::-1])
 
 
+def read_rgb(path):
+    """--device-convert: the decoded file as it is, (H, W, 3) uint8 RGB (a gray file replicated, like imread(IMREAD_COLOR)) --
+    the library converts it on the device (VO_FMT_RGB8); None if the file does not exist"""
+    if not os.path.exists(path):
+        return None
+    if path.lower().endswith(".pgm"):
+        return np.repeat(read_gray(path)[..., None], 3, axis=2)
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"), np.uint8).copy()
+
+
 def frame_paths(seq_dir, frame_id):
     """image_0/%06d.png, image_1/%06d.png (utils.cpp:174,184); .pgm as a fall-back"""
     out = []
@@ -83,9 +94,10 @@ def frame_paths(seq_dir, frame_id):
     return out
 
 
-def read_pair(seq_dir, frame_id):
+def read_pair(seq_dir, frame_id, rgb=False):
     left_path, right_path = frame_paths(seq_dir, frame_id)
-    left, right = read_gray(left_path), read_gray(right_path)
+    read = read_rgb if rgb else read_gray
+    left, right = read(left_path), read(right_path)
     return (left, right) if left is not None and right is not None else None
 
 
@@ -102,22 +114,27 @@ def main(argv=None):
     ap.add_argument("--decode-threads", type=int, default=8,
                     help="image files of frame k + 1 are read and decoded by this many threads while step k is pushed and runs "
                          "(PIL's decoders release the GIL); 0 = decode on the pushing thread like round 2")
+    ap.add_argument("--device-convert", action="store_true",
+                    help="hand the decoded RGB images to the library as they are (VO_FMT_RGB8: the colour conversion runs on the "
+                         "GPU, in the ingest kernel) instead of converting them to gray here")
     args = ap.parse_args(argv)
 
-    from . import odometry
+    from . import _lib, odometry
+    rgb = bool(args.device_convert)
     dirs = [d for d in args.sequences.split(",") if d]
     gts = args.ground_truth.split(",") if args.ground_truth else []
     cal = read_calibration(args.calibration)
     P_l, P_r = projection_matrices(cal)
-    first = [read_pair(d, 0) for d in dirs]
+    first = [read_pair(d, 0, rgb) for d in dirs]
     if any(p is None for p in first):
         raise SystemExit("cannot read frame 0 of %s" % dirs[[p is None for p in first].index(True)])
-    h, w = first[0][0].shape
-    if any(p[0].shape != (h, w) or p[1].shape != (h, w) for p in first):
+    h, w = first[0][0].shape[:2]
+    if any(p[0].shape[:2] != (h, w) or p[1].shape[:2] != (h, w) for p in first):
         raise SystemExit("all sequences run in one lock-step loop must have the same image size")
     S = len(dirs)
     vo = odometry.MultiSequenceOdometry(P_l, P_r, S, w, h, device=args.device, ring=3, max_steps=args.max_frames + 1,
-                                        mono_rotation=args.mono_rotation, features_per_bucket=args.features_per_bucket)
+                                        mono_rotation=args.mono_rotation, features_per_bucket=args.features_per_bucket,
+                                        input_format=_lib.FMT_RGB8 if rgb else _lib.FMT_GRAY8)
     live = [True] * S
     n_read = [0] * S
     import time
@@ -127,7 +144,7 @@ def main(argv=None):
     def prefetch(frame_id):
         if pool is None or frame_id >= args.max_frames:
             return {}
-        return {s: pool.submit(read_pair, d, frame_id) for s, d in enumerate(dirs) if live[s]}
+        return {s: pool.submit(read_pair, d, frame_id, rgb) for s, d in enumerate(dirs) if live[s]}
 
     t_start = time.perf_counter()
     t_wait = 0.0
@@ -149,14 +166,14 @@ def main(argv=None):
                 pairs[s] = cur[s].result()
                 t_wait += time.perf_counter() - t0
             else:
-                pairs[s] = read_pair(d, frame_id)
+                pairs[s] = read_pair(d, frame_id, rgb)
         if frame_id > 0:  # the frames ahead are decoded while this step is pushed and runs
             queue.append(prefetch(frame_id + depth))
         for s, d in enumerate(dirs):
             if not live[s]:
                 continue
             pair = pairs.get(s)
-            if pair is None or pair[0].shape != (h, w):
+            if pair is None or pair[0].shape[:2] != (h, w):
                 live[s] = False   # the reference runs until imread fails (main.cpp:123, utils.cpp:178)
                 continue
             vo.push(s, pair[0], pair[1])
