@@ -146,6 +146,22 @@ def test_product_library_reads_no_environment_variable():
     # the small-launch form of the pose solve is part of the product (pnp.hip, vo_svd_wide.h)
     for name in (b"epnp_prepare_kernel", b"svd12_wave_kernel", b"epnp_approx_kernel", b"epnp_select_kernel"):
         assert name in blob, name
+    # the sources say the same: what only the developer build compiles lives in csrc/dev/, its hooks inside product sources go
+    # through vo_dev_hooks.h, and the one guard left is the launch of the slim pose chain (two branches in pnp.hip -- a discarded
+    # `if constexpr` would still instantiate the 128-register kernels into the product)
+    csrc = os.path.join(os.path.dirname(build.__file__), "csrc")
+    guards, getenvs = {}, []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")) and f != "vo_dev_hooks.h":
+            text = open(os.path.join(csrc, f)).read()
+            if "VO_DEV_VARIANTS" in text:
+                guards[f] = text.count("VO_DEV_VARIANTS")
+            if "getenv" in text:
+                getenvs.append(f)
+    assert guards in ({}, {"pnp.hip": 1}, {"pnp.hip": 2}), guards
+    assert not getenvs, getenvs
+    for f in build.SOURCES:
+        assert "/" not in f and os.path.exists(os.path.join(csrc, f)), f   # the product is built from csrc/*.hip alone
 
 
 def test_product_library_exports_only_the_header():

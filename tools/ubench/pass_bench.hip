@@ -1,9 +1,10 @@
-// pass_bench.hip -- the product's fused pyramid pass (pyramid.hip, included as is) on a 514-image KITTI table, level by level,
+// pass_bench.hip -- the product's fused pyramid pass (pyramid.hip, included as is through the developer build's wrapper, which
+// adds the store-mode variants pyr_pass_sm_kernel) on a 514-image KITTI table, level by level,
 // outside the library: no tracking kernel, no pose chain, no Python.  Build variants knock parts of the pass out
 // (-DVO_PASS_X=bits: 1 no border items, 2 no next-level stores, 4 no edge items; results are wrong then, the time is the point)
 // to see what each part costs (profiles/r04_experiments.md section 5).
 //   hipcc --offload-arch=gfx950 -O3 -DVO_DEV_VARIANTS -Iinclude -Ivisual_odom_amd/csrc tools/ubench/pass_bench.hip -o /tmp/pass_bench
-#include "../../visual_odom_amd/csrc/pyramid.hip"
+#include "../../visual_odom_amd/csrc/dev/pyramid_dev.hip"
 #include <stdio.h>
 #include <vector>
 #include <string.h>

@@ -9,8 +9,8 @@ import os
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# VO_HIP_LIB: a developer build of the same library (python -m visual_odom_amd.build --dev -> libvo_hip_dev.so, the
-# measured-slower kernel variants and their environment switches compiled in) for tools/ -- never a different backend
+# VO_HIP_LIB: a developer build of the same library (python -m visual_odom_amd.build --dev -> libvo_hip_dev.so: the product
+# sources plus csrc/dev/, the measured-slower kernel variants and their environment switches) for tools/ -- never a different backend
 SO_PATH = os.environ.get("VO_HIP_LIB") or os.path.join(HERE, "libvo_hip.so")
 
 VO_OK, VO_ERR_ARG, VO_ERR_HIP, VO_ERR_STATE, VO_ERR_TOO_FEW, VO_ERR_OVERFLOW = 0, -1, -2, -3, -4, -5

@@ -110,11 +110,7 @@ bool ensure_partitioned_streams(StreamSet *s, int device)
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess)
         return false;
-    int n_cu = prop.multiProcessorCount, pose_cus = n_cu / 2;
-#ifdef VO_DEV_VARIANTS
-    if (const char *e = getenv("VO_POSE_CUS")) // developer build: 0 = no partition, n = CUs of the pose side
-        pose_cus = atoi(e);
-#endif
+    const int n_cu = prop.multiProcessorCount, pose_cus = dev_knob("VO_POSE_CUS", n_cu / 2); // (developer build: 0 = no partition, n = CUs of the pose side)
     if (n_cu < 16 || n_cu > 1024 || pose_cus <= 0 || pose_cus >= n_cu)
         return false;
     std::vector<uint32_t> pose_mask((size_t)(n_cu + 31) / 32, 0u), trk_mask(pose_mask.size(), 0u);
@@ -287,17 +283,9 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     for (auto &ev : c->ev_trk_free)
         ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&c->ev_t1_ready, hipEventDisableTiming) == hipSuccess;
-#ifdef VO_DEV_VARIANTS
-    // developer build only (python -m visual_odom_amd.build --dev -> libvo_hip_dev.so): VO_SERIAL_POSE=1 enqueues the pose
-    // solve on the tracking stream (no overlap), so that a kernel trace shows every kernel's stand-alone duration;
-    // VO_LK_PAIR=1 selects the measured-slower two-features-per-wavefront LK kernel
-    {
-        const char *e = getenv("VO_SERIAL_POSE");
-        c->serial_pose = e && e[0] == '1';
-        const char *elp = getenv("VO_LK_PAIR");
-        c->lk_pair = elp && elp[0] == '1';
-    }
-#endif
+    // developer build: VO_SERIAL_POSE=1 enqueues the pose solve on the tracking stream (no overlap), so that a kernel trace shows
+    // every kernel's stand-alone duration
+    c->serial_pose = dev_knob("VO_SERIAL_POSE", 0) == 1;
     for (auto &e : c->ev)
         ok = ok && hipEventCreate(&e) == hipSuccess;
     c->ring.assign((size_t)VO_EVENT_SLOTS * (VO_EV_PER_RUN), nullptr);
@@ -351,9 +339,8 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
                                            VO_EPNP_WS_HYPS * VO_EPNP_WS_DOUBLES) == hipSuccess;
         ok = ok && dmalloc(&b.rest_ws, (size_t)(c->max_frames < VO_EPNP_WS_MAX_FRAMES ? c->max_frames : VO_EPNP_WS_MAX_FRAMES) *
                                            pnp_rest_ws_doubles(c->ransac_cap)) == hipSuccess;
-#ifdef VO_DEV_VARIANTS
-        ok = ok && dmalloc(&b.epnp_gws, B * VO_EPNP_GWS_BLOCKS * VO_EPNP_UT_DOUBLES * 64) == hipSuccess;
-#endif
+        if (VO_DEV_MAX_POSE_WAVES >= 4) // the slim pose chain's workspace (pnp.hip)
+            ok = ok && dmalloc(&b.epnp_gws, B * VO_EPNP_GWS_BLOCKS * VO_EPNP_UT_DOUBLES * 64) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&b.ready, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&b.tri_done, hipEventDisableTiming) == hipSuccess;

@@ -1,21 +1,8 @@
 // capi_dropin.hip -- the synchronous drop-in calls (host buffers in, host buffers out): vo_circular_match, vo_triangulate,
 // vo_pnp_ransac, vo_fast_detect, vo_detect_bucket, vo_integrate_odometry, vo_track_frame.
 #include "capi_internal.h"
-#ifdef VO_DEV_VARIANTS
-#include <chrono>
-#endif
 
 namespace vo_capi {
-
-#ifdef VO_DEV_VARIANTS
-// developer build: host-side time stamps of the last vo_track_frame (ns, steady clock): [0] entry, [1] configure + sync_all
-// done, [2..5] image k staged and its copy enqueued, [6] points enqueued, [7] run_stages returned (everything enqueued),
-// [8] the final stream synchronisation returned, [9] results copied out (tools/host_gap_probe.py)
-long long g_host_stamp[16];
-#define VO_HOST_STAMP(k) (g_host_stamp[k] = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count())
-#else
-#define VO_HOST_STAMP(k) ((void)0)
-#endif
 
 /* ---------------------------------- drop-in calls ---------------------------------------- */
 
@@ -65,11 +52,8 @@ int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const ui
     // 0.60 -> 0.58 at 340 (gpurun_out/r6_split1).  Not with four images: two chain launches end on their slowest feature twice
     // (hop 0 alone 74 - 82 us, hops 1 .. 3 172 - 190, the whole chain 200 - 236) and the t0 pyramids become a launch set of their
     // own (27 us) -- measured 0.68 -> 0.70 ms, so four images go the way they always went.
-    bool split = defer_t1 && keep;
-#ifdef VO_DEV_VARIANTS
-    static const int split_env = [] { const char *e = getenv("VO_SYNC_SPLIT"); return e ? atoi(e) : 1; }();
-    split = split && split_env != 0 && !c->lk_pair;
-#endif
+    // (developer build: VO_SYNC_SPLIT=0 is the A/B partner; the split chain runs lk_hops_kernel, so VO_LK_PAIR=1 keeps to one launch)
+    const bool split = defer_t1 && keep && dev_knob("VO_SYNC_SPLIT", 1) != 0 && dev_knob("VO_LK_PAIR", 0) != 1;
     for (int i = keep ? 2 : 0; i < (split ? 2 : 4); i++) { // the points travel with the last image
         rc = upload_image(c, (i < 2 ? t0 : t1) + (i & 1), imgs[i], stride, hipMemcpyHostToDevice, /*idle*/ true, pts, i == 3 ? n : -1);
         if (rc != VO_OK)
@@ -135,7 +119,7 @@ int vo_circular_match(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uin
     g.n = status4 ? n : 0;
     g.cap = c->cap;
     g.consistency = apply_consistency ? 1 : 0;
-    if (!c->last_run_serial) { // (developer build, VO_SYNC_SERIAL=0: the filter ran on its own stream and this call has no
+    if (!c->last_run_serial) { // (a run on the batch mode's streams: the filter ran on its own stream and this call has no
                                // pose stage whose event would order the gather behind it -- ADVICE r05)
         rc = sync_all(c);
         if (rc != VO_OK)
@@ -483,27 +467,4 @@ int vo_track_frame(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_
     return r.status == 1 ? VO_OK : VO_NO_MODEL;
 }
 
-#ifdef VO_DEV_VARIANTS
-// developer build only: the 100 MHz stamps the pose kernels left for frame 0 / hypothesis 0 (pnp.hip, tools/pose_phases.py)
-int vo_dev_host_stamps(long long *out16)
-{
-    if (!out16)
-        return VO_ERR_ARG;
-    memcpy(out16, g_host_stamp, sizeof(g_host_stamp));
-    return VO_OK;
-}
-
-int vo_dev_pose_prof(vo_ctx *c, long long *out64)
-{
-    if (!c || !out64 || sync_all(c) != VO_OK)
-        return VO_ERR_ARG;
-    return vo::pose_prof_read(out64) == 0 ? VO_OK : VO_ERR_HIP;
-}
-
 } // extern "C"
-
-namespace vo_capi {
-
-#endif
-
-} // namespace vo_capi

@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/vo_hip.h"
 #include "vo_kernels.h"
+#include "vo_dev_hooks.h"
 #include "vo_integrate.h"
 #include "vo_linalg.h"
 
@@ -172,8 +173,7 @@ struct vo_ctx {
     // shares the context with others can tell whether the pair on the device is still the one ITS last call left
     int64_t tf_gen = 0;
     bool last_run_serial = true; // the last run_stages put everything on the tracking stream (else: sync_all before a gather)
-    bool serial_pose = false; // -DVO_DEV_VARIANTS + VO_SERIAL_POSE=1: the whole chain on the tracking stream (profiling)
-    bool lk_pair = false;     // -DVO_DEV_VARIANTS + VO_LK_PAIR=1: the two-features-per-wavefront LK kernel (lk.hip)
+    bool serial_pose = false; // developer build + VO_SERIAL_POSE=1 (vo_dev_hooks.h): the whole chain on the tracking stream (profiling)
     // pinned staging for host images: rows are repacked to the device pitch on the host and go over
     // PCIe as ONE contiguous copy (a pitched copy from pageable memory moves row by row: 3.3 ms per
     // 1241 x 376 image measured, tools/latency_mode.py)
@@ -304,12 +304,6 @@ hipError_t dmalloc(T **p, size_t n)
 {
     return hipMalloc((void **)p, n * sizeof(T));
 }
-
-#ifdef VO_DEV_VARIANTS
-namespace vo {
-int pose_prof_read(long long *out64); // pnp.hip
-}
-#endif
 
 constexpr int EM_MAX_ITERS = 1000; // maxIters of the findEssentialMat overload the reference calls (OpenCV 4.5)
 

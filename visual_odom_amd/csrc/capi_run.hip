@@ -58,18 +58,7 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
         if (ni > 0) {
             // One launch per level, no LDS (round 4): a level is read once and gives its Scharr image, the next level and its
             // own border (pyramid.hip).  (Round 3: eight launches of three kernels that each fetched the level again.)
-#ifdef VO_DEV_VARIANTS
-            static const bool fused = [] { const char *e = getenv("VO_PYR_FUSED"); return !(e && e[0] == '0'); }();
-            if (!fused) {
-                launch_border_fill(tab, ni, 0, 1, c->lstride, c->lh, pyrs);
-                launch_scharr(tab, ni, 0, 1, c->lw, c->lh, pyrs);
-                for (int l = 0; l + 1 < c->levels; l++)
-                    launch_pyr_down(tab, ni, l, c->lw[l + 1], c->lh[l + 1], pyrs);
-                launch_border_fill(tab, ni, 1, c->levels, c->lstride, c->lh, pyrs);
-                launch_scharr(tab, ni, 1, c->levels, c->lw, c->lh, pyrs);
-            } else
-#endif
-                launch_pyramid_fused(tab, ni, c->levels, c->lw, c->lh, c->lstride, pyrs);
+            launch_pyramid_fused(tab, ni, c->levels, c->lw, c->lh, c->lstride, pyrs);
             std::fill(c->img_stale.begin() + c->pyr_first, c->img_stale.begin() + c->pyr_first + ni, (uint8_t)0);
         }
     }
@@ -196,12 +185,6 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             launch_lk_hops(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
                            c->d_status2[wset], lp, 1, 4, c->stream);
         } else
-#ifdef VO_DEV_VARIANTS
-        if (c->lk_pair)
-            launch_lk_circular_pair(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
-                                    c->d_status2[wset], lp, c->stream);
-        else
-#endif
             launch_lk_circular(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
                                c->d_status2[wset], lp, c->stream);
         c->trk_last = wset;
@@ -226,12 +209,7 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
     // for the filter to have consumed the points / tracks / status it is about to overwrite.
     // A synchronous drop-in call (vo_track_frame) has nothing to overlap with: everything on the tracking stream saves the
     // three cross-stream hand-offs of the chain (~12 us each in the kernel timeline of one call).
-    bool serial = c->serial_pose || (c->sync_call && !sq.on);
-#ifdef VO_DEV_VARIANTS
-    static const int sync_serial_env = [] { const char *e = getenv("VO_SYNC_SERIAL"); return e ? atoi(e) : -1; }();
-    if (sync_serial_env == 0 && !c->serial_pose)
-        serial = false; // A/B: the synchronous call on the batch mode's streams
-#endif
+    const bool serial = c->serial_pose || (c->sync_call && !sq.on);
     c->last_run_serial = serial;
     hipStream_t fs = serial ? c->stream : c->stream_filter;
     const bool two_pose_streams = !serial && !c->prm.mono_rotation && c->sched.streams == 2;

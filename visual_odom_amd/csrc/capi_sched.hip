@@ -160,11 +160,8 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
             else
                 (void)hipGetLastError(); // (a step without an LK stage left no such events)
         }
-#ifdef VO_DEV_VARIANTS
-        static const int wait_env = [] { const char *e = getenv("VO_INGEST_WAIT"); return e ? atoi(e) : -1; }(); // A/B: 0 / 1 force
-        if (wait_env >= 0)
-            wait_detect = wait_env != 0;
-#endif
+        if (dev_knob("VO_INGEST_WAIT", -1) >= 0) // A/B: 0 / 1 force
+            wait_detect = dev_knob("VO_INGEST_WAIT", -1) != 0;
         if (wait_detect && over_pcie && !dry && !c->sched.prep && q.detect_pending) {
             VO_HIP_TRY(c, hipStreamWaitEvent(q.copy, q.ev_detect, 0));
             q.detect_pending = false;
@@ -380,13 +377,7 @@ int vo_set_schedule(vo_ctx *c, const vo_schedule *s)
         p = *s;
     if (p.epnp_wide_frames != 0 && p.epnp_wide_frames != VO_EPNP_SPLIT_DEFAULT_FRAMES && p.epnp_wide_frames != VO_EPNP_WS_MAX_FRAMES)
         return fail(c, VO_ERR_ARG, "vo_set_schedule: epnp_wide_frames 0 / 4 / 16");
-    const int max_waves =
-#ifdef VO_DEV_VARIANTS
-        4; // the slim pose chain (pnp.hip): measured slower everywhere, kept for the record in the developer build
-#else
-        2;
-#endif
-    if (p.pose_waves < 0 || p.pose_waves == 3 || p.pose_waves > max_waves || p.pose_streams < 0 || p.pose_streams > 2 ||
+    if (p.pose_waves < 0 || p.pose_waves == 3 || p.pose_waves > VO_DEV_MAX_POSE_WAVES || p.pose_streams < 0 || p.pose_streams > 2 ||
         p.prepare < -1 || p.prepare > 1)
         return fail(c, VO_ERR_ARG, "vo_set_schedule: pose_waves 0 / 1 / 2, pose_streams 0 / 1 / 2, prepare -1 / 0 / 1");
     int rc = sync_all(c);
@@ -461,15 +452,9 @@ int vo_import_schedule(const vo_schedule_record *recs, int n)
 {
     if (n < 0 || (n > 0 && !recs))
         return VO_ERR_ARG;
-    const int max_waves =
-#ifdef VO_DEV_VARIANTS
-        4;
-#else
-        2;
-#endif
     for (int k = 0; k < n; k++) { // validate everything before anything is taken over
         const vo_schedule &sc = recs[k].schedule;
-        if ((sc.pose_waves != 1 && sc.pose_waves != 2 && !(sc.pose_waves == 4 && max_waves == 4)) ||
+        if ((sc.pose_waves != 1 && sc.pose_waves != 2 && !(sc.pose_waves == 4 && VO_DEV_MAX_POSE_WAVES == 4)) ||
             (sc.pose_streams != 1 && sc.pose_streams != 2) || (sc.prepare != 0 && sc.prepare != 1) ||
             (sc.epnp_wide_frames != VO_EPNP_SPLIT_DEFAULT_FRAMES && sc.epnp_wide_frames != VO_EPNP_WS_MAX_FRAMES) || recs[k].key[0] < 0 ||
             recs[k].key[2] < 32 || recs[k].key[3] < 32 || recs[k].key[4] < 1 || recs[k].key[4] > VO_MAX_LEVELS || recs[k].key[5] < 1)

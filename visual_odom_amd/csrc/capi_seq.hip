@@ -248,11 +248,8 @@ int seq_begin_step(vo_ctx *c)
     // has to be under way while step k runs): 64 sequences from page-locked memory 41.8 / 42.0 / 38.7 k at 8 / 4 / 3 steps,
     // 8 sequences 12.4 / 14.6 / 14.4 k (gpurun_out/r6_ra2, r6_ra3).  (q.ing_pcie still describes the previous step here.)
     int ahead = q.ing_pcie ? VO_SEQ_RUNAHEAD + 1 : VO_SEQ_RUNAHEAD;
-#ifdef VO_DEV_VARIANTS
-    static const int ahead_env = [] { const char *e = getenv("VO_SEQ_RUNAHEAD"); return e ? atoi(e) : 0; }(); // A/B: 1 .. 8
-    if (ahead_env > 0)
-        ahead = ahead_env;
-#endif
+    if (dev_knob("VO_SEQ_RUNAHEAD", 0) > 0) // A/B: 1 .. 8
+        ahead = dev_knob("VO_SEQ_RUNAHEAD", 0);
     if (ahead < VO_SEQ_INFLIGHT && q.step >= ahead) {
         const int s3 = (int)((q.step - ahead) % VO_SEQ_INFLIGHT);
         if (q.step_pending[s3]) {

@@ -23,22 +23,7 @@
 //                              because rvec/tvec are shared buffers), inlier mask, the CvLevMarq
 //                              state machine with block-wide reductions of J^T J / J^T e, rvec -> R.
 #include "vo_kernels.h"
-#ifdef VO_DEV_VARIANTS
-// developer build: 100 MHz time stamps of one EPnP hypothesis / one refinement (tools/pose_phases.py)
-__device__ long long g_pose_prof[64];
-#ifdef __HIP_DEVICE_COMPILE__
-#define VO_EPNP_STAMP(i)                                                      \
-    do {                                                                      \
-        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {         \
-            g_pose_prof[i] = (long long)wall_clock64();                       \
-        }                                                                     \
-    } while (0)
-#define VO_POSE_NOW() ((long long)wall_clock64())
-#endif
-#endif
-#ifndef VO_POSE_NOW
-#define VO_POSE_NOW() 0ll
-#endif
+#include "vo_dev_hooks.h" // VO_EPNP_STAMP / VO_POSE_PROF: time stamps of the developer build (dev/pnp_dev.hip), nothing in the product
 #include "vo_epnp.h"
 #include "vo_svd_wide.h"
 #include "vo_p3p.h"
@@ -47,7 +32,6 @@ __device__ long long g_pose_prof[64];
 #include <mutex>
 
 #include <float.h>
-#include <stdlib.h>
 
 // Register budget of the two f64-heavy kernels, as minimum waves per SIMD (launch_bounds' second
 // argument), a template parameter with two instantiations:
@@ -680,12 +664,8 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
     const int frame = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int count = n_pts[frame];
     PnpResult &res = results[frame];
-#ifdef VO_DEV_VARIANTS
-    const bool prof = frame == 0 && tid == 0;
-    long long t_solve = 0, n_solve = 0, t_pass[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (prof)
-        g_pose_prof[16] = VO_POSE_NOW();
-#endif
+    VO_POSE_PROF(const bool prof = frame == 0 && tid == 0; long long t_solve = 0, n_solve = 0, t_pass[8] = {0, 0, 0, 0, 0, 0, 0, 0};)
+    VO_POSE_PROF(if (prof) g_pose_prof[16] = VO_POSE_NOW();)
     if (count < 5) {
         if (tid == 0) {
             if (count == 4) { // OpenCV's SOLVEPNP_P3P switch: the whole solve by one thread (round 5: a kernel of its own in
@@ -778,10 +758,7 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
         }
     }
     const int n1 = s_ninl;
-#ifdef VO_DEV_VARIANTS
-    if (prof)
-        g_pose_prof[17] = VO_POSE_NOW();
-#endif
+    VO_POSE_PROF(if (prof) g_pose_prof[17] = VO_POSE_NOW();)
 
     // ---- CvLevMarq (cvFindExtrinsicCameraParams2, useExtrinsicGuess) from the LAST hypothesis ----
     // Thread 0 runs the solver's state machine; what it asks for is done by the workgroup:
@@ -815,9 +792,7 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
     };
 
     for (;;) {
-#ifdef VO_DEV_VARIANTS
-        const long long t_in = VO_POSE_NOW();
-#endif
+        VO_POSE_PROF(const long long t_in = VO_POSE_NOW();)
         if (tid == 0) {
             int want_J = 0, want_err = 0, proceed = 1, need_solve = 0;
             if (state == LM_DONE) {
@@ -891,10 +866,7 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
                     s_param[k] = prevParam[k] - x[k];
             }
             __syncthreads();
-#ifdef VO_DEV_VARIANTS
-            t_solve += VO_POSE_NOW() - t_in;
-            n_solve++;
-#endif
+            VO_POSE_PROF(t_solve += VO_POSE_NOW() - t_in; n_solve++;)
         }
         if (!s_flags[0])
             break;
@@ -905,18 +877,13 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
 #pragma unroll
         for (int k = 0; k < LM_NRED; k++)
             acc[k] = 0;
-#ifdef VO_DEV_VARIANTS
-        const long long tp0 = VO_POSE_NOW();
-        long long tp1 = 0, tp2 = 0;
-#endif
+        VO_POSE_PROF(const long long tp0 = VO_POSE_NOW(); long long tp1 = 0, tp2 = 0;)
         {
             double R[9], dRdr[27];
             const double rv[3] = {s_param[0], s_param[1], s_param[2]};
             const double t[3] = {s_param[3], s_param[4], s_param[5]};
             rodrigues_v2m(rv, R, want_J ? dRdr : nullptr);
-#ifdef VO_DEV_VARIANTS
-            tp1 = VO_POSE_NOW();
-#endif
+            VO_POSE_PROF(tp1 = VO_POSE_NOW();)
             // (the point of the NEXT round is fetched -- index, then coordinates: two dependent loads -- while this one's
             // projection is computed: the loop was bound by that latency, 1.3 us per point)
             int k = tid;
@@ -958,9 +925,7 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
                 }
             }
         }
-#ifdef VO_DEV_VARIANTS
-        tp2 = VO_POSE_NOW();
-#endif
+        VO_POSE_PROF(tp2 = VO_POSE_NOW();)
         // ---- sum over the workgroup, in a fixed order: thread-major partial sums in LDS (row pitch 29: neighbouring threads
         // land in different banks), 8 x 28 threads add 32 of them each, 28 threads the 8 results.  (Butterfly sums through
         // ds_bpermute -- 12 per value and level set, 28 values -- took 6 us per pass, eight passes per frame.)
@@ -989,15 +954,13 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
             s_sum[tid] = sum;
         }
         __syncthreads();
-#ifdef VO_DEV_VARIANTS
-        if (prof) { // [22 + 4 j ..]: rodrigues, point loop, reduction, count -- j = 1 for passes with the Jacobian
+        VO_POSE_PROF(if (prof) { // [22 + 4 j ..]: rodrigues, point loop, reduction, count -- j = 1 for passes with the Jacobian
             const int o = want_J ? 4 : 0;
             t_pass[o] += tp1 - tp0;
             t_pass[o + 1] += tp2 - tp1;
             t_pass[o + 2] += VO_POSE_NOW() - tp2;
             t_pass[o + 3] += 1;
-        }
-#endif
+        })
     }
 
     if (tid == 0) {
@@ -1012,16 +975,14 @@ __device__ __forceinline__ void select_refine_frame(const float *__restrict__ xy
         res.best_iter = best;
         res.max_good = s_maxgood;
         res.lm_iters = iters;
-#ifdef VO_DEV_VARIANTS
-        if (prof) {
+        VO_POSE_PROF(if (prof) {
             g_pose_prof[18] = t_solve;
             g_pose_prof[19] = n_solve;
             g_pose_prof[20] = VO_POSE_NOW();
             g_pose_prof[21] = n1;
             for (int k = 0; k < 8; k++)
                 g_pose_prof[22 + k] = t_pass[k];
-        }
-#endif
+        })
     }
 }
 
@@ -1094,24 +1055,14 @@ void launch_pnp_ransac(const float *xyz, const float2 *uv, size_t uv_stride, con
     // other kernel that uses LDS at all (pyr_down, FAST, LK with 1.9 KB per wave) can start a workgroup there until one of
     // them retires: when the chain starts on an idle GPU, the next LDS-using kernel of the tracking stream sits behind it
     // for ~0.6 ms (round-2 trace of the lock-step loop, 256 sequences).  Capping the solver at ONE workgroup per CU by asking
-    // for more than half of the LDS (VO_EPNP_LDS_KB=82, developer build) was measured and is worse -- the chain gets longer
-    // than two steps -- so the tracking stream instead starts each step with its LDS-free kernels (capi.hip, PYRAMID stage).
-    static const size_t lds = [] {
-        size_t need = (144 + 12) * 64 * sizeof(double), want = 0;
-#ifdef VO_DEV_VARIANTS
-        if (const char *e = getenv("VO_EPNP_LDS_KB"))
-            want = (size_t)atoi(e) * 1024;
-#endif
-        return want > need ? want : need;
-    }();
+    // for more than half of the LDS (82 KB) was measured and is worse -- the chain gets longer than two steps
+    // (profiles/HISTORY.md) -- so the tracking stream instead starts each step with its LDS-free kernels (capi.hip, PYRAMID stage).
+    const size_t lds = (144 + 12) * 64 * sizeof(double);
     // Small launches: the four-kernel form (epnp_prepare_kernel ...) for the first chunk; the rarely needed second chunk stays
     // with the one kernel (four launches that mostly find nothing to do would cost more than they save).
     int split_max = wide_frames > 0 ? wide_frames : VO_EPNP_SPLIT_DEFAULT_FRAMES;
-#ifdef VO_DEV_VARIANTS
-    static const int split_env = [] { const char *e = getenv("VO_EPNP_SPLIT_MAX"); return e ? atoi(e) : -1; }();
-    if (split_env >= 0)
-        split_max = split_env;
-#endif
+    if (dev_knob("VO_EPNP_SPLIT_MAX", -1) >= 0)
+        split_max = dev_knob("VO_EPNP_SPLIT_MAX", -1);
     const bool split = epnp_ws && n_frames <= split_max && n_frames <= ws_frames;
     // First chunk: 128 hypotheses cover what OpenCV's adaptive count asks for down to ~55 % inliers in ONE round of dependent
     // launches -- right where the chain's latency counts.  From 128 frames on the chain is hidden behind the next run's
@@ -1120,11 +1071,8 @@ void launch_pnp_ransac(const float *xyz, const float2 *uv, size_t uv_stride, con
     // batch, ms per step with 128 | 64 | 32: 12.84 | 12.55 | 13.83 at ~2000 points, 3.57 | 3.18 | 3.64 at 340; lock-step loop
     // 256 sequences 4.03 | 4.04 | 4.23, 64 sequences 1.25 | 1.39 | 1.41 -- profiles/r03_pose_chain_experiments.md).
     int first_chunk = n_frames >= 128 ? 64 : RANSAC_CHUNK;
-#ifdef VO_DEV_VARIANTS
-    static const int chunk_env = [] { const char *e = getenv("VO_RANSAC_CHUNK"); return e ? atoi(e) : 0; }();
-    if (chunk_env > 0 && chunk_env <= RANSAC_CHUNK && !split)
-        first_chunk = chunk_env;
-#endif
+    if (const int chunk = dev_knob("VO_RANSAC_CHUNK", 0); chunk > 0 && chunk <= RANSAC_CHUNK && !split)
+        first_chunk = chunk;
     for (int h0 = 0; h0 < prm.iters;) {
         const int hn = h0 == 0 ? min(first_chunk, prm.iters) : prm.iters - h0;
         const dim3 eg((hn + 63) / 64, n_frames);
@@ -1143,26 +1091,15 @@ void launch_pnp_ransac(const float *xyz, const float2 *uv, size_t uv_stride, con
                                epnp_ws);
             hipLaunchKernelGGL(epnp_select_kernel, eg, dim3(64), 0, stream, n_pts, prm, state, h0, hn, epnp_ws, models);
         } else
-#ifdef VO_DEV_VARIANTS
+#ifdef VO_DEV_VARIANTS // (a preprocessor guard, not a constant: a discarded branch would still put the kernel into the product)
         if (waves >= 4 && gws && (int)eg.x <= VO_EPNP_GWS_BLOCKS) {
             // SLIM (round-4 experiment, developer build only): 12 x 12 matrices in a global workspace, VO_SLIM_WAVES waves per
             // SIMD worth of registers, no LDS -- such a wave starts wherever ONE LK wave has retired instead of waiting for half
             // an empty SIMD and 78 KB of LDS.  Bit-identical, and SLOWER in every configuration measured
             // (profiles/r04_experiments.md: headline step 12.45 -> 12.68 ms, 340-point step 3.15 -> 3.32 ... 3.72, lock-step loop
             // 3.71 -> 4.10): the scratch-resident solver takes 2 x as long and costs LK more than the fat one does.
-            static const int sw = [] { const char *e = getenv("VO_SLIM_WAVES"); return e ? atoi(e) : VO_SLIM_WAVES; }();
-            if (sw == 4)
-                hipLaunchKernelGGL((epnp_kernel<4, true>), eg, dim3(64), 0, stream, xyz, uv, uv_stride, n_pts, cap, subsets, prm,
-                                   state, h0, hn, models, gws);
-            else if (sw == 5)
-                hipLaunchKernelGGL((epnp_kernel<5, true>), eg, dim3(64), 0, stream, xyz, uv, uv_stride, n_pts, cap, subsets, prm,
-                                   state, h0, hn, models, gws);
-            else if (sw == 7)
-                hipLaunchKernelGGL((epnp_kernel<7, true>), eg, dim3(64), 0, stream, xyz, uv, uv_stride, n_pts, cap, subsets, prm,
-                                   state, h0, hn, models, gws);
-            else
-                hipLaunchKernelGGL((epnp_kernel<VO_SLIM_WAVES, true>), eg, dim3(64), 0, stream, xyz, uv, uv_stride, n_pts, cap,
-                                   subsets, prm, state, h0, hn, models, gws);
+            hipLaunchKernelGGL((epnp_kernel<VO_SLIM_WAVES, true>), eg, dim3(64), 0, stream, xyz, uv, uv_stride, n_pts, cap, subsets,
+                               prm, state, h0, hn, models, gws);
         } else
 #endif
         if (waves >= 2)
@@ -1211,12 +1148,5 @@ void launch_pnp(const float *xyz, const float2 *uv, size_t uv_stride, const int 
 }
 
 #endif // VO_HOST_EMUL
-
-#ifdef VO_DEV_VARIANTS
-int pose_prof_read(long long *out64)
-{
-    return hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_pose_prof), sizeof(long long) * 64) == hipSuccess ? 0 : -1;
-}
-#endif
 
 } // namespace vo

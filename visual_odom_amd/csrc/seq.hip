@@ -14,7 +14,7 @@
 //   (the pose tail -- rotationMatrixToEulerAngles + gates + integrateOdometryStereo, main.cpp:196-208, utils.cpp:57-131,
 //    one trajectory row per processed frame -- runs inside select_refine_kernel: vo_seqtail.h)
 #include "vo_kernels.h"
-#include <stdlib.h>
+#include "vo_dev_hooks.h"
 
 namespace vo {
 
@@ -136,10 +136,8 @@ void launch_seq_ingest(const SeqIngest *tab, int n_pairs, int w, int h, int pitc
     if (n_pairs <= 0)
         return;
     int want = over_pcie ? 192 : 8192;
-#ifdef VO_DEV_VARIANTS
-    if (const char *e = getenv(over_pcie ? "VO_INGEST_WAVES" : "VO_INGEST_WAVES_DEV")) // developer build: A/B of the grid size
-        want = atoi(e) > 0 ? atoi(e) : want;
-#endif
+    if (over_pcie && dev_knob("VO_INGEST_WAVES", 0) > 0) // developer build: A/B of the grid size
+        want = dev_knob("VO_INGEST_WAVES", 0);
     const int n_rows = 2 * n_pairs * h;
     const int n_waves = n_rows < want ? n_rows : want;
     hipLaunchKernelGGL(seq_ingest_kernel, dim3(n_waves), dim3(64), 0, stream, tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes);

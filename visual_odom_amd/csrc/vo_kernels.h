@@ -118,13 +118,6 @@ struct EmBufs {
     uint8_t *mask = nullptr;              // [B][cap]
 };
 
-#ifdef VO_DEV_VARIANTS // the round-3 three-kernel pyramid chain (A/B partner of launch_pyramid_fused, VO_PYR_FUSED=0)
-void launch_border_fill(const PyrImage *d_imgs, int n_images, int first_level, int n_levels, const int *lstride,
-                        const int *lh, hipStream_t stream);
-void launch_pyr_down(const PyrImage *d_imgs, int n_images, int level, int dw, int dh, hipStream_t stream);
-void launch_scharr(const PyrImage *d_imgs, int n_images, int first_level, int n_levels, const int *lw, const int *lh,
-                   hipStream_t stream);
-#endif
 void launch_pyramid_fused(const PyrImage *d_imgs, int n_images, int n_levels, const int *lw, const int *lh, const int *lstride,
                           hipStream_t stream);
 // pyramid.hip: a staged host image over PCIe by a kernel (+ optionally n_pts float2 and their count from pinned memory)
@@ -137,11 +130,6 @@ void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_trk, uint8_t *d_status, const LkParams &prm, int hop_begin, int hop_end,
                     hipStream_t stream);
-#ifdef VO_DEV_VARIANTS
-void launch_lk_circular_pair(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
-                        int cap, int max_pts, int n_frames, float2 *d_trk, uint8_t *d_status,
-                        const LkParams &prm, hipStream_t stream);
-#endif
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,
                           int h, int threshold, int nonmax, unsigned long long *d_nmsmask,
                           int *d_rowcnt, int *d_rowoff,
