@@ -55,11 +55,12 @@ bool acquire_streams(int device, StreamSet *out)
             return true;
         }
     }
-    StreamSet s;
+    StreamSet set;
     if (device < VO_MAX_DEVICES) {
         std::lock_guard<std::mutex> lk(g_pool_mu);
-        s.id = g_pool_created[device]++;
+        set.id = g_pool_created[device]++;
     }
+    Streams &s = set.plain;
     bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
     // the post-LK streams carry a few hundred waves next to LK's hundred thousand: at equal priority
     // their kernels trickle in behind LK's workgroups (pose chain 1.1 ms alone, 5-10 ms next to LK) and
@@ -70,22 +71,20 @@ bool acquire_streams(int device, StreamSet *out)
     ok = ok && hipStreamCreateWithPriority(&s.pnp2, hipStreamNonBlocking, greatest) == hipSuccess;
     ok = ok && hipStreamCreateWithPriority(&s.filter, hipStreamNonBlocking, greatest) == hipSuccess;
     ok = ok && hipStreamCreateWithPriority(&s.em, hipStreamNonBlocking, greatest) == hipSuccess;
-    *out = s;
+    *out = set;
     return ok;
 }
 
-// The lock-step loop's copy stream, created the first time a context of this set needs it.  Two flavours: the PREPARE
-// stream has the highest priority (it carries the new pairs' pyramids and FAST besides the ingest kernel, short
+// The lock-step loop's ingest stream (copy or prepare), created the first time a context of this set needs it.  Two flavours: the
+// PREPARE stream has the highest priority (it carries the new pairs' pyramids and FAST besides the ingest kernel, short
 // memory-bound kernels that have to find SIMD slots between the running step's LK waves); the plain COPY stream only
 // carries the ingest kernel and keeps the default priority -- at the highest priority that kernel runs into the current
 // step's pyramid / detection / LK kernels and costs each ~0.2 ms at 256 sequences (measured, round 3: 22.4 k -> 21.1 k
 // frames/s).
-hipStream_t ensure_copy_stream(StreamSet *s, bool prepare, bool partitioned)
+hipStream_t ensure_ingest_stream(vo_ctx *c, bool prepare)
 {
-    if (partitioned) // (created with the rest of the partitioned set)
-        return prepare ? s->part[6] : s->part[5];
-    hipStream_t &st = prepare ? s->prep : s->copy;
-    if (st)
+    hipStream_t &st = prepare ? c->sel->prep : c->sel->copy;
+    if (st) // (the partitioned twin is created whole: always here)
         return st;
     int least = 0, greatest = 0;
     bool ok = hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess;
@@ -101,11 +100,11 @@ hipStream_t ensure_copy_stream(StreamSet *s, bool prepare, bool partitioned)
 // against 115 alone, bucketing 48 against 10, LK 230 against 200).  Measured (tools/cu_mask_ab.sh, pairs resident): 2 763 ->
 // 3 115 frames/s with 128 + 128 CUs and two pose streams; 64 / 96 CUs for the pose side 3 014 / 2 978; with ONE pose stream
 // the partition loses (1 445), and at 8 sequences it loses with any split (13.7 k -> 12.9 k): vo_seq_configure uses it for
-// n_seq == 1 only and the schedule probe settles the rest.  part[]: stream, pnp, pnp2, filter, em, copy, prep.
+// n_seq == 1 only and the schedule probe settles the rest.
 bool ensure_partitioned_streams(StreamSet *s, int device)
 {
     if (s->part_tried)
-        return s->part[0] != nullptr;
+        return s->part.stream != nullptr;
     s->part_tried = true;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess)
@@ -117,46 +116,37 @@ bool ensure_partitioned_streams(StreamSet *s, int device)
     for (int cu = 0; cu < n_cu; cu++)
         (cu < pose_cus ? pose_mask : trk_mask)[(size_t)cu >> 5] |= 1u << (cu & 31);
     const uint32_t words = (uint32_t)pose_mask.size();
-    hipStream_t t[7] = {};
+    Streams t;
     bool ok = true;
-    for (int k = 0; k < 7 && ok; k++) // stream, pnp, pnp2, filter, em, copy, prep
-        ok = hipExtStreamCreateWithCUMask(&t[k], words, (k == 0 || k >= 5 ? trk_mask : pose_mask).data()) == hipSuccess;
+    for (const StreamSlot &k : VO_STREAM_SLOTS)
+        ok = ok && hipExtStreamCreateWithCUMask(&(t.*k.m), words, (k.role == POST ? pose_mask : trk_mask).data()) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        for (hipStream_t st : t)
-            if (st)
-                (void)hipStreamDestroy(st);
+        for (const StreamSlot &k : VO_STREAM_SLOTS)
+            if (t.*k.m)
+                (void)hipStreamDestroy(t.*k.m);
         return false;
     }
-    for (int k = 0; k < 7; k++)
-        s->part[k] = t[k];
+    s->part = t;
     return true;
 }
 
 // which twin of its stream set a context enqueues on; the caller has drained every stream (sync_all)
 int select_streams(vo_ctx *c, bool partitioned)
 {
-    if (partitioned && !ensure_partitioned_streams(&c->streams, c->device))
-        partitioned = false; // (no CU masks on this device / runtime: the ordinary set)
-    const StreamSet &s = c->streams;
-    c->partitioned = partitioned;
-    c->stream = partitioned ? s.part[0] : s.stream;
-    c->stream_pnp = partitioned ? s.part[1] : s.pnp;
-    c->stream_pnp2 = partitioned ? s.part[2] : s.pnp2;
-    c->stream_filter = partitioned ? s.part[3] : s.filter;
-    c->stream_em = partitioned ? s.part[4] : s.em;
+    // (no CU masks on this device / runtime: the ordinary set all the same)
+    c->sel = partitioned && ensure_partitioned_streams(&c->streams, c->device) ? &c->streams.part : &c->streams.plain;
     c->last_pose_stream = nullptr;
     return VO_OK;
 }
 
 void release_streams(int device, const StreamSet &s)
 {
-    hipStream_t all[] = {s.stream, s.pnp, s.pnp2, s.filter, s.em, s.copy, s.prep, s.part[0], s.part[1], s.part[2], s.part[3],
-                         s.part[4], s.part[5], s.part[6]};
-    for (hipStream_t st : all)
-        if (st)
-            (void)hipStreamSynchronize(st);
-    if (!s.stream || device >= VO_MAX_DEVICES)
+    for (const Streams *t : {&s.plain, &s.part})
+        for (const StreamSlot &k : VO_STREAM_SLOTS)
+            if (t->*k.m)
+                (void)hipStreamSynchronize(t->*k.m);
+    if (!s.plain.stream || device >= VO_MAX_DEVICES)
         return;
     std::lock_guard<std::mutex> lk(g_pool_mu);
     g_pool[device].push_back(s);
@@ -199,57 +189,10 @@ void vo_destroy(vo_ctx *c)
     if (!c)
         return;
     (void)hipSetDevice(c->device);
-    if (c->stream)
+    if (c->sel->stream)
         (void)sync_all(c); // nothing of this context may still run on streams that go back to the pool
-    void *ptrs[] = {c->d_der, c->d_pix, c->d_imgs, c->d_quads, c->d_pts, c->d_trk2[0], c->d_trk2[1], c->d_outA,
-                    c->d_status2[0], c->d_status2[1], c->d_npts, c->d_nA, c->d_idxA, c->d_P, c->d_rowoff, c->d_nmsmask, c->d_rowcnt, c->d_detect,
-                    c->d_ntracked, c->d_nnew, c->d_feat, c->d_fages, c->d_ages, c->d_pts_det[0], c->d_pts_det[1],
-                    c->d_npts_det[0], c->d_npts_det[1], c->d_ages_det[0], c->d_ages_det[1], c->d_overflow};
-    for (void *p : ptrs)
-        if (p)
-            (void)hipFree(p);
     seq_free(c);
-    for (auto &b : c->pb) {
-        void *q[] = {b.outB, b.idxB, b.nB, b.xyz, b.subsets, b.inliers, b.models, b.counts, b.rstate, b.results,
-                     b.em_results, b.epnp_ws, b.epnp_gws, b.rest_ws};
-        for (void *p : q)
-            if (p)
-                (void)hipFree(p);
-        if (b.ready)
-            (void)hipEventDestroy(b.ready);
-        if (b.done)
-            (void)hipEventDestroy(b.done);
-        if (b.tri_done)
-            (void)hipEventDestroy(b.tri_done);
-        if (b.em_done)
-            (void)hipEventDestroy(b.em_done);
-    }
-    {
-        void *q[] = {c->em.q0, c->em.q1, c->em.subsets, c->em.rstate, c->em.models, c->em.nmodels, c->em.counts,
-                     c->em.bestE, c->em.mask};
-        for (void *p : q)
-            if (p)
-                (void)hipFree(p);
-    }
-    for (auto &ev : c->ev_trk_free)
-        if (ev)
-            (void)hipEventDestroy(ev);
-    if (c->ev_t1_ready)
-        (void)hipEventDestroy(c->ev_t1_ready);
-    if (c->h_stage)
-        (void)hipHostFree(c->h_stage);
-    if (c->h_gather)
-        (void)hipHostFree(c->h_gather);
-    if (c->h_pts_stage)
-        (void)hipHostFree(c->h_pts_stage);
-    if (c->h_feat_stage)
-        (void)hipHostFree(c->h_feat_stage);
-    for (auto &e : c->ev)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : c->ring)
-        if (e)
-            (void)hipEventDestroy(e);
+    c->own.release();
     release_streams(c->device, c->streams); // synchronises them; back to the per-device pool
     delete c;
 }
@@ -274,23 +217,19 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     c->ransac_cap = 1000;
     const size_t B = (size_t)max_frames, cap = (size_t)max_pts;
     bool ok = acquire_streams(device, &c->streams);
-    ok = ok && pnp_init_device(c->streams.stream) == 0;
-    c->stream = c->streams.stream;
-    c->stream_pnp = c->streams.pnp;
-    c->stream_pnp2 = c->streams.pnp2;
-    c->stream_filter = c->streams.filter;
-    c->stream_em = c->streams.em;
+    ok = ok && pnp_init_device(c->sel->stream) == 0;
+    Owner &o = c->own;
     for (auto &ev : c->ev_trk_free)
-        ok = ok && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_t1_ready, hipEventDisableTiming) == hipSuccess;
+        ok = ok && o.event(&ev);
+    ok = ok && o.event(&c->ev_t1_ready);
     // developer build: VO_SERIAL_POSE=1 enqueues the pose solve on the tracking stream (no overlap), so that a kernel trace shows
     // every kernel's stand-alone duration
     c->serial_pose = dev_knob("VO_SERIAL_POSE", 0) == 1;
     for (auto &e : c->ev)
-        ok = ok && hipEventCreate(&e) == hipSuccess;
+        ok = ok && o.event(&e, /*timing*/ true);
     c->ring.assign((size_t)VO_EVENT_SLOTS * (VO_EV_PER_RUN), nullptr);
     for (auto &e : c->ring)
-        ok = ok && hipEventCreate(&e) == hipSuccess;
+        ok = ok && o.event(&e, /*timing*/ true);
     // worst case pyramid bytes per image (5 levels, padded strides)
     {
         size_t per = 0;
@@ -304,48 +243,42 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     }
     c->stage_slot = (size_t)level_stride(max_w) * max_h;
     c->stage_slot = (c->stage_slot + 255) / 256 * 256; // (slots stay 16-byte aligned for launch_pull_image)
-    ok = ok && hipHostMalloc((void **)&c->h_stage, c->stage_slot * VO_STAGE_SLOTS, hipHostMallocMapped) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer((void **)&c->d_stage, c->h_stage, 0) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&c->h_gather, frame_gather_bytes(c->cap), hipHostMallocMapped) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer((void **)&c->d_gather, c->h_gather, 0) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&c->h_pts_stage, sizeof(float2) * (size_t)c->cap + 16, hipHostMallocMapped) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer((void **)&c->d_pts_stage, c->h_pts_stage, 0) == hipSuccess;
-    ok = ok && dmalloc(&c->d_pix, c->pix_capacity) == hipSuccess;
-    ok = ok && dmalloc(&c->d_der, c->pix_capacity) == hipSuccess;
-    ok = ok && dmalloc(&c->d_imgs, (size_t)c->max_images) == hipSuccess;
-    ok = ok && dmalloc(&c->d_quads, B + VO_CONST_QUADS) == hipSuccess; // (the table + const_quad()'s four)
-    ok = ok && dmalloc(&c->d_pts, B * cap) == hipSuccess;
+    ok = ok && o.pinned(&c->h_stage, c->stage_slot * VO_STAGE_SLOTS, hipHostMallocMapped, &c->d_stage);
+    ok = ok && o.pinned(&c->h_gather, frame_gather_bytes(c->cap), hipHostMallocMapped, &c->d_gather);
+    ok = ok && o.pinned(&c->h_pts_stage, sizeof(float2) * (size_t)c->cap + 16, hipHostMallocMapped, &c->d_pts_stage);
+    ok = ok && o.device(&c->d_pix, c->pix_capacity);
+    ok = ok && o.device(&c->d_der, c->pix_capacity);
+    ok = ok && o.device(&c->d_imgs, (size_t)c->max_images);
+    ok = ok && o.device(&c->d_quads, B + VO_CONST_QUADS); // (the table + const_quad()'s four)
+    ok = ok && o.device(&c->d_pts, B * cap);
     for (int k = 0; k < 2; k++) {
-        ok = ok && dmalloc(&c->d_trk2[k], B * 4 * cap) == hipSuccess;
-        ok = ok && dmalloc(&c->d_status2[k], B * 4 * cap) == hipSuccess;
+        ok = ok && o.device(&c->d_trk2[k], B * 4 * cap);
+        ok = ok && o.device(&c->d_status2[k], B * 4 * cap);
     }
-    ok = ok && dmalloc(&c->d_outA, B * 5 * cap) == hipSuccess;
-    ok = ok && dmalloc(&c->d_npts, B) == hipSuccess;
-    ok = ok && dmalloc(&c->d_nA, B) == hipSuccess;
-    ok = ok && dmalloc(&c->d_idxA, B * cap) == hipSuccess;
-    ok = ok && dmalloc(&c->d_P, (size_t)24) == hipSuccess;
+    ok = ok && o.device(&c->d_outA, B * 5 * cap);
+    ok = ok && o.device(&c->d_npts, B, /*zero*/ true);
+    ok = ok && o.device(&c->d_nA, B, /*zero*/ true);
+    ok = ok && o.device(&c->d_idxA, B * cap);
+    ok = ok && o.device(&c->d_P, (size_t)24);
     for (auto &b : c->pb) {
-        ok = ok && dmalloc(&b.outB, B * 4 * cap) == hipSuccess;
-        ok = ok && dmalloc(&b.nB, B) == hipSuccess;
-        ok = ok && dmalloc(&b.idxB, B * cap) == hipSuccess;
-        ok = ok && dmalloc(&b.xyz, B * cap * 3) == hipSuccess;
-        ok = ok && dmalloc(&b.subsets, B * c->ransac_cap * 5) == hipSuccess;
-        ok = ok && dmalloc(&b.inliers, B * cap) == hipSuccess;
-        ok = ok && dmalloc(&b.models, B * c->ransac_cap * 6) == hipSuccess;
-        ok = ok && dmalloc(&b.counts, B * c->ransac_cap) == hipSuccess;
-        ok = ok && dmalloc(&b.results, B) == hipSuccess;
-        ok = ok && dmalloc(&b.rstate, B) == hipSuccess;
-        ok = ok && dmalloc(&b.epnp_ws, (size_t)(c->max_frames < VO_EPNP_WS_MAX_FRAMES ? c->max_frames : VO_EPNP_WS_MAX_FRAMES) *
-                                           VO_EPNP_WS_HYPS * VO_EPNP_WS_DOUBLES) == hipSuccess;
-        ok = ok && dmalloc(&b.rest_ws, (size_t)(c->max_frames < VO_EPNP_WS_MAX_FRAMES ? c->max_frames : VO_EPNP_WS_MAX_FRAMES) *
-                                           pnp_rest_ws_doubles(c->ransac_cap)) == hipSuccess;
+        ok = ok && o.device(&b.outB, B * 4 * cap);
+        ok = ok && o.device(&b.nB, B, /*zero*/ true);
+        ok = ok && o.device(&b.idxB, B * cap);
+        ok = ok && o.device(&b.xyz, B * cap * 3);
+        ok = ok && o.device(&b.subsets, B * c->ransac_cap * 5);
+        ok = ok && o.device(&b.inliers, B * cap);
+        ok = ok && o.device(&b.models, B * c->ransac_cap * 6);
+        ok = ok && o.device(&b.counts, B * c->ransac_cap);
+        ok = ok && o.device(&b.results, B);
+        ok = ok && o.device(&b.rstate, B);
+        ok = ok && o.device(&b.epnp_ws, (size_t)epnp_ws_frames(c) * VO_EPNP_WS_HYPS * VO_EPNP_WS_DOUBLES);
+        ok = ok && o.device(&b.rest_ws, (size_t)epnp_ws_frames(c) * pnp_rest_ws_doubles(c->ransac_cap));
         if (VO_DEV_MAX_POSE_WAVES >= 4) // the slim pose chain's workspace (pnp.hip)
-            ok = ok && dmalloc(&b.epnp_gws, B * VO_EPNP_GWS_BLOCKS * VO_EPNP_UT_DOUBLES * 64) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&b.ready, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&b.done, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&b.tri_done, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&b.em_done, hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipMemset(b.nB, 0, B * sizeof(int)) == hipSuccess;
+            ok = ok && o.device(&b.epnp_gws, B * VO_EPNP_GWS_BLOCKS * VO_EPNP_UT_DOUBLES * 64);
+        ok = ok && o.event(&b.ready);
+        ok = ok && o.event(&b.done);
+        ok = ok && o.event(&b.tri_done);
+        ok = ok && o.event(&b.em_done);
     }
     vo_default_detect_params(&c->dprm);
     // carried + detected features of one frame before bucketing: cv::FAST on a textured image returns one corner
@@ -354,34 +287,21 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     c->fcap = max_pts * 4 > 16384 ? max_pts * 4 : 16384;
     if ((long long)max_w * max_h / 16 > c->fcap)
         c->fcap = (int)((long long)max_w * max_h / 16);
-    ok = ok && dmalloc(&c->d_nmsmask, B * (size_t)max_h * ((max_w + 63) / 64)) == hipSuccess;
-    ok = ok && dmalloc(&c->d_rowcnt, B * (size_t)max_h) == hipSuccess;
-    ok = ok && dmalloc(&c->d_rowoff, B * (size_t)max_h) == hipSuccess;
-    ok = ok && hipMemset(c->d_rowcnt, 0, B * (size_t)max_h * sizeof(int)) == hipSuccess;
-    ok = ok && dmalloc(&c->d_detect, B) == hipSuccess;
-    ok = ok && dmalloc(&c->d_ntracked, B) == hipSuccess;
-    ok = ok && dmalloc(&c->d_nnew, B) == hipSuccess;
-    ok = ok && dmalloc(&c->d_feat, B * (size_t)c->fcap) == hipSuccess;
-    ok = ok && dmalloc(&c->d_fages, B * (size_t)c->fcap) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&c->h_feat_stage, features_stage_bytes(c->fcap), hipHostMallocMapped) == hipSuccess;
-    ok = ok && hipHostGetDevicePointer((void **)&c->d_feat_stage, c->h_feat_stage, 0) == hipSuccess;
-    ok = ok && dmalloc(&c->d_ages, B * cap) == hipSuccess;
-    ok = ok && dmalloc(&c->d_overflow, B) == hipSuccess;
-    ok = ok && hipMemset(c->d_overflow, 0, B * sizeof(int)) == hipSuccess;
+    ok = ok && o.device(&c->d_nmsmask, B * (size_t)max_h * ((max_w + 63) / 64));
+    ok = ok && o.device(&c->d_rowcnt, B * (size_t)max_h, /*zero*/ true);
+    ok = ok && o.device(&c->d_rowoff, B * (size_t)max_h);
+    ok = ok && o.device(&c->d_detect, B, /*zero*/ true);
+    ok = ok && o.device(&c->d_ntracked, B, /*zero*/ true);
+    ok = ok && o.device(&c->d_nnew, B, /*zero*/ true);
+    ok = ok && o.device(&c->d_feat, B * (size_t)c->fcap);
+    ok = ok && o.device(&c->d_fages, B * (size_t)c->fcap, /*zero*/ true);
+    ok = ok && o.pinned(&c->h_feat_stage, features_stage_bytes(c->fcap), hipHostMallocMapped, &c->d_feat_stage);
+    ok = ok && o.device(&c->d_ages, B * cap, /*zero*/ true);
+    ok = ok && o.device(&c->d_overflow, B, /*zero*/ true);
     for (int k = 0; k < 2; k++) {
-        ok = ok && dmalloc(&c->d_pts_det[k], B * cap) == hipSuccess;
-        ok = ok && dmalloc(&c->d_npts_det[k], B) == hipSuccess;
-        ok = ok && dmalloc(&c->d_ages_det[k], B * cap) == hipSuccess;
-        ok = ok && hipMemset(c->d_npts_det[k], 0, B * sizeof(int)) == hipSuccess;
-    }
-    if (ok) {
-        ok = hipMemset(c->d_npts, 0, B * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_nA, 0, B * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_ntracked, 0, B * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_nnew, 0, B * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_detect, 0, B * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_fages, 0, B * (size_t)c->fcap * sizeof(int)) == hipSuccess &&
-             hipMemset(c->d_ages, 0, B * cap * sizeof(int)) == hipSuccess;
+        ok = ok && o.device(&c->d_pts_det[k], B * cap);
+        ok = ok && o.device(&c->d_npts_det[k], B, /*zero*/ true);
+        ok = ok && o.device(&c->d_ages_det[k], B * cap);
     }
     c->h_ntracked.assign(B, 0);
     c->h_detect.assign(B, 1);
@@ -419,12 +339,12 @@ int vo_set_params(vo_ctx *c, const vo_params *p)
         if (rcs != VO_OK)
             return rcs;
         uint8_t *h_new = nullptr, *d_new = nullptr;
-        VO_HIP_TRY(c, hipHostMalloc((void **)&h_new, raw * VO_STAGE_SLOTS, hipHostMallocMapped));
-        if (hipHostGetDevicePointer((void **)&d_new, h_new, 0) != hipSuccess) {
-            (void)hipHostFree(h_new);
-            return fail(c, VO_ERR_HIP, "vo_set_params: no device address for the staging slots");
+        if (!c->own.pinned(&h_new, raw * VO_STAGE_SLOTS, hipHostMallocMapped, &d_new)) {
+            const hipError_t e = c->own.err;
+            (void)c->own.give_back(&h_new);
+            return fail_hip(c, "vo_set_params: page-locked staging slots for this input format", e);
         }
-        (void)hipHostFree(c->h_stage);
+        (void)c->own.give_back(&c->h_stage);
         c->h_stage = h_new;
         c->d_stage = d_new;
         c->stage_slot = raw;
@@ -489,10 +409,10 @@ int vo_batch_configure(vo_ctx *c, int n_images, int w, int h, int n_frames)
         }
     }
     VO_HIP_TRY(c, hipMemcpyAsync(c->d_imgs, tab.data(), sizeof(PyrImage) * n_images, hipMemcpyHostToDevice,
-                                 c->stream));
+                                 c->sel->stream));
     // the Scharr border is BORDER_CONSTANT 0 (and stays 0: scharr_kernel writes interiors only)
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_der, 0, sizeof(uint32_t) * c->img_bytes * (size_t)n_images, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_der, 0, sizeof(uint32_t) * c->img_bytes * (size_t)n_images, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     c->n_images = n_images;
     c->pyr_first = 0;
     c->pyr_count = n_images;
@@ -505,19 +425,35 @@ int vo_batch_configure(vo_ctx *c, int n_images, int w, int h, int n_frames)
     std::fill(c->img_stale.begin(), c->img_stale.end(), 0);
     std::fill(c->h_quads.begin(), c->h_quads.end(), Quad{0, 0, 0, 0});
     c->quads_set = false;
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_quads, 0, sizeof(Quad) * c->max_frames, c->stream));
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_overflow, 0, sizeof(int) * c->max_frames, c->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_quads, 0, sizeof(Quad) * c->max_frames, c->sel->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_overflow, 0, sizeof(int) * c->max_frames, c->sel->stream));
     c->detect_uploaded = false; // the per-frame detect flags on the device belong to the previous batch shape
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_npts, 0, sizeof(int) * c->max_frames, c->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_npts, 0, sizeof(int) * c->max_frames, c->sel->stream));
     c->pts_sel = -1;
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_ntracked, 0, sizeof(int) * c->max_frames, c->stream));
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_fages, 0, sizeof(int) * (size_t)c->max_frames * c->fcap, c->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_ntracked, 0, sizeof(int) * c->max_frames, c->sel->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_fages, 0, sizeof(int) * (size_t)c->max_frames * c->fcap, c->sel->stream));
     return VO_OK;
 }
 
 } // extern "C"
 
 namespace vo_capi {
+
+// A host image into the next page-locked staging slot, row_bytes of each row, the rows `pitch` bytes apart; the points of an
+// idle (synchronous) call into their own staging buffer beside it.  Returns the slot.
+static int stage_image(vo_ctx *c, const void *src, int stride, size_t pitch, size_t row_bytes, bool idle, const float *pts, int n_pts,
+                       uint8_t **slot)
+{
+    if (c->stage_next == 0 && !idle) // all slots may still be in flight from the previous round of uploads
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    *slot = c->h_stage + c->stage_slot * (size_t)c->stage_next;
+    c->stage_next = (c->stage_next + 1) % VO_STAGE_SLOTS;
+    for (int y = 0; y < c->h; y++)
+        memcpy(*slot + (size_t)y * pitch, (const uint8_t *)src + (size_t)y * stride, row_bytes);
+    if (idle && n_pts > 0)
+        memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n_pts);
+    return VO_OK;
+}
 
 int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind kind, bool idle, const float *pts, int n_pts,
                  hipStream_t on)
@@ -546,18 +482,14 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
         const bool with_pts = kind == hipMemcpyHostToDevice && idle && n_pts >= 0;
         if (kind == hipMemcpyHostToDevice) {
             const size_t rb = fmt_row_bytes(fmt, c->w);
-            if (c->stage_next == 0 && !idle)
-                VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-            uint8_t *slot = c->h_stage + c->stage_slot * (size_t)c->stage_next;
-            c->stage_next = (c->stage_next + 1) % VO_STAGE_SLOTS;
-            for (int y = 0; y < c->h; y++)
-                memcpy(slot + (size_t)y * rb, (const uint8_t *)src + (size_t)y * stride, rb);
-            if (with_pts && n_pts > 0)
-                memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n_pts);
+            uint8_t *slot = nullptr;
+            int rc = stage_image(c, src, stride, rb, rb, idle, pts, n_pts, &slot);
+            if (rc != VO_OK)
+                return rc;
             from = c->d_stage + (slot - c->h_stage);
             from_stride = (int)rb;
         }
-        hipStream_t st = idle && on ? on : c->stream;
+        hipStream_t st = idle && on ? on : c->sel->stream;
         if (launch_pull_image_fmt(fmt, from, from_stride, dst, c->lstride[0], c->w, c->h, st, with_pts ? c->d_pts_stage : nullptr,
                                   with_pts ? c->d_pts : nullptr, with_pts ? n_pts : 0, with_pts ? c->d_npts : nullptr) != 0)
             return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
@@ -569,30 +501,25 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
         // last interior pixel.  The bytes between two rows land in border columns, which the pyramid
         // stage's border fill rewrites before anything reads them.
         const size_t pitch = (size_t)c->lstride[0];
-        if (c->stage_next == 0 && !idle) // all slots may still be in flight from the previous round of uploads
-            VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        uint8_t *slot = c->h_stage + c->stage_slot * (size_t)c->stage_next;
-        c->stage_next = (c->stage_next + 1) % VO_STAGE_SLOTS;
-        for (int y = 0; y < c->h; y++)
-            memcpy(slot + (size_t)y * pitch, (const uint8_t *)src + (size_t)y * stride, (size_t)c->w);
+        uint8_t *slot = nullptr;
+        int rc = stage_image(c, src, stride, pitch, (size_t)c->w, idle, pts, n_pts, &slot);
+        if (rc != VO_OK)
+            return rc;
         const size_t bytes = pitch * (size_t)(c->h - 1) + (size_t)c->w;
         if (idle) { // a synchronous drop-in call: the GPU pulls the slot itself (pyramid.hip, launch_pull_image; the 16-byte
                     // round-up of the last row stays inside the row's pitch)
-            if (n_pts >= 0) { // the call's points (frame 0) and their count with this image
-                if (n_pts > 0)
-                    memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n_pts);
-                launch_pull_image(c->d_stage + (slot - c->h_stage), dst, bytes, on ? on : c->stream, c->d_pts_stage, c->d_pts, n_pts, c->d_npts);
-            } else {
-                launch_pull_image(c->d_stage + (slot - c->h_stage), dst, bytes, on ? on : c->stream);
-            }
+            if (n_pts >= 0) // the call's points (frame 0) and their count with this image
+                launch_pull_image(c->d_stage + (slot - c->h_stage), dst, bytes, on ? on : c->sel->stream, c->d_pts_stage, c->d_pts, n_pts, c->d_npts);
+            else
+                launch_pull_image(c->d_stage + (slot - c->h_stage), dst, bytes, on ? on : c->sel->stream);
             VO_HIP_TRY(c, hipGetLastError());
         } else {
-            VO_HIP_TRY(c, hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, c->stream));
+            VO_HIP_TRY(c, hipMemcpyAsync(dst, slot, bytes, hipMemcpyHostToDevice, c->sel->stream));
         }
         return VO_OK;
     }
     VO_HIP_TRY(c, hipMemcpy2DAsync(dst, (size_t)c->lstride[0], src, (size_t)stride, (size_t)c->w, (size_t)c->h,
-                                   kind, c->stream));
+                                   kind, c->sel->stream));
     return VO_OK;
 }
 
@@ -606,7 +533,7 @@ int vo_batch_upload_image(vo_ctx *c, int idx, const uint8_t *host, int stride)
         c->tf_base = -1; // the caller owns the image table now (see vo_ctx::tf_base)
     int rc = upload_image(c, idx, host, stride, hipMemcpyHostToDevice);
     if (rc == VO_OK) // pageable host memory: make the call safe to return from
-        VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     return rc;
 }
 
@@ -631,8 +558,8 @@ int vo_batch_set_quads(vo_ctx *c, const int32_t *quads4, int n_frames)
     if (c->quads_set && memcmp(c->h_quads.data(), quads4, sizeof(Quad) * n_frames) == 0)
         return VO_OK; // the table on the device already says so (the single-frame calls set {0, 1, 2, 3} every time)
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    VO_HIP_TRY(c, hipMemcpyAsync(c->d_quads, quads4, sizeof(Quad) * n_frames, hipMemcpyHostToDevice, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(c->d_quads, quads4, sizeof(Quad) * n_frames, hipMemcpyHostToDevice, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     memcpy(c->h_quads.data(), quads4, sizeof(Quad) * n_frames);
     c->quads_set = true;
     c->quads_cur = c->d_quads; // (a synchronous drop-in call may have left it at one of its constant quadruples)
@@ -665,22 +592,22 @@ int vo_batch_set_points(vo_ctx *c, int frame, const float *pts, int n)
         return rcs;
     if (c->pts_sel >= 0) { // the other frames keep what the last DETECT stage gave them
         const size_t B = (size_t)c->max_frames, cap = (size_t)c->cap;
-        VO_HIP_TRY(c, hipMemcpyAsync(c->d_pts, cur_pts(c), sizeof(float2) * B * cap, hipMemcpyDeviceToDevice, c->stream));
-        VO_HIP_TRY(c, hipMemcpyAsync(c->d_ages, cur_ages(c), sizeof(int) * B * cap, hipMemcpyDeviceToDevice, c->stream));
-        VO_HIP_TRY(c, hipMemcpyAsync(c->d_npts, cur_npts(c), sizeof(int) * B, hipMemcpyDeviceToDevice, c->stream));
+        VO_HIP_TRY(c, hipMemcpyAsync(c->d_pts, cur_pts(c), sizeof(float2) * B * cap, hipMemcpyDeviceToDevice, c->sel->stream));
+        VO_HIP_TRY(c, hipMemcpyAsync(c->d_ages, cur_ages(c), sizeof(int) * B * cap, hipMemcpyDeviceToDevice, c->sel->stream));
+        VO_HIP_TRY(c, hipMemcpyAsync(c->d_npts, cur_npts(c), sizeof(int) * B, hipMemcpyDeviceToDevice, c->sel->stream));
         VO_HIP_TRY(c, hipMemcpyAsync(c->h_npts.data(), c->d_npts, sizeof(int) * c->n_frames, hipMemcpyDeviceToHost,
-                                     c->stream));
-        VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                                     c->sel->stream));
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
         c->pts_sel = -1;
     }
     if (n > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(c->d_pts + (size_t)frame * c->cap, pts, sizeof(float2) * n,
-                                     hipMemcpyHostToDevice, c->stream));
+                                     hipMemcpyHostToDevice, c->sel->stream));
     c->h_npts[frame] = n;
     c->pts_on_device = false;
     VO_HIP_TRY(c, hipMemcpyAsync(c->d_npts + frame, &c->h_npts[frame], sizeof(int), hipMemcpyHostToDevice,
-                                 c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                                 c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     c->max_pts_set = 0;
     for (int f = 0; f < c->n_frames; f++)
         c->max_pts_set = c->h_npts[f] > c->max_pts_set ? c->h_npts[f] : c->max_pts_set;
@@ -702,17 +629,17 @@ int vo_batch_set_features(vo_ctx *c, int frame, const float *pts, int n_pts, con
     if (rcs != VO_OK)
         return rcs;
     // ages beyond n_ages must read as 0 (age of a freshly appended corner, feature.cpp:260)
-    VO_HIP_TRY(c, hipMemsetAsync(c->d_fages + (size_t)frame * c->fcap, 0, sizeof(int) * (size_t)c->fcap, c->stream));
+    VO_HIP_TRY(c, hipMemsetAsync(c->d_fages + (size_t)frame * c->fcap, 0, sizeof(int) * (size_t)c->fcap, c->sel->stream));
     if (n_pts > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(c->d_feat + (size_t)frame * c->fcap, pts, sizeof(float2) * n_pts,
-                                     hipMemcpyHostToDevice, c->stream));
+                                     hipMemcpyHostToDevice, c->sel->stream));
     if (n_ages > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(c->d_fages + (size_t)frame * c->fcap, ages, sizeof(int) * n_ages,
-                                     hipMemcpyHostToDevice, c->stream));
+                                     hipMemcpyHostToDevice, c->sel->stream));
     c->h_ntracked[frame] = n_pts;
     VO_HIP_TRY(c, hipMemcpyAsync(c->d_ntracked + frame, &c->h_ntracked[frame], sizeof(int), hipMemcpyHostToDevice,
-                                 c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                                 c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     return VO_OK;
 }
 
@@ -738,23 +665,19 @@ int vo_batch_get_features(vo_ctx *c, int frame, float *pts, int32_t *ages, int *
         return fail(c, VO_ERR_ARG, "vo_batch_get_features: bad frame");
     VO_HIP_TRY(c, hipSetDevice(c->device));
     int k = 0;
-    VO_HIP_TRY(c, hipMemcpyAsync(&k, cur_npts(c) + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(&k, cur_npts(c) + frame, sizeof(int), hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     if (pts && k > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(pts, cur_pts(c) + (size_t)frame * c->cap, sizeof(float2) * k, hipMemcpyDeviceToHost,
-                                     c->stream));
+                                     c->sel->stream));
     if (ages && k > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(ages, cur_ages(c) + (size_t)frame * c->cap, sizeof(int) * k, hipMemcpyDeviceToHost,
-                                     c->stream));
+                                     c->sel->stream));
     int ovf = 0;
-    VO_HIP_TRY(c, hipMemcpyAsync(&ovf, c->d_overflow + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(&ovf, c->d_overflow + frame, sizeof(int), hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     *n = k;
-    if (ovf)
-        return fail(c, VO_ERR_OVERFLOW, ovf & 1 ? "VO_STAGE_DETECT: carried + detected features exceed the feature-list "
-                                                  "capacity (4 x max_pts, >= 16384, >= w * h / 16): bucketed set truncated"
-                                                : "VO_STAGE_DETECT: the bucketed set exceeds max_pts");
-    return VO_OK;
+    return ovf ? fail_overflow(c, ovf) : VO_OK;
 }
 
 int vo_batch_set_projection(vo_ctx *c, const float *P_l, const float *P_r)
@@ -766,8 +689,8 @@ int vo_batch_set_projection(vo_ctx *c, const float *P_l, const float *P_r)
     memcpy(c->h_P, P_l, 12 * sizeof(float));
     memcpy(c->h_P + 12, P_r, 12 * sizeof(float));
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    VO_HIP_TRY(c, hipMemcpyAsync(c->d_P, c->h_P, 24 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(c->d_P, c->h_P, 24 * sizeof(float), hipMemcpyHostToDevice, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     c->have_P = true;
     return VO_OK;
 }
@@ -783,19 +706,14 @@ int ensure_em(vo_ctx *c)
         return VO_OK;
     VO_HIP_TRY(c, hipSetDevice(c->device));
     const size_t B = (size_t)c->max_frames, cap = (size_t)c->cap;
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.q0, sizeof(double2) * B * cap));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.q1, sizeof(double2) * B * cap));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.subsets, sizeof(int32_t) * B * EM_MAX_ITERS * 5));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.rstate, sizeof(RansacState) * B));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.models, sizeof(double) * B * 128 * 90));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.nmodels, sizeof(int) * B * 128));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.counts, sizeof(int) * B * 128 * 10));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.bestE, sizeof(double) * B * 9));
-    VO_HIP_TRY(c, hipMalloc((void **)&c->em.mask, B * cap));
-    for (auto &b : c->pb) {
-        VO_HIP_TRY(c, hipMalloc((void **)&b.em_results, sizeof(EmResult) * B));
-        VO_HIP_TRY(c, hipMemset(b.em_results, 0, sizeof(EmResult) * B));
-    }
+    Owner &o = c->own;
+    bool ok = o.device(&c->em.q0, B * cap) && o.device(&c->em.q1, B * cap) && o.device(&c->em.subsets, B * EM_MAX_ITERS * 5) &&
+              o.device(&c->em.rstate, B) && o.device(&c->em.models, B * 128 * 90) && o.device(&c->em.nmodels, B * 128) &&
+              o.device(&c->em.counts, B * 128 * 10) && o.device(&c->em.bestE, B * 9) && o.device(&c->em.mask, B * cap);
+    for (auto &b : c->pb)
+        ok = ok && o.device(&b.em_results, B, /*zero*/ true);
+    if (!ok)
+        return fail_hip(c, "working set of the essential-matrix chain", o.err);
     c->em_ready = true;
     return VO_OK;
 }
@@ -826,7 +744,7 @@ int vo_batch_run_timed(vo_ctx *c, int stages, float *ms)
     if (rc != VO_OK)
         return rc;
     for (int s = 0; s < VO_NUM_STAGES; s++) // PYRAMID, DETECT, LK on the tracking stream; the rest on the post stream
-        VO_HIP_TRY(c, hipEventElapsedTime(&ms[s], c->ev[s == 1 ? VO_NUM_STAGES + 2 : s < 3 ? s : s + 1], c->ev[s < 3 ? s + 1 : s + 2]));
+        VO_HIP_TRY(c, hipEventElapsedTime(&ms[s], c->ev[stage_events(s).start], c->ev[stage_events(s).end]));
     return VO_OK;
 }
 
@@ -845,8 +763,8 @@ int vo_batch_slot_times(vo_ctx *c, int slot, float *ms)
         return VO_ERR_ARG;
     VO_HIP_TRY(c, hipSetDevice(c->device));
     hipEvent_t *evs = &c->ring[(size_t)slot * (VO_EV_PER_RUN)];
-    for (int s = 0; s < VO_NUM_STAGES; s++) // PYRAMID, DETECT, LK on the tracking stream; the rest on the post stream
-        VO_HIP_TRY(c, hipEventElapsedTime(&ms[s], evs[s == 1 ? VO_NUM_STAGES + 2 : s < 3 ? s : s + 1], evs[s < 3 ? s + 1 : s + 2]));
+    for (int s = 0; s < VO_NUM_STAGES; s++)
+        VO_HIP_TRY(c, hipEventElapsedTime(&ms[s], evs[stage_events(s).start], evs[stage_events(s).end]));
     return VO_OK;
 }
 
@@ -874,7 +792,7 @@ int vo_batch_get_tracks(vo_ctx *c, int frame, float *r0, float *r1, float *l1, f
     if (status4)
         for (int hop = 0; hop < 4; hop++)
             D2H(status4 + (size_t)hop * n, c->d_status2[c->trk_last] + ((size_t)frame * 4 + hop) * cap, (size_t)n);
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     return VO_OK;
 }
 
@@ -890,9 +808,9 @@ int vo_batch_get_filtered(vo_ctx *c, int frame, float *l0, float *r0, float *l1,
         return rcs;
     const vo_ctx::PoseBufs &pb = c->pb[c->last];
     int nAB[2] = {0, 0};
-    VO_HIP_TRY(c, hipMemcpyAsync(&nAB[0], c->d_nA + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    VO_HIP_TRY(c, hipMemcpyAsync(&nAB[1], pb.nB + frame, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(&nAB[0], c->d_nA + frame, sizeof(int), hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(&nAB[1], pb.nB + frame, sizeof(int), hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     const size_t cap = c->cap;
     const int K = nAB[1], M = nAB[0];
     const float2 *b = pb.outB + (size_t)frame * 4 * cap;
@@ -903,7 +821,7 @@ int vo_batch_get_filtered(vo_ctx *c, int frame, float *l0, float *r0, float *l1,
     D2H(xyz, pb.xyz + (size_t)frame * cap * 3, sizeof(float) * 3 * K);
     D2H(keep_idx, pb.idxB + (size_t)frame * cap, sizeof(int32_t) * K);
     D2H(keep_idx_circ, c->d_idxA + (size_t)frame * cap, sizeof(int32_t) * M);
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     if (n_out)
         *n_out = K;
     if (n_circ)
@@ -915,8 +833,69 @@ int vo_batch_get_filtered(vo_ctx *c, int frame, float *l0, float *r0, float *l1,
 
 namespace vo_capi {
 
-// pnp_rotation: R = Rodrigues(rvec) even under mono_rotation (vo_pnp_ransac).  em_status (optional): status of the
-// essential-matrix side of the frame under mono_rotation (1 ok, 0 no model, -1 too few points), 1 otherwise.
+// PnpParams of the context; K: the caller's intrinsic matrix, else projMatrl(0:3, 0:3) (visualOdometry.cpp:163-165)
+PnpParams pnp_params(const vo_ctx *c, const float *K)
+{
+    PnpParams pp;
+    pp.iters = c->prm.ransac_iterations;
+    pp.reproj = c->prm.ransac_reproj_error;
+    pp.confidence = c->prm.ransac_confidence;
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++)
+            pp.K[r * 3 + k] = K ? K[r * 3 + k] : c->h_P[r * 4 + k];
+    return pp;
+}
+
+// the context holds the t1 pair of a previous synchronous call of this size, pyramids built (vo_ctx::tf_base; stale: the call
+// that uploaded the pair failed before its pyramids were built)
+bool have_kept_pair(const vo_ctx *c, int w, int h)
+{
+    return c->tf_base >= 0 && !c->seq.on && c->n_images == 4 && c->n_frames == 1 && c->w == w && c->h == h && !c->img_stale[c->tf_base] &&
+           !c->img_stale[c->tf_base + 1];
+}
+
+int fail_overflow(vo_ctx *c, int ovf) // ovf: a frame's VO_STAGE_DETECT capacity flags (vo_ctx::d_overflow)
+{
+    return fail(c, VO_ERR_OVERFLOW, ovf & 1 ? "VO_STAGE_DETECT: carried + detected features exceed the feature-list "
+                                              "capacity (4 x max_pts, >= 16384, >= w * h / 16): bucketed set truncated"
+                                            : "VO_STAGE_DETECT: the bucketed set exceeds max_pts");
+}
+
+int fail_too_few_pnp(vo_ctx *c)
+{
+    return fail(c, VO_ERR_TOO_FEW, "fewer than 4 correspondences reached solvePnPRansac (CV_Assert(npoints >= 4))");
+}
+
+// THE rule by which a frame's pose reaches the caller's rvec / tvec / R (every pointer optional).  r: the PnP side; e: the
+// essential-matrix side under mono_rotation, else null.  pnp_rotation: R = Rodrigues(rvec) even under mono_rotation
+// (vo_pnp_ransac).  Returns the status of the essential-matrix side (1 ok, 0 no model, -1 too few points), 1 without one.
+int deliver_pose(const vo_ctx *c, const PnpResult &r, const EmResult *e, double *rvec, double *tvec, double *R, bool pnp_rotation, bool io_pose)
+{
+    const bool R_from_pnp = pnp_rotation || !c->prm.mono_rotation; // `if (!mono_rotation) Rodrigues(rvec, rotation)` (visualOdometry.cpp:186-189)
+    if (r.status == 0 && r.lm_iters < 0 && io_pose) {
+        // four points, P3P without a solution: solvePnP returned false and never wrote rvec / tvec -- the caller's
+        // buffers stay as they are; the reference then still runs Rodrigues(rvec, rotation) on what rvec holds.
+        // (io_pose = false, vo_batch_get_pose: its rvec / tvec / R are pure OUTPUTS -- a batch frame has no caller pose -- and
+        // receive what the kernel left: rvec = 0 like the reference's `cv::Mat::zeros` at visualOdometry.cpp:162, tvec = 0,
+        // R = identity, never a Rodrigues of uninitialised memory; ADVICE r03)
+        if (R && rvec && R_from_pnp)
+            rodrigues_v2m(rvec, R, nullptr);
+    } else if (r.status >= 0) {
+        if (rvec)
+            memcpy(rvec, r.rvec, sizeof(r.rvec));
+        if (tvec)
+            memcpy(tvec, r.tvec, sizeof(r.tvec));
+        if (R && R_from_pnp)
+            memcpy(R, r.R, sizeof(r.R));
+    }
+    if (!e)
+        return 1;
+    if (e->status == 1 && R) // rotation = recoverPose's; left untouched when no essential matrix was found (OpenCV throws there)
+        memcpy(R, e->R, sizeof(e->R));
+    return e->status;
+}
+
+// em_status (optional): status of the essential-matrix side of the frame under mono_rotation, 1 otherwise.
 int get_pose_impl(vo_ctx *c, int frame, double *rvec, double *tvec, double *R, int32_t *inliers,
                          int *n_inliers, int *status, int32_t *dbg4, bool pnp_rotation, int *em_status, bool io_pose)
 {
@@ -929,38 +908,18 @@ int get_pose_impl(vo_ctx *c, int frame, double *rvec, double *tvec, double *R, i
         return rcs;
     const vo_ctx::PoseBufs &pb = c->pb[c->last];
     PnpResult r;
-    VO_HIP_TRY(c, hipMemcpyAsync(&r, pb.results + frame, sizeof(r), hipMemcpyDeviceToHost, c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (r.status == 0 && r.lm_iters < 0 && io_pose) {
-        // four points, P3P without a solution: solvePnP returned false and never wrote rvec / tvec -- the caller's
-        // buffers stay as they are; the reference then still runs Rodrigues(rvec, rotation) on what rvec holds.
-        // (io_pose = false, vo_batch_get_pose: its rvec / tvec / R are pure OUTPUTS -- a batch frame has no caller pose -- and
-        // receive what the kernel left: rvec = 0 like the reference's `cv::Mat::zeros` at visualOdometry.cpp:162, tvec = 0,
-        // R = identity, never a Rodrigues of uninitialised memory; ADVICE r03)
-        if (R && rvec && (pnp_rotation || !c->prm.mono_rotation))
-            rodrigues_v2m(rvec, R, nullptr);
-    } else if (r.status >= 0) {
-        if (rvec)
-            memcpy(rvec, r.rvec, sizeof(r.rvec));
-        if (tvec)
-            memcpy(tvec, r.tvec, sizeof(r.tvec));
-        if (R && (pnp_rotation || !c->prm.mono_rotation))
-            memcpy(R, r.R, sizeof(r.R)); // `if (!mono_rotation) Rodrigues(rvec, rotation)` (visualOdometry.cpp:186-189)
-    }
-    if (em_status)
-        *em_status = 1;
-    if (!pnp_rotation && c->prm.mono_rotation && c->em_ready) {
-        // rotation = recoverPose's; left untouched when no essential matrix was found (OpenCV throws there)
-        EmResult e;
+    VO_HIP_TRY(c, hipMemcpyAsync(&r, pb.results + frame, sizeof(r), hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    EmResult e;
+    const bool mono = !pnp_rotation && c->prm.mono_rotation && c->em_ready;
+    if (mono)
         VO_HIP_TRY(c, hipMemcpy(&e, pb.em_results + frame, sizeof(e), hipMemcpyDeviceToHost));
-        if (e.status == 1 && R)
-            memcpy(R, e.R, sizeof(e.R));
-        if (em_status)
-            *em_status = e.status;
-    }
+    const int ems = deliver_pose(c, r, mono ? &e : nullptr, rvec, tvec, R, pnp_rotation, io_pose);
+    if (em_status)
+        *em_status = ems;
     if (inliers && r.n_inliers > 0) {
         D2H(inliers, pb.inliers + (size_t)frame * c->cap, sizeof(int32_t) * r.n_inliers);
-        VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     }
     if (n_inliers)
         *n_inliers = r.n_inliers;
@@ -1038,10 +997,10 @@ int vo_essential_pose(vo_ctx *c, const float *pts0, const float *pts1, int n, do
     vo_ctx::PoseBufs &pb = c->pb[c->last];
     const size_t cap = (size_t)c->cap;
     if (n > 0) {
-        VO_HIP_TRY(c, hipMemcpyAsync(pb.outB, pts0, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
-        VO_HIP_TRY(c, hipMemcpyAsync(pb.outB + 2 * cap, pts1, sizeof(float2) * n, hipMemcpyHostToDevice, c->stream));
+        VO_HIP_TRY(c, hipMemcpyAsync(pb.outB, pts0, sizeof(float2) * n, hipMemcpyHostToDevice, c->sel->stream));
+        VO_HIP_TRY(c, hipMemcpyAsync(pb.outB + 2 * cap, pts1, sizeof(float2) * n, hipMemcpyHostToDevice, c->sel->stream));
     }
-    VO_HIP_TRY(c, hipMemcpyAsync(pb.nB, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    VO_HIP_TRY(c, hipMemcpyAsync(pb.nB, &n, sizeof(int), hipMemcpyHostToDevice, c->sel->stream));
     if (c->n_frames < 1)
         c->n_frames = 1;
     EmParams ep;
@@ -1052,7 +1011,7 @@ int vo_essential_pose(vo_ctx *c, const float *pts0, const float *pts1, int n, do
     ep.threshold = threshold;
     ep.max_iters = EM_MAX_ITERS;
     launch_essential(pb.outB, pb.outB + 2 * cap, 4 * cap, pb.nB, c->cap, 1, ep, c->em, pb.em_results,
-                     /*crowded*/ standalone_waves(c) >= 2, c->stream);
+                     /*crowded*/ standalone_waves(c) >= 2, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
     int status = 0, good = 0;
     int rc = vo_batch_get_essential(c, 0, E, R, t, mask, n, nullptr, &good, &status, nullptr);
@@ -1081,8 +1040,8 @@ int vo_batch_get_pyramid_level(vo_ctx *c, int idx, int level, uint8_t *out, int 
                                        c->d_pix + (size_t)idx * c->img_bytes + c->loff[level] +
                                            (size_t)VO_BY * c->lstride[level] + VO_BX,
                                        (size_t)c->lstride[level], (size_t)c->lw[level], (size_t)c->lh[level],
-                                       hipMemcpyDeviceToHost, c->stream));
-        VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+                                       hipMemcpyDeviceToHost, c->sel->stream));
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     }
     return VO_OK;
 }

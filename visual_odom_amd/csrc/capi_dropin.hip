@@ -25,8 +25,7 @@ int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const ui
         return fail(c, VO_ERR_ARG, "more points than max_pts given to vo_create");
     if (stride < w * fmt_bpp(c->prm.input_format)) // (before anything changes: a refused call leaves the kept pair as it is)
         return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
-    if (keep && (c->tf_base < 0 || c->seq.on || c->n_images != 4 || c->n_frames != 1 || c->w != w || c->h != h ||
-                 c->img_stale[c->tf_base] || c->img_stale[c->tf_base + 1])) // (stale: the call that uploaded the pair failed before its pyramids were built)
+    if (keep && !have_kept_pair(c, w, h))
         return fail(c, VO_ERR_STATE, "no t0 images given, and the context does not hold the t1 pair of a previous call of this "
                                      "size (first call, another size, or the batch / sequence API used the images since)");
     int rc = vo_batch_configure(c, 4, w, h, 1);
@@ -63,7 +62,7 @@ int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const ui
     if (split) {
         if (n > 0)
             memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n);
-        launch_pull_image(nullptr, nullptr, 0, c->stream, c->d_pts_stage, c->d_pts, n, c->d_npts);
+        launch_pull_image(nullptr, nullptr, 0, c->sel->stream, c->d_pts_stage, c->d_pts, n, c->d_npts);
         VO_HIP_TRY(c, hipGetLastError());
         c->defer.img[0] = l1;
         c->defer.img[1] = r1;
@@ -125,22 +124,21 @@ int vo_circular_match(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uin
         if (rc != VO_OK)
             return rc;
     }
-    launch_circ_gather(g, c->d_gather, c->stream); // (circ_gather_bytes(cap) <= frame_gather_bytes(cap))
+    launch_circ_gather(g, c->d_gather, c->sel->stream); // (fits the buffer of the frame gather: vo_kernels.h, CircGatherLayout)
     VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     const uint8_t *hb = c->h_gather;
-    int count = 0;
-    memcpy(&count, hb, sizeof(int));
-    const size_t cap = (size_t)c->cap;
+    const CircGatherLayout L{(size_t)c->cap};
+    const int count = peek<int>(hb + L.count);
     float *outs[5] = {out_l0, out_r0, out_r1, out_l1, out_l0_ret};
     for (int k = 0; k < 5; k++)
         if (outs[k] && count > 0)
-            memcpy(outs[k], hb + 16 + (size_t)k * cap * 8, (size_t)count * 8);
+            memcpy(outs[k], hb + L.row(k), (size_t)count * sizeof(float2));
     if (keep_idx && count > 0)
-        memcpy(keep_idx, hb + 16 + 5 * cap * 8, (size_t)count * 4);
+        memcpy(keep_idx, hb + L.keep_idx(), (size_t)count * sizeof(int32_t));
     if (status4 && n > 0)
         for (int hop = 0; hop < 4; hop++) // [4][n] for the caller
-            memcpy(status4 + (size_t)hop * n, hb + 16 + 5 * cap * 8 + cap * 4 + (size_t)hop * cap, (size_t)n);
+            memcpy(status4 + (size_t)hop * n, hb + L.status(hop), (size_t)n);
     *n_out = count;
     return VO_OK;
 }
@@ -165,12 +163,12 @@ int vo_triangulate(vo_ctx *c, const float *P_l, const float *P_r, const float *p
     vo_ctx::PoseBufs &pb = c->pb[c->last];
     memcpy(c->h_feat_stage, pl, sizeof(float2) * (size_t)n);
     memcpy(c->h_feat_stage + sizeof(float2) * (size_t)n, pr, sizeof(float2) * (size_t)n);
-    launch_words_in(c->d_feat_stage, 2 * n, pb.outB, 2 * n, pb.outB + c->cap, pb.nB, n, c->stream);
+    launch_words_in(c->d_feat_stage, 2 * n, pb.outB, 2 * n, pb.outB + c->cap, pb.nB, n, c->sel->stream);
     launch_triangulate(c->d_P, c->d_P + 12, pb.outB, pb.outB + c->cap, (size_t)4 * c->cap, pb.nB, c->cap, n, 1,
-                       pb.xyz, c->stream);
-    launch_words_out(pb.xyz, 3 * n, c->d_gather, c->stream);
+                       pb.xyz, c->sel->stream);
+    launch_words_out(pb.xyz, 3 * n, c->d_gather, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     memcpy(xyz_out, c->h_gather, sizeof(float) * 3 * (size_t)n);
     return VO_OK;
 }
@@ -186,52 +184,37 @@ int vo_pnp_ransac(vo_ctx *c, const float *xyz, const float *uv, int n, const flo
     if (rcs != VO_OK)
         return rcs;
     vo_ctx::PoseBufs &pb = c->pb[c->last];
-    PnpParams pp;
-    pp.iters = c->prm.ransac_iterations;
-    pp.reproj = c->prm.ransac_reproj_error;
-    pp.confidence = c->prm.ransac_confidence;
-    memcpy(pp.K, K, sizeof(pp.K));
+    const PnpParams pp = pnp_params(c, K);
     // the correspondences in and the pose out through page-locked memory the kernels address (the staging buffer holds
     // 12 bytes x 4 max_pts or more, a correspondence is 20): one synchronisation per call, no copy call
     if (n > 0) {
         memcpy(c->h_feat_stage, xyz, sizeof(float) * 3 * (size_t)n);
         memcpy(c->h_feat_stage + sizeof(float) * 3 * (size_t)n, uv, sizeof(float2) * (size_t)n);
     }
-    launch_words_in(c->d_feat_stage, 3 * n, pb.xyz, 2 * n, pb.outB + 2 * (size_t)c->cap, pb.nB, n, c->stream);
+    launch_words_in(c->d_feat_stage, 3 * n, pb.xyz, 2 * n, pb.outB + 2 * (size_t)c->cap, pb.nB, n, c->sel->stream);
     if (c->n_frames < 1)
         c->n_frames = 1;
     launch_pnp(pb.xyz, pb.outB + 2 * (size_t)c->cap, (size_t)4 * c->cap, pb.nB, c->cap, 1, pp, pb.subsets,
-               pb.models, pb.counts, pb.rstate, pb.inliers, pb.results, standalone_waves(c), c->stream, pb.epnp_ws, 1, pb.epnp_gws, pb.rest_ws);
+               pb.models, pb.counts, pb.rstate, pb.inliers, pb.results, standalone_waves(c), c->sel->stream, pb.epnp_ws, 1, pb.epnp_gws, pb.rest_ws);
     FrameGather g = {};
     g.nA = g.nB = pb.nB;
     g.inliers = pb.inliers;
     g.result = pb.results;
     g.cap = c->cap;
     g.pose_only = 1;
-    launch_frame_gather(g, c->d_gather, c->stream);
+    launch_frame_gather(g, c->d_gather, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    PnpResult r;
-    memcpy(&r, c->h_gather + 16, sizeof(r));
-    // by the rules of get_pose_impl with pnp_rotation: R = Rodrigues(rvec) whatever vo_params.mono_rotation says
-    if (r.status == 0 && r.lm_iters < 0) { // four points, P3P without a solution: rvec / tvec stay the caller's
-        if (R_out && rvec_io)
-            rodrigues_v2m(rvec_io, R_out, nullptr);
-    } else if (r.status >= 0) {
-        if (rvec_io)
-            memcpy(rvec_io, r.rvec, sizeof(r.rvec));
-        if (tvec_io)
-            memcpy(tvec_io, r.tvec, sizeof(r.tvec));
-        if (R_out)
-            memcpy(R_out, r.R, sizeof(r.R));
-    }
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    const FrameGatherLayout L{(size_t)c->cap};
+    const PnpResult r = peek<PnpResult>(c->h_gather + L.pnp);
+    (void)deliver_pose(c, r, nullptr, rvec_io, tvec_io, R_out, /*pnp_rotation*/ true, /*io_pose*/ true); // (R = Rodrigues(rvec) whatever vo_params.mono_rotation says)
     const int ninl = r.n_inliers < c->cap ? r.n_inliers : c->cap;
     if (inliers && ninl > 0)
-        memcpy(inliers, c->h_gather + VO_GATHER_HEADER + (size_t)c->cap * (4 * 8 + 12 + 2 * 4), sizeof(int32_t) * (size_t)ninl);
+        memcpy(inliers, c->h_gather + L.inliers(), sizeof(int32_t) * (size_t)ninl);
     if (n_inliers)
         *n_inliers = r.n_inliers;
     if (r.status < 0)
-        return fail(c, VO_ERR_TOO_FEW, "fewer than 4 correspondences reached solvePnPRansac (CV_Assert(npoints >= 4))");
+        return fail_too_few_pnp(c);
     return r.status == 1 ? VO_OK : VO_NO_MODEL;
 }
 
@@ -247,8 +230,7 @@ int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride)
 {
     if (img && c && stride < w * fmt_bpp(c->prm.input_format))
         return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
-    if (!img && (c->tf_base < 0 || c->seq.on || c->n_images != 4 || c->n_frames != 1 || c->w != w || c->h != h ||
-                 c->img_stale[c->tf_base] || c->img_stale[c->tf_base + 1]))
+    if (!img && !have_kept_pair(c, w, h))
         return fail(c, VO_ERR_STATE, "no image given, and the context does not hold the t1 pair of a previous vo_track_frame "
                                      "of this size");
     int rc = vo_batch_configure(c, 4, w, h, 1);
@@ -288,22 +270,22 @@ int vo_fast_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, int 
         return rc;
     // (no copy call: the flags by features_in_kernel, the corners and their count back through page-locked memory, one
     // synchronisation -- see vo_detect_bucket)
-    launch_features_in(c->d_feat_stage, 0, 0, 0, /*detect*/ 1, c->d_feat, c->d_fages, c->fcap, c->d_ntracked, c->d_detect, c->stream);
+    launch_features_in(c->d_feat_stage, 0, 0, 0, /*detect*/ 1, c->d_feat, c->d_fages, c->fcap, c->d_ntracked, c->d_detect, c->sel->stream);
     c->h_ntracked[0] = 0;
     c->h_detect[0] = 1;
     c->detect_uploaded = true;
     threshold = threshold < 0 ? 0 : threshold > 255 ? 255 : threshold;
     launch_detect_bucket(c->d_imgs, c->quads_cur, c->d_detect, 1, w, h, threshold, nonmax, c->d_nmsmask, c->d_rowcnt, c->d_rowoff,
                          c->d_ntracked, c->d_nnew, c->fcap, c->d_feat, c->d_fages, /*bucket_size*/ 0, 1, nullptr,
-                         nullptr, nullptr, 0, nullptr, nullptr, c->stream);
-    launch_features_out(c->d_feat, c->d_fages, c->d_nnew, c->d_overflow, c->fcap, c->d_feat_stage, c->stream);
+                         nullptr, nullptr, 0, nullptr, nullptr, c->sel->stream);
+    launch_features_out(c->d_feat, c->d_fages, c->d_nnew, c->d_overflow, c->fcap, c->d_feat_stage, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int n = reinterpret_cast<const int *>(c->h_feat_stage)[0];
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    const int n = peek<int>(c->h_feat_stage + FeaturesOutLayout::count);
     int k = n < cap ? n : cap;
     k = k < c->fcap ? k : c->fcap;
     if (k > 0)
-        memcpy(pts_out, c->h_feat_stage + 16, sizeof(float2) * (size_t)k);
+        memcpy(pts_out, c->h_feat_stage + FeaturesOutLayout::pts, sizeof(float2) * (size_t)k);
     *n_out = n;
     if (n > c->fcap && cap > c->fcap) // the caller's buffer would have held them, the context's corner list does not
         return fail(c, VO_ERR_OVERFLOW, "vo_fast_detect: more corners than the context's corner-list capacity "
@@ -331,12 +313,12 @@ int vo_detect_bucket(vo_ctx *c, const uint8_t *img, int w, int h, int stride, co
     // synchronisations, 0.15 of its 0.18 ms on an idle GPU).  single_image_setup has drained the context.
     if (np > 0)
         memcpy(c->h_feat_stage, pts_io, sizeof(float2) * (size_t)np);
-    const size_t ages_off = sizeof(float2) * (size_t)c->fcap;
+    const size_t ages_off = features_in_ages(c->fcap);
     if (na > 0)
         memcpy(c->h_feat_stage + ages_off, ages_io, sizeof(int32_t) * (size_t)na);
     const int detect = np < c->dprm.redetect_below ? 1 : 0; // appendNewFeatures only then (visualOdometry.cpp:95)
     launch_features_in(c->d_feat_stage, ages_off, np, na, detect, c->d_feat, c->d_fages, c->fcap, c->d_ntracked, c->d_detect,
-                       c->stream);
+                       c->sel->stream);
     c->h_ntracked[0] = np;
     c->h_detect[0] = detect; // (what run_stages would upload: it finds the flag on the device already)
     c->detect_uploaded = true;
@@ -344,22 +326,19 @@ int vo_detect_bucket(vo_ctx *c, const uint8_t *img, int w, int h, int stride, co
     c->dprm = saved;
     if (rc != VO_OK)
         return rc;
-    launch_features_out(cur_pts(c), cur_ages(c), cur_npts(c), c->d_overflow, c->cap, c->d_gather, c->stream);
+    launch_features_out(cur_pts(c), cur_ages(c), cur_npts(c), c->d_overflow, c->cap, c->d_gather, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int k = reinterpret_cast<const int *>(c->h_gather)[0], ovf = reinterpret_cast<const int *>(c->h_gather)[1];
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    const FeaturesOutLayout L{(size_t)c->cap};
+    const int k = peek<int>(c->h_gather + L.count), ovf = peek<int>(c->h_gather + L.overflow);
     if (k > cap)
         return fail(c, VO_ERR_ARG, "vo_detect_bucket: bucketed set larger than the caller's capacity");
     const int kc = k < c->cap ? k : c->cap;
-    memcpy(pts_io, c->h_gather + 16, sizeof(float2) * (size_t)kc);
-    memcpy(ages_io, c->h_gather + 16 + sizeof(float2) * (size_t)c->cap, sizeof(int32_t) * (size_t)kc);
+    memcpy(pts_io, c->h_gather + L.pts, sizeof(float2) * (size_t)kc);
+    memcpy(ages_io, c->h_gather + L.ages(), sizeof(int32_t) * (size_t)kc);
     *n_pts = k;
     *n_ages = k;
-    if (ovf)
-        return fail(c, VO_ERR_OVERFLOW, ovf & 1 ? "VO_STAGE_DETECT: carried + detected features exceed the feature-list "
-                                                  "capacity (4 x max_pts, >= 16384, >= w * h / 16): bucketed set truncated"
-                                                : "VO_STAGE_DETECT: the bucketed set exceeds max_pts");
-    return VO_OK;
+    return ovf ? fail_overflow(c, ovf) : VO_OK;
 }
 
 int vo_integrate_odometry(double *pose, const double *R, const double *t, float *euler_out)
@@ -406,62 +385,39 @@ int vo_track_frame(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_
     g.em = mono ? pb.em_results : nullptr;
     g.cap = c->cap;
     if (pb.pending) { // (the chain ran on other streams: `done` covers the filter and both pose chains)
-        VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, pb.done, 0));
+        VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, pb.done, 0));
         pb.pending = false;
     }
-    launch_frame_gather(g, c->d_gather, c->stream);
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_frame_gather(g, c->d_gather, c->sel->stream);
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     VO_HOST_STAMP(8);
     const uint8_t *hb = c->h_gather;
-    int hdr[3];
-    memcpy(hdr, hb, sizeof(hdr));
-    const int M = hdr[0], K = hdr[1];
-    PnpResult r;
-    memcpy(&r, hb + 16, sizeof(r));
-    const size_t cap = (size_t)c->cap;
-    const uint8_t *arr = hb + VO_GATHER_HEADER;
+    const FrameGatherLayout L{(size_t)c->cap};
+    const int M = peek<int>(hb + L.n_circ), K = peek<int>(hb + L.n_out);
+    const PnpResult r = peek<PnpResult>(hb + L.pnp);
     float *outs[4] = {out_l0, out_r0, out_l1, out_r1};
     for (int k = 0; k < 4; k++)
         if (outs[k] && K > 0)
-            memcpy(outs[k], arr + (size_t)k * cap * 8, (size_t)K * 8);
-    const uint8_t *ax = arr + 4 * cap * 8, *ak = ax + cap * 12, *ac = ak + cap * 4, *ai = ac + cap * 4;
+            memcpy(outs[k], hb + L.row(k), (size_t)K * sizeof(float2));
     if (xyz_out && K > 0)
-        memcpy(xyz_out, ax, (size_t)K * 12);
+        memcpy(xyz_out, hb + L.xyz(), (size_t)K * 3 * sizeof(float));
     if (keep_idx && K > 0)
-        memcpy(keep_idx, ak, (size_t)K * 4);
+        memcpy(keep_idx, hb + L.keep_idx(), (size_t)K * sizeof(int32_t));
     if (keep_idx_circ && M > 0)
-        memcpy(keep_idx_circ, ac, (size_t)M * 4);
+        memcpy(keep_idx_circ, hb + L.keep_idx_circ(), (size_t)M * sizeof(int32_t));
     if (n_out)
         *n_out = K;
     if (n_circ)
         *n_circ = M;
-    // the pose, by the rules of vo_batch_get_pose / fetch_pose
-    if (r.status == 0 && r.lm_iters < 0) { // P3P without a solution: rvec / tvec untouched (see get_pose_impl)
-        if (R_out && rvec_io && !c->prm.mono_rotation)
-            rodrigues_v2m(rvec_io, R_out, nullptr);
-    } else if (r.status >= 0) {
-        if (rvec_io)
-            memcpy(rvec_io, r.rvec, sizeof(r.rvec));
-        if (tvec_io)
-            memcpy(tvec_io, r.tvec, sizeof(r.tvec));
-        if (R_out && !c->prm.mono_rotation)
-            memcpy(R_out, r.R, sizeof(r.R)); // `if (!mono_rotation) Rodrigues(rvec, rotation)` (visualOdometry.cpp:186-189)
-    }
-    int em_status = 1;
-    if (mono) {
-        EmResult e;
-        memcpy(&e, hb + 256, sizeof(e));
-        if (e.status == 1 && R_out)
-            memcpy(R_out, e.R, sizeof(e.R));
-        em_status = e.status;
-    }
+    const EmResult e = peek<EmResult>(hb + L.em); // (meaningful under mono only)
+    const int em_status = deliver_pose(c, r, mono ? &e : nullptr, rvec_io, tvec_io, R_out, /*pnp_rotation*/ false, /*io_pose*/ true);
     if (inliers && r.n_inliers > 0)
-        memcpy(inliers, ai, (size_t)r.n_inliers * 4);
+        memcpy(inliers, hb + L.inliers(), (size_t)r.n_inliers * sizeof(int32_t));
     if (n_inliers)
         *n_inliers = r.n_inliers;
     VO_HOST_STAMP(9);
     if (r.status < 0)
-        return fail(c, VO_ERR_TOO_FEW, "fewer than 4 correspondences reached solvePnPRansac (CV_Assert(npoints >= 4))");
+        return fail_too_few_pnp(c);
     if (em_status != 1) // mono_rotation and findEssentialMat found nothing: R_out was left untouched
         return VO_NO_ESSENTIAL;
     return r.status == 1 ? VO_OK : VO_NO_MODEL;

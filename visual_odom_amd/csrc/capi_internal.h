@@ -29,13 +29,89 @@ using namespace vo;
 #define VO_EV_PER_RUN (VO_NUM_STAGES + 3)
 #define VO_SEQ_MAX_RING 3
 
-// the HIP streams of one context (pooled per device, see acquire_streams)
+// Device memory, page-locked host memory and events of ONE lifetime (a context; a configuration of the lock-step loop): handed
+// out here, recorded, and released together.  The typed pointers the kernels and getters use stay where they are -- members of
+// vo_ctx -- and own nothing.  A request that fails leaves its pointer null and the HIP error in `err`.
+struct Owner {
+    std::vector<void *> dev, host;
+    std::vector<hipEvent_t> events;
+    hipError_t err = hipSuccess;
+    template <typename T>
+    bool device(T **p, size_t n, bool zero = false) // n elements
+    {
+        if ((err = hipMalloc((void **)p, n * sizeof(T))) != hipSuccess) {
+            *p = nullptr;
+            return false;
+        }
+        dev.push_back(*p);
+        return !zero || (err = hipMemset(*p, 0, n * sizeof(T))) == hipSuccess;
+    }
+    // flags: hipHostMallocMapped / hipHostMallocDefault; alias (optional): the address the GPU reads and writes the memory at
+    template <typename T>
+    bool pinned(T **p, size_t bytes, unsigned flags, uint8_t **alias = nullptr)
+    {
+        if ((err = hipHostMalloc((void **)p, bytes, flags)) != hipSuccess) {
+            *p = nullptr;
+            return false;
+        }
+        host.push_back(*p);
+        return !alias || (err = hipHostGetDevicePointer((void **)alias, *p, 0)) == hipSuccess;
+    }
+    bool event(hipEvent_t *e, bool timing = false)
+    {
+        if ((err = timing ? hipEventCreate(e) : hipEventCreateWithFlags(e, hipEventDisableTiming)) != hipSuccess) {
+            *e = nullptr;
+            return false;
+        }
+        events.push_back(*e);
+        return true;
+    }
+    template <typename T>
+    hipError_t give_back(T **p) // one buffer (device or host) now: a buffer that is regrown
+    {
+        void *v = *p;
+        *p = nullptr;
+        for (std::vector<void *> *list : {&dev, &host})
+            for (size_t i = 0; v && i < list->size(); i++)
+                if ((*list)[i] == v) {
+                    list->erase(list->begin() + i);
+                    return list == &dev ? hipFree(v) : hipHostFree(v);
+                }
+        return hipSuccess;
+    }
+    void release()
+    {
+        for (void *p : dev)
+            (void)hipFree(p);
+        for (void *p : host)
+            (void)hipHostFree(p);
+        for (hipEvent_t e : events)
+            (void)hipEventDestroy(e);
+        dev.clear();
+        host.clear();
+        events.clear();
+    }
+};
+
+// The HIP streams of one context (pooled per device, see acquire_streams).  One table, twice: the ordinary set and its
+// PARTITIONED twin on two disjoint halves of the compute units (capi.hip, ensure_partitioned_streams) -- the one-sequence
+// lock-step loop runs on that; vo_ctx::sel points at the one the context enqueues on.
+struct Streams {
+    hipStream_t stream = nullptr;                                          // tracking stream
+    hipStream_t pnp = nullptr, pnp2 = nullptr, filter = nullptr, em = nullptr; // post-LK streams
+    hipStream_t copy = nullptr, prep = nullptr; // lock-step loop's ingest: plain copy stream / highest-priority prepare stream
+};
+// THE list of a set's streams, in the order the partitioned twin creates them.  TRACK and INGEST streams get one half of the
+// compute units there and POST streams the other; the INGEST streams of the ordinary set are created on first use.
+enum StreamRole { TRACK, POST, INGEST };
+struct StreamSlot {
+    hipStream_t Streams::*m;
+    StreamRole role;
+};
+static const StreamSlot VO_STREAM_SLOTS[] = {{&Streams::stream, TRACK}, {&Streams::pnp, POST},    {&Streams::pnp2, POST}, {&Streams::filter, POST},
+                                            {&Streams::em, POST},      {&Streams::copy, INGEST}, {&Streams::prep, INGEST}};
 struct StreamSet {
-    hipStream_t stream = nullptr, pnp = nullptr, pnp2 = nullptr, filter = nullptr, em = nullptr;
-    hipStream_t copy = nullptr, prep = nullptr; // lock-step loop: plain copy stream / highest-priority prepare stream
-    // the PARTITIONED twin (capi.hip, ensure_partitioned_streams): stream, pnp, pnp2, filter, em, copy, prep on two disjoint
-    // halves of the compute units -- the one-sequence lock-step loop runs on it
-    hipStream_t part[7] = {};
+    Streams plain, part;
     bool part_tried = false;
     int id = 0; // creation rank on its device: the pool hands out the oldest free set first
 };
@@ -43,9 +119,10 @@ struct StreamSet {
 struct vo_ctx {
     int device = 0;
     StreamSet streams;
+    Streams *sel = &streams.plain; // the twin every launch goes to (select_streams)
+    Owner own;                    // everything allocated for the context's lifetime
     int max_w = 0, max_h = 0, cap = 0, max_frames = 0, max_images = 0;
     vo_params prm;
-    hipStream_t stream = nullptr; // tracking stream; all streams belong to `streams` (pooled per device)
     hipEvent_t ev[VO_EV_PER_RUN] = {}; // [0..3] tracking stream (3 stages), [4..7] post stream (3 stages)
     std::vector<hipEvent_t> ring; // VO_EVENT_SLOTS x (VO_EV_PER_RUN) for vo_batch_run_slot
     std::string err;
@@ -115,13 +192,11 @@ struct vo_ctx {
     int *d_fages = nullptr;        // [B][fcap] ages of d_feat (zero beyond the uploaded ages)
     int *d_ages = nullptr;         // [B][cap] ages of the bucketed set (parallel to d_pts)
     std::vector<int> h_ntracked, h_detect;
-    hipStream_t stream_pnp = nullptr, stream_filter = nullptr;
-    // second pose stream: in a SMALL batch the pose chain is a few latency-bound waves (1.0-1.3 ms for one frame) and
+    // second pose stream (Streams::pnp2): in a SMALL batch the pose chain is a few latency-bound waves (1.0-1.3 ms for one frame) and
     // longer than the tracking stages of the next run, so back-to-back runs were throttled by it (lock-step loop with
     // one sequence: 1.35 ms per step, of which 1.3 ms waiting behind the previous step's chain).  Runs alternate between
     // the two buffer sets anyway; giving each set its own stream lets two chains overlap.  Whether that pays is part of
     // the SCHEDULE, which is probed, not looked up (see Schedule below).
-    hipStream_t stream_pnp2 = nullptr;
     // How the pose chain is scheduled next to the tracking stages -- three knobs, none of which changes a result:
     //   waves   register budget of the f64 pose kernels as waves per SIMD: 1 = 512 registers (fastest alone, but such a
     //           wave only starts on a completely empty SIMD and keeps the next run's kernels waiting), 2 = 256 registers
@@ -151,8 +226,6 @@ struct vo_ctx {
     float probe_ms[VO_PROBE_LOG_MAX] = {};
     int probe_real[VO_PROBE_LOG_MAX] = {};          // 1: probe_ms[i] was (re)measured over real steps of the lock-step loop
     hipStream_t last_pose_stream = nullptr; // stream the latest pose chain was enqueued on
-    hipStream_t stream_em = nullptr; // essential-matrix chain of the mono_rotation branch, next to the PnP chain
-    bool partitioned = false; // stream / stream_pnp ... are the partitioned twin of `streams` (select_streams)
     bool quads_set = false; // d_quads holds h_quads (cleared whenever the table is zeroed)
     // synchronous drop-in calls (capi_dropin.hip): image slot of the LEFT image of the stereo pair the last vo_track_frame /
     // vo_circular_match received as its t1 pair (0 or 2; its right image follows it), pyramids built -- the next call may name it
@@ -195,6 +268,7 @@ struct vo_ctx {
     // ---- lock-step sequence loop (vo_seq_*): S sequences x 1 frame per step, state carried on the device ----
     struct Seq {
         bool on = false;
+        Owner own; // everything allocated for this configuration (seq_free)
         int S = 0, ring = 0, max_steps = 0;
         long long step = 0;           // steps enqueued so far
         Quad *d_quads = nullptr;      // [ring][S]: phase r = (t0 in ring slot r, t1 in slot (r + 1) % ring)
@@ -208,7 +282,6 @@ struct vo_ctx {
         std::vector<uint8_t> ever, gap;        // has had a pair since its reset / resumes after a pause (VO_SEQ_F_GAP)
         std::vector<int> h_rows;               // frames processed per sequence since its reset (host mirror of d_rows)
         bool broken = false;                   // a step failed after it had consumed its pairs: vo_seq_reset(-1) first
-        hipStream_t copy = nullptr;
         hipEvent_t ev_upload = nullptr, ev_carry = nullptr, ev_integ = nullptr;
         bool integ_pending = false;
         hipEvent_t ev_slot_free[VO_SEQ_MAX_RING] = {}; // the LK that read ring slot r as its t0 pair has finished
@@ -232,7 +305,7 @@ struct vo_ctx {
         // their pyramids, and FAST + non-maximum suppression of their LEFT images -- the corners the NEXT step's
         // appendNewFeatures needs (visualOdometry.cpp:95-101 detects on imageLeft_t0, i.e. on the pair that arrived one
         // step earlier).  Per step the tracking stream is left with: bucketing -> LK -> filter -> carry.
-        // (whether the prepare stream is used is vo_ctx::sched.prep; `copy` below is the stream the step's ingest kernel
+        // (whether the prepare stream is used is vo_ctx::sched.prep; ingest_stream() is the stream the step's ingest kernel
         // goes to: the prepare stream when it is, a plain copy stream when not)
         float2 *d_corners = nullptr;      // [ring][S][fcap] FAST corners of the left image in each ring slot
         int *d_ncorn = nullptr;           // [ring][S]
@@ -262,20 +335,22 @@ struct vo_ctx {
 #define VO_CONST_QUADS 4
 static const vo::Quad VO_CONST_QUAD_TABLE[VO_CONST_QUADS] = {{0, 1, 2, 3}, {2, 3, 0, 1}, {0, 0, 0, 0}, {2, 2, 2, 2}};
 
-#define VO_HIP_TRY(ctx, call)                                                                         \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) {                                                                       \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                           \
-            return VO_ERR_HIP;                                                                        \
-        }                                                                                             \
-    } while (0)
-
 inline int fail(vo_ctx *ctx, int code, const char *msg)
 {
     ctx->err = msg;
     return code;
 }
+inline int fail_hip(vo_ctx *ctx, const char *what, hipError_t e)
+{
+    ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+    return VO_ERR_HIP;
+}
+#define VO_HIP_TRY(ctx, call)                                                                         \
+    do {                                                                                              \
+        hipError_t e_ = (call);                                                                       \
+        if (e_ != hipSuccess)                                                                         \
+            return fail_hip(ctx, #call, e_);                                                          \
+    } while (0)
 
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 // register budget of the pose kernels for the stand-alone calls (vo_pnp_ransac, vo_essential_pose): nothing runs beside
@@ -299,10 +374,23 @@ inline int level_stride(int w) { return align_up(VO_BX + w + VO_BY, 16); }
 inline int fmt_bpp(int fmt) { return fmt == VO_FMT_GRAY8 ? 1 : fmt == VO_FMT_GRAY8_X2 ? 2 : fmt <= VO_FMT_RGB8 ? 3 : 4; }
 inline size_t fmt_row_bytes(int fmt, int w) { return fmt == VO_FMT_GRAY8_X2 ? 2 * (size_t)w - 1 : (size_t)w * fmt_bpp(fmt); }
 
+// the stream the lock-step loop's ingest kernel goes to (created by ensure_ingest_stream; set_sched keeps it in existence)
+inline hipStream_t ingest_stream(const vo_ctx *c) { return c->sched.prep ? c->sel->prep : c->sel->copy; }
+// frames the EPnP workspaces of a pose buffer set are allocated for
+inline int epnp_ws_frames(const vo_ctx *c) { return c->max_frames < VO_EPNP_WS_MAX_FRAMES ? c->max_frames : VO_EPNP_WS_MAX_FRAMES; }
+// the pair of timing events (indices into the VO_EV_PER_RUN events of a run) that brackets stage s of the timing order PYRAMID,
+// DETECT, LK, FILTER, TRIANGULATE, PNP: run_stages records by it, the timed getters read by it
+struct StageEvents {
+    int start, end;
+};
+inline StageEvents stage_events(int s) { return {s == 1 ? VO_NUM_STAGES + 2 : s < 3 ? s : s + 1, s < 3 ? s + 1 : s + 2}; }
+// a value out of a host-visible result buffer
 template <typename T>
-hipError_t dmalloc(T **p, size_t n)
+T peek(const uint8_t *p)
 {
-    return hipMalloc((void **)p, n * sizeof(T));
+    T v;
+    memcpy(&v, p, sizeof(T));
+    return v;
 }
 
 constexpr int EM_MAX_ITERS = 1000; // maxIters of the findEssentialMat overload the reference calls (OpenCV 4.5)
@@ -327,7 +415,7 @@ inline int pts_bucket(long long pts) { return pts <= 0 ? 0 : (int)floor(2.0 * lo
 #define D2H(dst, src, bytes)                                                                           \
     do {                                                                                              \
         if ((dst) && (bytes) > 0)                                                                      \
-            VO_HIP_TRY(c, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, c->stream));   \
+            VO_HIP_TRY(c, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToHost, c->sel->stream)); \
     } while (0)
 
 namespace vo_capi {
@@ -335,7 +423,7 @@ extern std::mutex g_tune_mu;
 extern std::map<TuneKey, vo_ctx::Schedule> g_tuned; // per process: a second context of the same shape starts tuned
 int plan_levels(vo_ctx *c, int w, int h);
 bool acquire_streams(int device, StreamSet *out);
-hipStream_t ensure_copy_stream(StreamSet *s, bool prepare, bool partitioned = false);
+hipStream_t ensure_ingest_stream(vo_ctx *c, bool prepare);
 bool ensure_partitioned_streams(StreamSet *s, int device);
 int select_streams(vo_ctx *c, bool partitioned); // call with every stream idle
 void release_streams(int device, const StreamSet &s);
@@ -359,6 +447,11 @@ int probe_run(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry);
 int probe_candidate(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry, bool latency, double *ms_per_run);
 int tune_schedule(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry, bool latency = false, bool publish = true);
 int run_stages_auto(vo_ctx *c, int stages, bool timed, hipEvent_t *evs = nullptr, bool sync_call = false);
+PnpParams pnp_params(const vo_ctx *c, const float *K = nullptr);
+bool have_kept_pair(const vo_ctx *c, int w, int h);
+int deliver_pose(const vo_ctx *c, const PnpResult &r, const EmResult *e, double *rvec, double *tvec, double *R, bool pnp_rotation, bool io_pose);
+int fail_overflow(vo_ctx *c, int ovf);
+int fail_too_few_pnp(vo_ctx *c);
 int get_pose_impl(vo_ctx *c, int frame, double *rvec, double *tvec, double *R, int32_t *inliers, int *n_inliers, int *status, int32_t *dbg4, bool pnp_rotation, int *em_status, bool io_pose = true);
 int seq_begin_step(vo_ctx *c);
 int seq_push(vo_ctx *c, int seq, const void *left, const void *right, int stride, int mode);

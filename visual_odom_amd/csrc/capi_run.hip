@@ -35,8 +35,9 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
     const bool crowded = c->sched.waves >= 2; // essential-matrix kernels: their reduced-register variant goes with the PnP one
     vo_ctx::Seq &sq = c->seq;
     const bool prep = sq.on && c->sched.prep; // lock-step loop: pyramids (and, from vo_seq_step, FAST) on the prepare stream
-    hipStream_t pyrs = prep ? sq.copy : c->stream;
-    int e = 0;
+    hipStream_t pyrs = prep ? c->sel->prep : c->sel->stream;
+    // the timing events of the run: stage_events() says which pair brackets a stage
+    enum { PYR, DET, LK, FIL, TRI, PNP };
     // A synchronous drop-in call on the kept pair that left its t1 pair in host memory (single_frame_setup): hop 0 of the LK
     // chain reads the t0 pair only, so it starts before the t1 pair has crossed PCIe -- lk_hops_kernel [0, 1) on the tracking
     // stream, the two pulls + the t1 pyramids on the idle filter stream beside it, lk_hops_kernel [1, 4) behind ev_t1_ready.
@@ -45,13 +46,12 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
     const bool split = c->defer.n == 2 && !sq.on && B == 1 && (stages & VO_STAGE_PYRAMID) && (stages & VO_STAGE_LK) &&
                        !(stages & VO_STAGE_DETECT) && !c->tuning;
     if (c->defer.n && !split) {
-        int rcd = flush_deferred(c, c->stream);
+        int rcd = flush_deferred(c, c->sel->stream);
         if (rcd != VO_OK)
             return rcd;
     }
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], pyrs));
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(PYR).start], pyrs));
     if (!split && (stages & VO_STAGE_PYRAMID)) { // (split: the t1 pyramids follow their pixels, in the LK stage below)
         const PyrImage *tab = c->d_imgs + c->pyr_first;
         const int ni = c->pyr_count;
@@ -74,17 +74,16 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
         }
     }
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], pyrs));
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(PYR).end], pyrs));
     // DETECT and LK write the set of buffers (bucketed features / tracks + status) that the filter of two runs
     // ago read; the filter of the previous run reads the other set
     const int wset = (stages & (VO_STAGE_DETECT | VO_STAGE_LK)) ? c->trk_next : c->trk_last;
     if ((stages & (VO_STAGE_DETECT | VO_STAGE_LK)) && c->trk_busy[wset]) {
-        VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trk_free[wset], 0));
+        VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, c->ev_trk_free[wset], 0));
         c->trk_busy[wset] = false;
     }
     if (timed && !(stages & VO_STAGE_DETECT))
-        VO_HIP_TRY(c, hipEventRecord(evs[VO_NUM_STAGES + 2], c->stream));
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(DET).start], c->sel->stream));
     if (stages & VO_STAGE_DETECT) {
         const int bs = c->dprm.bucket_size > 0 ? c->dprm.bucket_size : c->h / 10;
         const int fpb = c->dprm.features_per_bucket;
@@ -95,11 +94,11 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             return fail(c, VO_ERR_ARG, "vo_batch_run: VO_STAGE_DETECT handles images up to 4096 pixels wide");
         // appendNewFeatures only when fewer than redetect_below features were carried in (visualOdometry.cpp:95)
         if (timed)
-            VO_HIP_TRY(c, hipEventRecord(evs[VO_NUM_STAGES + 2], c->stream));
+            VO_HIP_TRY(c, hipEventRecord(evs[stage_events(DET).start], c->sel->stream));
         if (sq.on) {
             // the carried set lives on the device (seq_carry_kernel of the previous step wrote it on the filter stream)
             if (sq.carry_pending) {
-                VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, sq.ev_carry, 0));
+                VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, sq.ev_carry, 0));
                 sq.carry_pending = false;
             }
             const int rp = (int)((sq.step - 1) % sq.ring); // ring slot of this step's t0 pair
@@ -107,11 +106,11 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             for (int r2 = 0; r2 < sq.ring; r2++)
                 if (sq.fast_pending[r2] && (r2 == rp || !ahead)) {
                     // (inline detection shares the FAST scratch buffers with a look-ahead pass that may still run)
-                    VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, sq.ev_fast[r2], 0));
+                    VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, sq.ev_fast[r2], 0));
                     sq.fast_pending[r2] = false;
                 }
             launch_seq_prepare(seq_active, c->d_ntracked, c->dprm.redetect_below, c->d_detect,
-                               ahead ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, c->stream);
+                               ahead ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, c->sel->stream);
             c->detect_uploaded = false;
         } else {
             bool changed = false;
@@ -122,8 +121,8 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             }
             if (changed || !c->detect_uploaded) {
                 VO_HIP_TRY(c, hipMemcpyAsync(c->d_detect, c->h_detect.data(), sizeof(int) * B, hipMemcpyHostToDevice,
-                                             c->stream));
-                VO_HIP_TRY(c, hipStreamSynchronize(c->stream)); // h_detect is reused by the next call
+                                             c->sel->stream));
+                VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream)); // h_detect is reused by the next call
                 c->detect_uploaded = true;
             }
         }
@@ -133,15 +132,15 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             const int rp = (int)((sq.step - 1) % sq.ring);
             launch_bucket(c->d_feat, sq.d_corners + (size_t)rp * sq.S * c->fcap, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap,
                           c->w, c->h, bs, fpb, c->d_pts_det[wset], c->d_ages_det[wset], c->d_npts_det[wset], cap, seq_active,
-                          c->d_overflow, B, c->stream);
+                          c->d_overflow, B, c->sel->stream);
         } else {
             launch_detect_bucket(c->d_imgs, c->quads_cur, c->d_detect, B, c->w, c->h, t, c->dprm.fast_nonmax,
                                  c->d_nmsmask, c->d_rowcnt, c->d_rowoff, c->d_ntracked, c->d_nnew, c->fcap, c->d_feat, c->d_fages, bs, fpb,
                                  c->d_pts_det[wset], c->d_ages_det[wset], c->d_npts_det[wset], cap, seq_active,
-                                 c->d_overflow, c->stream);
+                                 c->d_overflow, c->sel->stream);
         }
         if (sq.on && !prep) { // (seq_enqueue_inputs: the NEXT step's PCIe ingest waits for this)
-            VO_HIP_TRY(c, hipEventRecord(sq.ev_detect, c->stream));
+            VO_HIP_TRY(c, hipEventRecord(sq.ev_detect, c->sel->stream));
             sq.detect_pending = true;
         }
         c->pts_sel = wset;
@@ -151,11 +150,10 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
         c->pts_on_device = true;
     }
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], c->stream));
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(DET).end], c->sel->stream)); // (= start of LK)
     if (stages & VO_STAGE_LK) {
         if (prep) // the t1 pyramids of this step were built on the prepare stream
-            VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, sq.ev_pyr, 0));
+            VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, sq.ev_pyr, 0));
         LkParams lp;
         lp.max_level = c->levels - 1;
         int mc = c->prm.lk_max_count;
@@ -170,8 +168,8 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             if (c->img_stale[q.l0] | c->img_stale[q.r0])
                 return fail(c, VO_ERR_STATE, "synchronous call: the t0 pair has no pyramids");
             launch_lk_hops(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
-                           c->d_status2[wset], lp, 0, 1, c->stream);
-            hipStream_t side = c->stream_filter; // idle: the chain of a synchronous call stays on the tracking stream
+                           c->d_status2[wset], lp, 0, 1, c->sel->stream);
+            hipStream_t side = c->sel->filter; // idle: the chain of a synchronous call stays on the tracking stream
             const int t1 = c->defer.first;
             int rcd = flush_deferred(c, side);
             if (rcd != VO_OK)
@@ -179,26 +177,25 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             launch_pyramid_fused(c->d_imgs + t1, 2, c->levels, c->lw, c->lh, c->lstride, side);
             c->img_stale[t1] = c->img_stale[t1 + 1] = 0;
             VO_HIP_TRY(c, hipEventRecord(c->ev_t1_ready, side));
-            VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_t1_ready, 0));
+            VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, c->ev_t1_ready, 0));
             if (c->img_stale[q.l1] | c->img_stale[q.r1])
                 return fail(c, VO_ERR_STATE, "synchronous call: the t1 pair has no pyramids");
             launch_lk_hops(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
-                           c->d_status2[wset], lp, 1, 4, c->stream);
+                           c->d_status2[wset], lp, 1, 4, c->sel->stream);
         } else
             launch_lk_circular(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
-                               c->d_status2[wset], lp, c->stream);
+                               c->d_status2[wset], lp, c->sel->stream);
         c->trk_last = wset;
         c->trk_next = wset ^ 1;
         if (sq.on) { // the ring slots holding this step's pairs may be overwritten once this LK has finished
             const int r0 = (int)((sq.step - 1) % sq.ring), r1 = (int)(sq.step % sq.ring);
-            VO_HIP_TRY(c, hipEventRecord(sq.ev_slot_free[r0], c->stream));
-            VO_HIP_TRY(c, hipEventRecord(sq.ev_slot_free[r1], c->stream));
+            VO_HIP_TRY(c, hipEventRecord(sq.ev_slot_free[r0], c->sel->stream));
+            VO_HIP_TRY(c, hipEventRecord(sq.ev_slot_free[r1], c->sel->stream));
             sq.slot_busy[r0] = sq.slot_busy[r1] = true;
         }
     }
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], c->stream)); // evs[3]: end of LK on the tracking stream
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(LK).end], c->sel->stream)); // end of LK on the tracking stream
     // Everything after LK is small, latency-bound work and leaves the tracking stream so that the next
     // run's pyramid / LK launches overlap it:
     //   filter stream: filter + triangulation of run k start as soon as LK(k) is done (they must not
@@ -211,15 +208,15 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
     // three cross-stream hand-offs of the chain (~12 us each in the kernel timeline of one call).
     const bool serial = c->serial_pose || (c->sync_call && !sq.on);
     c->last_run_serial = serial;
-    hipStream_t fs = serial ? c->stream : c->stream_filter;
+    hipStream_t fs = serial ? c->sel->stream : c->sel->filter;
     const bool two_pose_streams = !serial && !c->prm.mono_rotation && c->sched.streams == 2;
-    hipStream_t ps = serial ? c->stream : (two_pose_streams && (c->cur & 1)) ? c->stream_pnp2 : c->stream_pnp;
+    hipStream_t ps = serial ? c->sel->stream : (two_pose_streams && (c->cur & 1)) ? c->sel->pnp2 : c->sel->pnp;
     // (serial: filter, triangulation and pose chain follow LK on the tracking stream itself -- stream order is the dependency,
     // and none of the events that hand work from one stream to the next is recorded: each cost ~6 us of idle GPU between two
     // kernels of the synchronous call, three of them per call, profiles/r04_track_frame_timeline.txt)
     if (touches_pose) {
         if (!serial) {
-            VO_HIP_TRY(c, hipEventRecord(pb.ready, c->stream));
+            VO_HIP_TRY(c, hipEventRecord(pb.ready, c->sel->stream));
             VO_HIP_TRY(c, hipStreamWaitEvent(fs, pb.ready, 0));
         }
         if (pb.pending) {
@@ -227,10 +224,9 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             pb.pending = false;
         }
     }
-    hipStream_t ts = touches_pose ? fs : c->stream;
+    hipStream_t ts = touches_pose ? fs : c->sel->stream;
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], ts)); // evs[4]
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(FIL).start], ts));
     if (stages & VO_STAGE_FILTER) {
         launch_compact(cur_pts(c), c->d_trk2[c->trk_last], c->d_status2[c->trk_last], cur_npts(c), cap,
                        c->prm.consistency_threshold, c->d_outA, c->d_idxA, c->d_nA, pb.outB, pb.idxB, pb.nB, B, fs);
@@ -256,27 +252,18 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
         }
     }
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], ts)); // evs[5]
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(FIL).end], ts)); // (= start of triangulation)
     if (stages & VO_STAGE_TRIANGULATE) // stage-B rows: 0 = l0, 1 = r0, 2 = l1, 3 = r1
         launch_triangulate(c->d_P, c->d_P + 12, pb.outB, pb.outB + cap, (size_t)4 * cap, pb.nB, cap,
                            c->max_pts_set, B, pb.xyz, fs);
     if (timed)
-        VO_HIP_TRY(c, hipEventRecord(evs[e], ts)); // evs[6]: end of triangulation
-    e++;
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(TRI).end], ts)); // end of triangulation
     if (stages & VO_STAGE_PNP) {
         if (!serial) {
             VO_HIP_TRY(c, hipEventRecord(pb.tri_done, fs));
             VO_HIP_TRY(c, hipStreamWaitEvent(ps, pb.tri_done, 0));
         }
-        PnpParams pp;
-        pp.iters = c->prm.ransac_iterations;
-        pp.reproj = c->prm.ransac_reproj_error;
-        pp.confidence = c->prm.ransac_confidence;
-        // intrinsic_matrix = projMatrl(0:3, 0:3) (visualOdometry.cpp:163-165)
-        for (int r = 0; r < 3; r++)
-            for (int k = 0; k < 3; k++)
-                pp.K[r * 3 + k] = c->h_P[r * 4 + k];
+        const PnpParams pp = pnp_params(c);
         if (c->prm.mono_rotation) {
             // rotation from the essential matrix of (pointsLeft_t0, pointsLeft_t1) = stage-B rows 0 and 2
             // (visualOdometry.cpp:146-157); the PnP solve below still provides the translation
@@ -292,7 +279,7 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
             ep.max_iters = EM_MAX_ITERS;
             // its own stream: the two chains only share their inputs, and together they would outlast the LK
             // launch they hide behind
-            hipStream_t es = serial ? c->stream : c->stream_em;
+            hipStream_t es = serial ? c->sel->stream : c->sel->em;
             if (!serial)
                 VO_HIP_TRY(c, hipStreamWaitEvent(es, pb.tri_done, 0));
             launch_essential(pb.outB, pb.outB + 2 * cap, (size_t)4 * cap, pb.nB, cap, B, ep, c->em, pb.em_results,
@@ -301,9 +288,7 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
                 VO_HIP_TRY(c, hipEventRecord(pb.em_done, es));
         }
         launch_pnp_ransac(pb.xyz, pb.outB + 2 * cap, (size_t)4 * cap, pb.nB, cap, B, pp, pb.subsets, pb.models, pb.counts,
-                          pb.rstate, c->sched.waves, ps, pb.epnp_ws,
-                          c->max_frames < VO_EPNP_WS_MAX_FRAMES ? c->max_frames : VO_EPNP_WS_MAX_FRAMES, pb.epnp_gws, c->sched.wide,
-                          pb.rest_ws);
+                          pb.rstate, c->sched.waves, ps, pb.epnp_ws, epnp_ws_frames(c), pb.epnp_gws, c->sched.wide, pb.rest_ws);
         if (c->prm.mono_rotation && !serial)
             VO_HIP_TRY(c, hipStreamWaitEvent(ps, pb.em_done, 0)); // `done` covers both chains; the tail below reads E's rotation
         SeqTail tail;
@@ -331,13 +316,13 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
         }
         c->last_pose_stream = ps;
         if (timed)
-            VO_HIP_TRY(c, hipEventRecord(evs[e], ps)); // evs[7]: pose solve timed from the end of triangulation
+            VO_HIP_TRY(c, hipEventRecord(evs[stage_events(PNP).end], ps)); // pose solve timed from the end of triangulation
         if (!serial) { // (serial: whoever needs the results waits for the tracking stream)
             VO_HIP_TRY(c, hipEventRecord(pb.done, ps));
             pb.pending = true;
         }
     } else if (timed) {
-        VO_HIP_TRY(c, hipEventRecord(evs[e], ts));
+        VO_HIP_TRY(c, hipEventRecord(evs[stage_events(PNP).end], ts));
     }
     VO_HIP_TRY(c, hipGetLastError());
     if (touches_pose) {
@@ -351,18 +336,13 @@ int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry)
 int sync_all(vo_ctx *c)
 {
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream_filter));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream_pnp));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream_pnp2));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->stream_em));
-    if (c->streams.copy)
-        VO_HIP_TRY(c, hipStreamSynchronize(c->streams.copy));
-    if (c->streams.prep)
-        VO_HIP_TRY(c, hipStreamSynchronize(c->streams.prep));
-    if (c->partitioned) // (the copy / prepare streams of the partitioned twin; its other streams are the ones above)
-        for (int k = 5; k < 7; k++)
-            VO_HIP_TRY(c, hipStreamSynchronize(c->streams.part[k]));
+    for (const StreamSlot &k : VO_STREAM_SLOTS) {
+        if (k.role != INGEST || c->sel->*k.m) // (the ordinary set's ingest streams exist from their first use on)
+            VO_HIP_TRY(c, hipStreamSynchronize(c->sel->*k.m));
+        // while the partitioned twin is selected, the ordinary set's ingest streams are waited for all the same
+        if (k.role == INGEST && c->sel != &c->streams.plain && c->streams.plain.*k.m)
+            VO_HIP_TRY(c, hipStreamSynchronize(c->streams.plain.*k.m));
+    }
     return VO_OK;
 }
 

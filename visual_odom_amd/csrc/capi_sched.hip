@@ -65,12 +65,11 @@ bool all_pinned(const vo_ctx *c)
 // ordered per stream).
 int set_sched(vo_ctx *c, const vo_ctx::Schedule &s)
 {
-    if (c->seq.on && (s.prep != c->sched.prep || !c->seq.copy)) {
+    if (c->seq.on && (s.prep != c->sched.prep || !ingest_stream(c))) {
         int rc = sync_all(c);
         if (rc != VO_OK)
             return rc;
-        c->seq.copy = ensure_copy_stream(&c->streams, s.prep != 0, c->partitioned);
-        if (!c->seq.copy)
+        if (!ensure_ingest_stream(c, s.prep != 0))
             return fail(c, VO_ERR_HIP, "could not create the copy stream");
         for (auto &b : c->seq.fast_pending)
             b = false;
@@ -119,9 +118,10 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
 {
     vo_ctx::Seq &q = c->seq;
     const int slot = (int)(q.step % VO_SEQ_INFLIGHT), r = (int)(q.step % q.ring);
+    hipStream_t copy = ingest_stream(c);
     if (q.n_ing > 0) {
         if (!dry && q.slot_busy[r]) {
-            VO_HIP_TRY(c, hipStreamWaitEvent(q.copy, q.ev_slot_free[r], 0));
+            VO_HIP_TRY(c, hipStreamWaitEvent(copy, q.ev_slot_free[r], 0));
             q.slot_busy[r] = false;
         }
         SeqIngest *d_tab = q.d_ing + (size_t)slot * q.S;
@@ -134,7 +134,7 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
         // per step through the kernel, 0.80 through the engine; 64: 1.67 / 1.63; 256: 5.20 / 4.77 and, at 2 000 points, 11.34 / 10.28)
         if (q.d_stage && q.S >= 32 && q.n_pageable == q.S && q.n_ing == q.S) {
             const size_t half = q.stage_img * 2 * (size_t)q.S, off = (size_t)(q.step & 1) * half;
-            VO_HIP_TRY(c, hipMemcpyAsync(q.d_stage + off, q.h_stage + off, half, hipMemcpyHostToDevice, q.copy));
+            VO_HIP_TRY(c, hipMemcpyAsync(q.d_stage + off, q.h_stage + off, half, hipMemcpyHostToDevice, copy));
             if (!dry) // (a dry re-run finds the entries already pointing at the device twin)
                 for (int i = 0; i < q.n_ing; i++) {
                     h_tab[i].left = q.d_stage + (h_tab[i].left - q.h_stage);
@@ -155,7 +155,8 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
         if (over_pcie && !dry && q.step > VO_SEQ_INFLIGHT + 1) {
             hipEvent_t *old = &c->ring[(size_t)((q.step - VO_SEQ_INFLIGHT - 1) % VO_EVENT_SLOTS) * (VO_EV_PER_RUN)];
             float lk_ms = 0.f;
-            if (hipEventQuery(old[3]) == hipSuccess && hipEventElapsedTime(&lk_ms, old[2], old[3]) == hipSuccess)
+            const StageEvents lk = stage_events(2);
+            if (hipEventQuery(old[lk.end]) == hipSuccess && hipEventElapsedTime(&lk_ms, old[lk.start], old[lk.end]) == hipSuccess)
                 wait_detect = (double)lk_ms >= 1.6 * ((double)q.n_ing * 2.0 * c->w * c->h / 48e6);
             else
                 (void)hipGetLastError(); // (a step without an LK stage left no such events)
@@ -163,30 +164,30 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
         if (dev_knob("VO_INGEST_WAIT", -1) >= 0) // A/B: 0 / 1 force
             wait_detect = dev_knob("VO_INGEST_WAIT", -1) != 0;
         if (wait_detect && over_pcie && !dry && !c->sched.prep && q.detect_pending) {
-            VO_HIP_TRY(c, hipStreamWaitEvent(q.copy, q.ev_detect, 0));
+            VO_HIP_TRY(c, hipStreamWaitEvent(copy, q.ev_detect, 0));
             q.detect_pending = false;
         }
-        VO_HIP_TRY(c, hipMemcpyAsync(d_tab, h_tab, sizeof(SeqIngest) * q.n_ing, hipMemcpyHostToDevice, q.copy));
+        VO_HIP_TRY(c, hipMemcpyAsync(d_tab, h_tab, sizeof(SeqIngest) * q.n_ing, hipMemcpyHostToDevice, copy));
         if (c->prm.input_format == VO_FMT_GRAY8)
             launch_seq_ingest(d_tab, q.n_ing, c->w, c->h, c->lstride[0],
-                              c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, q.copy);
+                              c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, copy);
         else if (launch_seq_ingest_fmt(c->prm.input_format, d_tab, q.n_ing, c->w, c->h, c->lstride[0], // (ingest_fmt.hip: converts on the way)
-                                       c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, q.copy) != 0)
+                                       c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, copy) != 0)
             return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
         if (!dry && q.staged) {
             const int g = (int)(q.step & 1);
-            VO_HIP_TRY(c, hipEventRecord(q.ev_stage[g], q.copy));
+            VO_HIP_TRY(c, hipEventRecord(q.ev_stage[g], copy));
             q.stage_busy[g] = true;
             q.staged = false;
         }
     }
     if (!c->sched.prep) {
-        VO_HIP_TRY(c, hipEventRecord(q.ev_upload, q.copy));
-        VO_HIP_TRY(c, hipStreamWaitEvent(c->stream, q.ev_upload, 0));
+        VO_HIP_TRY(c, hipEventRecord(q.ev_upload, copy));
+        VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, q.ev_upload, 0));
     }
     if (q.n_active > 0)
         VO_HIP_TRY(c, hipMemcpyAsync(q.d_active + (size_t)slot * q.S, q.h_active + (size_t)slot * q.S, sizeof(int) * q.S,
-                                     hipMemcpyHostToDevice, c->stream));
+                                     hipMemcpyHostToDevice, c->sel->stream));
     return VO_OK;
 }
 
@@ -199,8 +200,8 @@ int seq_lookahead(vo_ctx *c, int r)
     t = t < 0 ? 0 : t > 255 ? 255 : t;
     launch_fast_corners(c->d_imgs, q.d_quads + (size_t)r * q.S, nullptr, q.S, c->w, c->h, t, c->dprm.fast_nonmax,
                         c->d_nmsmask, c->d_rowcnt, c->d_rowoff, nullptr, q.d_ncorn + (size_t)r * q.S, c->fcap,
-                        q.d_corners + (size_t)r * q.S * c->fcap, q.copy);
-    VO_HIP_TRY(c, hipEventRecord(q.ev_fast[r], q.copy));
+                        q.d_corners + (size_t)r * q.S * c->fcap, ingest_stream(c));
+    VO_HIP_TRY(c, hipEventRecord(q.ev_fast[r], ingest_stream(c)));
     q.fast_pending[r] = true;
     q.have_corners[r] = true;
     VO_HIP_TRY(c, hipGetLastError());

@@ -14,37 +14,9 @@ namespace vo_capi {
 void seq_free(vo_ctx *c)
 {
     vo_ctx::Seq &q = c->seq;
-    void *ptrs[] = {q.d_quads, q.d_active, q.d_pose, q.d_traj, q.d_info, q.d_rows, q.d_rows_carry, q.d_nages, q.d_ing,
-                    q.d_corners, q.d_ncorn};
-    for (void *p : ptrs)
-        if (p)
-            (void)hipFree(p);
-    if (q.h_active)
-        (void)hipHostFree(q.h_active);
-    if (q.h_ing)
-        (void)hipHostFree(q.h_ing);
-    if (q.h_stage)
-        (void)hipHostFree(q.h_stage);
-    if (q.d_stage)
-        (void)hipFree(q.d_stage);
-    hipEvent_t evs[] = {q.ev_upload, q.ev_carry, q.ev_integ, q.ev_pyr, q.ev_stage[0], q.ev_stage[1], q.ev_detect};
-    for (auto &e : q.ev_fast)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : q.ev_ab)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (hipEvent_t e : evs)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : q.ev_slot_free)
-        if (e)
-            (void)hipEventDestroy(e);
-    for (auto &e : q.ev_step)
-        if (e)
-            (void)hipEventDestroy(e);
-    if (q.copy)
-        (void)hipStreamSynchronize(q.copy); // belongs to the context's stream set, not to the loop
+    q.own.release();
+    if (q.S && ingest_stream(c))
+        (void)hipStreamSynchronize(ingest_stream(c)); // belongs to the context's stream set, not to the loop
     q = vo_ctx::Seq();
 }
 
@@ -113,38 +85,35 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
             memcpy(c->sched_key, key.k, sizeof(key.k));
         else
             c->sched_key[0] = -1; // the first full step probes
-        q.copy = ensure_copy_stream(&c->streams, sc.prep != 0, c->partitioned);
-        ok = q.copy != nullptr;
+        ok = ensure_ingest_stream(c, sc.prep != 0) != nullptr;
     }
-    ok = ok && dmalloc(&q.d_corners, (size_t)ring * S * c->fcap) == hipSuccess;
-    ok = ok && dmalloc(&q.d_ncorn, (size_t)ring * S) == hipSuccess;
-    ok = ok && hipMemset(q.d_ncorn, 0, sizeof(int) * ring * S) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q.ev_pyr, hipEventDisableTiming) == hipSuccess;
+    Owner &o = q.own;
+    ok = ok && o.device(&q.d_corners, (size_t)ring * S * c->fcap);
+    ok = ok && o.device(&q.d_ncorn, (size_t)ring * S, /*zero*/ true);
+    ok = ok && o.event(&q.ev_pyr);
     for (auto &e : q.ev_fast)
-        ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-    ok = ok && dmalloc(&q.d_quads, (size_t)ring * S) == hipSuccess;
-    ok = ok && dmalloc(&q.d_active, (size_t)VO_SEQ_INFLIGHT * S) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&q.h_active, sizeof(int) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault) == hipSuccess;
-    ok = ok && dmalloc(&q.d_ing, (size_t)VO_SEQ_INFLIGHT * S) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&q.h_ing, sizeof(SeqIngest) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault) == hipSuccess;
-    ok = ok && dmalloc(&q.d_pose, S * 16) == hipSuccess;
-    ok = ok && dmalloc(&q.d_traj, S * (size_t)max_steps * VO_SEQ_ROW) == hipSuccess;
-    ok = ok && dmalloc(&q.d_info, S * (size_t)max_steps) == hipSuccess;
-    ok = ok && dmalloc(&q.d_rows, S) == hipSuccess;
-    ok = ok && dmalloc(&q.d_rows_carry, S) == hipSuccess;
-    ok = ok && dmalloc(&q.d_nages, S) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q.ev_upload, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q.ev_detect, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q.ev_carry, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q.ev_integ, hipEventDisableTiming) == hipSuccess;
+        ok = ok && o.event(&e);
+    ok = ok && o.device(&q.d_quads, (size_t)ring * S);
+    ok = ok && o.device(&q.d_active, (size_t)VO_SEQ_INFLIGHT * S);
+    ok = ok && o.pinned(&q.h_active, sizeof(int) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
+    ok = ok && o.device(&q.d_ing, (size_t)VO_SEQ_INFLIGHT * S);
+    ok = ok && o.pinned(&q.h_ing, sizeof(SeqIngest) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
+    ok = ok && o.device(&q.d_pose, S * 16);
+    ok = ok && o.device(&q.d_traj, S * (size_t)max_steps * VO_SEQ_ROW);
+    ok = ok && o.device(&q.d_info, S * (size_t)max_steps);
+    ok = ok && o.device(&q.d_rows, S);
+    ok = ok && o.device(&q.d_rows_carry, S);
+    ok = ok && o.device(&q.d_nages, S);
+    for (hipEvent_t *e : {&q.ev_upload, &q.ev_detect, &q.ev_carry, &q.ev_integ})
+        ok = ok && o.event(e);
     for (auto &e : q.ev_slot_free)
-        ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        ok = ok && o.event(&e);
     for (auto &e : q.ev_step)
-        ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        ok = ok && o.event(&e);
     for (auto &e : q.ev_stage)
-        ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        ok = ok && o.event(&e);
     for (auto &e : q.ev_ab)
-        ok = ok && hipEventCreate(&e) == hipSuccess;
+        ok = ok && o.event(&e, /*timing*/ true);
     if (!ok) {
         seq_free(c);
         (void)select_streams(c, false); // (n_seq == 1 had moved the context onto the CU-partitioned twin: not without a loop)
@@ -314,21 +283,17 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
         const size_t img = (size_t)c->w * c->h * bpp; // (raw bytes: the ingest kernel converts)
         if (!q.h_stage || q.stage_img != img) {
             if (q.h_stage) {
-                VO_HIP_TRY(c, hipStreamSynchronize(q.copy));
-                VO_HIP_TRY(c, hipHostFree(q.h_stage));
-                q.h_stage = nullptr;
-                if (q.d_stage)
-                    VO_HIP_TRY(c, hipFree(q.d_stage));
-                q.d_stage = nullptr;
+                VO_HIP_TRY(c, hipStreamSynchronize(ingest_stream(c)));
+                VO_HIP_TRY(c, q.own.give_back(&q.h_stage));
+                VO_HIP_TRY(c, q.own.give_back(&q.d_stage));
             }
             q.stage_img = img;
-            VO_HIP_TRY(c, hipHostMalloc((void **)&q.h_stage, img * 2 * 2 * (size_t)q.S, hipHostMallocDefault));
+            if (!q.own.pinned(&q.h_stage, img * 2 * 2 * (size_t)q.S, hipHostMallocDefault))
+                return fail_hip(c, "vo_seq_push_pair: page-locked staging area", q.own.err);
             // the device twin serves the one-transfer path alone (seq_enqueue_inputs: from 32 sequences on); optional even
             // there: without it the kernel reads h_stage over PCIe
-            if (q.S >= 32 && hipMalloc((void **)&q.d_stage, img * 2 * 2 * (size_t)q.S) != hipSuccess) {
+            if (q.S >= 32 && !q.own.device(&q.d_stage, img * 2 * 2 * (size_t)q.S))
                 (void)hipGetLastError();
-                q.d_stage = nullptr;
-            }
         }
         if (q.stage_busy[g]) { // the ingest kernel of step - 2 still reads this half of the staging area
             VO_HIP_TRY(c, hipEventSynchronize(q.ev_stage[g]));
@@ -635,7 +600,7 @@ int vo_seq_step(vo_ctx *c)
     }
     // end of the step = end of its last stream: the pose stream when a frame was processed; without a processed frame
     // the step's work is the ingest + pyramids (+ FAST) -- on the prepare stream when there is one
-    hipStream_t end_stream = n_active > 0 && c->last_pose_stream ? c->last_pose_stream : c->sched.prep ? q.copy : c->stream;
+    hipStream_t end_stream = n_active > 0 && c->last_pose_stream ? c->last_pose_stream : c->sched.prep ? c->sel->prep : c->sel->stream;
     VO_HIP_TRY(c, hipEventRecord(q.ev_step[slot], end_stream));
     q.step_pending[slot] = true;
     q.step++;

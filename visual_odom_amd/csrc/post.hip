@@ -138,18 +138,19 @@ __global__ __launch_bounds__(256) void frame_gather_kernel(FrameGather g, uint8_
     const int K = g.pose_only ? 0 : g.nB[0], M = g.pose_only ? 0 : g.nA[0], cap = g.cap; // (pose_only: vo_pnp_ransac)
     const PnpResult r = g.result[0];
     const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    const FrameGatherLayout L{(size_t)cap};
     if (tid == 0) {
-        int *h = reinterpret_cast<int *>(out);
-        h[0] = M;
-        h[1] = K;
-        h[2] = g.em ? 1 : 0;
-        *reinterpret_cast<PnpResult *>(out + 16) = r;
+        *reinterpret_cast<int *>(out + L.n_circ) = M;
+        *reinterpret_cast<int *>(out + L.n_out) = K;
+        *reinterpret_cast<int *>(out + L.has_em) = g.em ? 1 : 0;
+        *reinterpret_cast<PnpResult *>(out + L.pnp) = r;
         if (g.em)
-            *reinterpret_cast<EmResult *>(out + 256) = g.em[0];
+            *reinterpret_cast<EmResult *>(out + L.em) = g.em[0];
     }
-    float2 *o2 = reinterpret_cast<float2 *>(out + VO_GATHER_HEADER);
-    float *ox = reinterpret_cast<float *>(o2 + 4 * (size_t)cap);
-    int32_t *ok = reinterpret_cast<int32_t *>(ox + 3 * (size_t)cap), *oc = ok + cap, *oi = oc + cap;
+    float2 *o2 = reinterpret_cast<float2 *>(out + L.row(0));
+    float *ox = reinterpret_cast<float *>(out + L.xyz());
+    int32_t *ok = reinterpret_cast<int32_t *>(out + L.keep_idx()), *oc = reinterpret_cast<int32_t *>(out + L.keep_idx_circ()),
+            *oi = reinterpret_cast<int32_t *>(out + L.inliers());
     for (int i = tid; i < K; i += nth) {
 #pragma unroll
         for (int row = 0; row < 4; row++)
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(256) void frame_gather_kernel(FrameGather g, uint8_
 // set of frame 0 read out of page-locked host memory (pts [n_pts] float2, then ages [n_ages] int32 at `ages_off` bytes) into the
 // DETECT stage's lists -- ages beyond n_ages read 0, the age of a freshly appended corner (feature.cpp:260) -- with the
 // frame's tracked count and its "detect again" flag.  OUT: the bucketed set and the overflow flags into page-locked host
-// memory: k, overflow at bytes 0 / 4, pts at byte 16, ages behind cap points.
+// memory, laid out by FeaturesOutLayout (vo_kernels.h).
 __global__ __launch_bounds__(256) void features_in_kernel(const uint8_t *__restrict__ src, size_t ages_off, int n_pts, int n_ages,
                                                           int detect, float2 *__restrict__ feat, int *__restrict__ fages,
                                                           int fcap, int *__restrict__ n_tracked, int *__restrict__ detect_flag)
@@ -195,12 +196,13 @@ __global__ __launch_bounds__(256) void features_out_kernel(const float2 *__restr
 {
     const int k = n[0] < cap ? n[0] : cap;
     const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    const FeaturesOutLayout L{(size_t)cap};
     if (tid == 0) {
-        reinterpret_cast<int *>(out)[0] = n[0];
-        reinterpret_cast<int *>(out)[1] = overflow[0];
+        *reinterpret_cast<int *>(out + L.count) = n[0];
+        *reinterpret_cast<int *>(out + L.overflow) = overflow[0];
     }
-    float2 *op = reinterpret_cast<float2 *>(out + 16);
-    int *oa = reinterpret_cast<int *>(op + cap);
+    float2 *op = reinterpret_cast<float2 *>(out + L.pts);
+    int *oa = reinterpret_cast<int *>(out + L.ages());
     for (int i = tid; i < k; i += nth) {
         op[i] = pts[i];
         oa[i] = ages[i];
@@ -232,11 +234,12 @@ __global__ __launch_bounds__(256) void circ_gather_kernel(CircGather g, uint8_t 
 {
     const int cap = g.cap, count = g.consistency ? g.nB[0] : g.nA[0];
     const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    const CircGatherLayout L{(size_t)cap};
     if (tid == 0)
-        reinterpret_cast<int *>(out)[0] = count;
-    float2 *o = reinterpret_cast<float2 *>(out + 16);
-    int32_t *oi = reinterpret_cast<int32_t *>(o + 5 * (size_t)cap);
-    uint8_t *os = reinterpret_cast<uint8_t *>(oi + cap);
+        *reinterpret_cast<int *>(out + L.count) = count;
+    float2 *o = reinterpret_cast<float2 *>(out + L.row(0));
+    int32_t *oi = reinterpret_cast<int32_t *>(out + L.keep_idx());
+    uint8_t *os = reinterpret_cast<uint8_t *>(oi + cap); // = out + L.status(0), in the form that keeps the kernel's instruction order
     for (int i = tid; i < count; i += nth) {
         if (!g.consistency) { // stage A rows: l0, r0, r1, l1, l0_ret
 #pragma unroll

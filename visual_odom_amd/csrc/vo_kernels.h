@@ -158,9 +158,22 @@ void launch_seq_carry(const int *active, const float2 *outB, const int *nB, cons
                       const int *ages, const int *n_bucketed, int cap, int fcap, float2 *feat, int *fages,
                       int *n_tracked, const int *overflow, int *n_rows_carry, int *n_ages, SeqFrameInfo *info,
                       int max_steps, int n_seq, hipStream_t stream);
-// Everything vo_track_frame returns for its one frame, gathered by one kernel into one host-visible buffer (layout: a
-// 512-byte header -- nA, nB, has_em at bytes 0 / 4 / 8, the PnpResult at byte 16, the EmResult at byte 256 -- then fixed
-// capacity arrays l0, r0, l1, r1 [cap] float2, xyz [cap][3] float, keep_idx, keep_idx_circ, inliers [cap] int32).
+// Everything vo_track_frame returns for its one frame, gathered by one kernel into one host-visible buffer: a header (counts,
+// the PnpResult, the EmResult), then fixed-capacity arrays.  FrameGatherLayout is THE definition of where each part lies (byte
+// offsets; frame_gather_kernel writes by it, the synchronous calls of capi_dropin.hip read by it).
+constexpr size_t VO_GATHER_HEADER = 512;
+struct FrameGatherLayout {
+    size_t cap;
+    static constexpr size_t n_circ = 0, n_out = 4, has_em = 8, pnp = 16, em = 256; // nA, nB, flag; PnpResult; EmResult
+    constexpr size_t row(int k) const { return VO_GATHER_HEADER + (size_t)k * cap * sizeof(float2); } // l0, r0, l1, r1 [cap] float2
+    constexpr size_t xyz() const { return row(4); }                                                   // [cap][3] float
+    constexpr size_t keep_idx() const { return xyz() + cap * 3 * sizeof(float); }                     // [cap] int32, like the next two
+    constexpr size_t keep_idx_circ() const { return keep_idx() + cap * sizeof(int32_t); }
+    constexpr size_t inliers() const { return keep_idx_circ() + cap * sizeof(int32_t); }
+    constexpr size_t bytes() const { return inliers() + cap * sizeof(int32_t); }
+};
+static_assert(FrameGatherLayout::pnp + sizeof(PnpResult) <= FrameGatherLayout::em, "the PnpResult lies in bytes 16 .. 256 of the header");
+static_assert(FrameGatherLayout::em + sizeof(EmResult) <= VO_GATHER_HEADER, "the EmResult lies in bytes 256 .. 512 of the header");
 struct FrameGather {
     const int *nA, *nB;
     const float2 *outB; // [4][cap]
@@ -171,12 +184,20 @@ struct FrameGather {
     int cap;
     int pose_only = 0; // no point arrays, only the PnpResult and its inliers (vo_pnp_ransac)
 };
-constexpr size_t VO_GATHER_HEADER = 512;
-inline size_t frame_gather_bytes(int cap) { return VO_GATHER_HEADER + (size_t)cap * (4 * 8 + 12 + 3 * 4); }
+inline size_t frame_gather_bytes(int cap) { return FrameGatherLayout{(size_t)cap}.bytes(); }
 void launch_frame_gather(const FrameGather &g, uint8_t *out, hipStream_t stream);
-// vo_circular_match's results in one host-visible buffer (layout: count at byte 0; from byte 16 five rows l0, r0, r1, l1, l0_ret
-// of [cap] float2, keep_idx [cap] int32, the raw LK status [4][cap] bytes): stage A (deleteUnmatchFeaturesCircle) or, with
+// vo_circular_match's results in one host-visible buffer (CircGatherLayout): stage A (deleteUnmatchFeaturesCircle) or, with
 // `consistency`, stage B (+ checkValidMatch / removeInvalidPoints) with l0_ret picked out of the raw tracks by index
+struct CircGatherLayout {
+    size_t cap;
+    static constexpr size_t count = 0;
+    constexpr size_t row(int k) const { return 16 + (size_t)k * cap * sizeof(float2); } // l0, r0, r1, l1, l0_ret [cap] float2
+    constexpr size_t keep_idx() const { return row(5); }                                // [cap] int32
+    constexpr size_t status(int hop) const { return keep_idx() + cap * sizeof(int32_t) + (size_t)hop * cap; } // raw LK status [4][cap] bytes
+    constexpr size_t bytes() const { return status(4); }
+};
+// (both gathers go to the one buffer vo_create sizes with frame_gather_bytes)
+static_assert(CircGatherLayout{1}.bytes() - 16 <= FrameGatherLayout{1}.bytes() - VO_GATHER_HEADER, "circ_gather_bytes(cap) <= frame_gather_bytes(cap)");
 struct CircGather {
     const float2 *outA; // [5][cap]
     const int32_t *idxA;
@@ -188,13 +209,22 @@ struct CircGather {
     const uint8_t *status; // [4][cap]
     int n, cap, consistency;
 };
-inline size_t circ_gather_bytes(int cap) { return 16 + (size_t)cap * (5 * 8 + 4 + 4); }
+inline size_t circ_gather_bytes(int cap) { return CircGatherLayout{(size_t)cap}.bytes(); }
 void launch_circ_gather(const CircGather &g, uint8_t *out, hipStream_t stream);
 void launch_words_in(const void *src, int n0, void *dst0, int n1, void *dst1, int *count_dst, int count, hipStream_t stream);
 void launch_words_out(const void *src, int n, void *dst, hipStream_t stream);
-// vo_detect_bucket's feature set in and out through page-locked host memory (post.hip)
-inline size_t features_stage_bytes(int fcap) { return 16 + (size_t)fcap * (sizeof(float2) + sizeof(int)); } // (in: fcap points + fcap ages; out: vo_fast_detect's corners, features_out_kernel's layout)
-inline size_t features_out_bytes(int cap) { return 16 + (size_t)cap * (sizeof(float2) + sizeof(int)); }
+// vo_detect_bucket's feature set in and out through page-locked host memory (post.hip).  OUT, features_out_kernel:
+struct FeaturesOutLayout {
+    size_t cap;
+    static constexpr size_t count = 0, overflow = 4, pts = 16; // pts [cap] float2
+    constexpr size_t ages() const { return pts + cap * sizeof(float2); } // [cap] int32
+    constexpr size_t bytes() const { return ages() + cap * sizeof(int); }
+};
+inline size_t features_out_bytes(int cap) { return FeaturesOutLayout{(size_t)cap}.bytes(); }
+// IN, features_in_kernel: fcap points, then fcap ages at features_in_ages(fcap); the same buffer takes vo_fast_detect's corners back
+// in features_out_kernel's layout, which is the larger of the two
+inline size_t features_in_ages(int fcap) { return (size_t)fcap * sizeof(float2); }
+inline size_t features_stage_bytes(int fcap) { return features_out_bytes(fcap); }
 void launch_features_in(const uint8_t *src, size_t ages_off, int n_pts, int n_ages, int detect, float2 *feat, int *fages, int fcap,
                         int *n_tracked, int *detect_flag, hipStream_t stream);
 void launch_features_out(const float2 *pts, const int *ages, const int *n, const int *overflow, int cap, uint8_t *out,
