@@ -219,8 +219,8 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     bool ok = acquire_streams(device, &c->streams);
     ok = ok && pnp_init_device(c->sel->stream) == 0;
     Owner &o = c->own;
-    for (auto &ev : c->ev_trk_free)
-        ok = ok && o.event(&ev);
+    for (Signal &g : c->trk_free)
+        ok = ok && o.signal(&g);
     ok = ok && o.event(&c->ev_t1_ready);
     // developer build: VO_SERIAL_POSE=1 enqueues the pose solve on the tracking stream (no overlap), so that a kernel trace shows
     // every kernel's stand-alone duration
@@ -276,7 +276,7 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
         if (VO_DEV_MAX_POSE_WAVES >= 4) // the slim pose chain's workspace (pnp.hip)
             ok = ok && o.device(&b.epnp_gws, B * VO_EPNP_GWS_BLOCKS * VO_EPNP_UT_DOUBLES * 64);
         ok = ok && o.event(&b.ready);
-        ok = ok && o.event(&b.done);
+        ok = ok && o.signal(&b.done);
         ok = ok && o.event(&b.tri_done);
         ok = ok && o.event(&b.em_done);
     }
@@ -846,6 +846,27 @@ PnpParams pnp_params(const vo_ctx *c, const float *K)
     return pp;
 }
 
+LkParams lk_params(const vo_ctx *c)
+{
+    LkParams lp;
+    lp.max_level = c->levels - 1;
+    int mc = c->prm.lk_max_count;
+    lp.max_count = mc < 0 ? 0 : mc > 100 ? 100 : mc;
+    double eps = c->prm.lk_epsilon;
+    eps = eps < 0. ? 0. : eps > 10. ? 10. : eps;
+    lp.epsilon = eps * eps;
+    lp.min_eig = (float)c->prm.lk_min_eig_threshold;
+    lp.full_chain = c->prm.lk_full_chain;
+    return lp;
+}
+
+// findEssentialMat's arguments in a run with vo_params.mono_rotation: focal length and principal point of projMatrl with the
+// context's em_prob / em_threshold (vo_essential_pose passes its caller's five instead)
+EmParams em_params(const vo_ctx *c)
+{
+    return EmParams{(double)c->h_P[0], (double)c->h_P[2], (double)c->h_P[6], c->prm.em_prob, c->prm.em_threshold, EM_MAX_ITERS};
+}
+
 // the context holds the t1 pair of a previous synchronous call of this size, pyramids built (vo_ctx::tf_base; stale: the call
 // that uploaded the pair failed before its pyramids were built)
 bool have_kept_pair(const vo_ctx *c, int w, int h)
@@ -1003,14 +1024,7 @@ int vo_essential_pose(vo_ctx *c, const float *pts0, const float *pts1, int n, do
     VO_HIP_TRY(c, hipMemcpyAsync(pb.nB, &n, sizeof(int), hipMemcpyHostToDevice, c->sel->stream));
     if (c->n_frames < 1)
         c->n_frames = 1;
-    EmParams ep;
-    ep.focal = focal;
-    ep.ppx = ppx;
-    ep.ppy = ppy;
-    ep.prob = prob;
-    ep.threshold = threshold;
-    ep.max_iters = EM_MAX_ITERS;
-    launch_essential(pb.outB, pb.outB + 2 * cap, 4 * cap, pb.nB, c->cap, 1, ep, c->em, pb.em_results,
+    launch_essential(pb.outB, pb.outB + 2 * cap, 4 * cap, pb.nB, c->cap, 1, EmParams{focal, ppx, ppy, prob, threshold, EM_MAX_ITERS}, c->em, pb.em_results,
                      /*crowded*/ standalone_waves(c) >= 2, c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
     int status = 0, good = 0;

@@ -384,10 +384,7 @@ int vo_track_frame(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_
     g.result = pb.results;
     g.em = mono ? pb.em_results : nullptr;
     g.cap = c->cap;
-    if (pb.pending) { // (the chain ran on other streams: `done` covers the filter and both pose chains)
-        VO_HIP_TRY(c, hipStreamWaitEvent(c->sel->stream, pb.done, 0));
-        pb.pending = false;
-    }
+    VO_HIP_TRY(c, pb.done.wait(c->sel->stream)); // (the chain ran on other streams: `done` covers the filter and both pose chains)
     launch_frame_gather(g, c->d_gather, c->sel->stream);
     VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     VO_HOST_STAMP(8);

@@ -29,6 +29,28 @@ using namespace vo;
 #define VO_EV_PER_RUN (VO_NUM_STAGES + 3)
 #define VO_SEQ_MAX_RING 3
 
+// A cross-stream dependency: an event (handed out by an Owner) and whether it has been recorded and not yet waited for.  Whoever
+// writes what the other side reads records; whoever is about to overwrite or read it waits -- once: a signal nobody recorded, or
+// that has been waited for already, costs no HIP call.  Forgetting is for after a full drain (seq_forget).
+struct Signal {
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    hipError_t record(hipStream_t s)
+    {
+        pending = true;
+        return hipEventRecord(ev, s);
+    }
+    hipError_t wait(hipStream_t s) { return take() ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; } // stream s waits, if pending
+    hipError_t wait_host() { return take() ? hipEventSynchronize(ev) : hipSuccess; }               // the calling thread waits, if pending
+    void forget() { pending = false; }
+    bool take() // clears the flag and says whether it was set
+    {
+        const bool was = pending;
+        pending = false;
+        return was;
+    }
+};
+
 // Device memory, page-locked host memory and events of ONE lifetime (a context; a configuration of the lock-step loop): handed
 // out here, recorded, and released together.  The typed pointers the kernels and getters use stay where they are -- members of
 // vo_ctx -- and own nothing.  A request that fails leaves its pointer null and the HIP error in `err`.
@@ -66,6 +88,7 @@ struct Owner {
         events.push_back(*e);
         return true;
     }
+    bool signal(Signal *s) { return event(&s->ev); }
     template <typename T>
     hipError_t give_back(T **p) // one buffer (device or host) now: a buffer that is regrown
     {
@@ -146,8 +169,7 @@ struct vo_ctx {
     // while the filter of run k still reads the other, so the tracking stream never idles behind the filter
     float2 *d_trk2[2] = {};
     uint8_t *d_status2[2] = {};
-    hipEvent_t ev_trk_free[2] = {}; // recorded after the filter has read that set (and d_pts)
-    bool trk_busy[2] = {};
+    Signal trk_free[2]; // recorded after the filter has read that set (and d_pts)
     int trk_next = 0, trk_last = 0; // set the next LK writes / set the latest LK wrote
     // The bucketed feature set VO_STAGE_DETECT produces belongs to the same set as the tracks made from it, so
     // DETECT of run k + 1 never waits for the filter of run k either.  pts_sel = -1: the current features are
@@ -172,9 +194,9 @@ struct vo_ctx {
         double *epnp_ws = nullptr;      // workspace of the four-kernel EPnP (small launches, pnp.hip)
         double *rest_ws = nullptr;      // ransac_rest_kernel's 12 x 12 matrices [min(max_frames, VO_EPNP_WS_MAX_FRAMES)][groups][156][64]
         double *epnp_gws = nullptr;     // developer build: the slim chain's 12 x 12 matrices [max_frames][VO_EPNP_GWS_BLOCKS][156][64]
-        hipEvent_t ready = nullptr, tri_done = nullptr, done = nullptr; // LK done / triangulation done / pose solve done
+        hipEvent_t ready = nullptr, tri_done = nullptr; // LK done / triangulation done
         hipEvent_t em_done = nullptr; // essential-matrix chain done (mono_rotation)
-        bool pending = false;                        // `done` has been recorded and not waited for
+        Signal done;                  // pose solve done
     } pb[2];
     int cur = 0, last = 0; // set the next run writes / set the last run wrote
     // findEssentialMat + recoverPose working set (vo_params.mono_rotation / vo_essential_pose): one copy, only
@@ -211,16 +233,35 @@ struct vo_ctx {
     struct Schedule {
         int waves = 2, streams = 1, prep = 1;
         int wide = 4; // four-kernel EPnP for launches of up to this many frames (4 or 16; acts for 5 .. 16 frames per run)
+        bool operator==(const Schedule &o) const { return waves == o.waves && streams == o.streams && prep == o.prep && wide == o.wide; }
+        bool same_pair(const Schedule &o) const { return streams == o.streams && prep == o.prep; } // the two knobs dry runs misjudge
+        vo_schedule abi() const { return vo_schedule{waves, streams, prep, wide}; }
+        static Schedule from(const vo_schedule &s)
+        {
+            Schedule r;
+            r.waves = s.pose_waves, r.streams = s.pose_streams, r.prep = s.prepare, r.wide = s.epnp_wide_frames;
+            return r;
+        }
     } sched;
     vo_schedule pin = {0, 0, -1, 0}; // 0 / 0 / -1 / 0 = probe
     long long sched_key[8] = {-1, 0, 0, 0, 0, 0, 0, 0}; // key `sched` was resolved for
     bool sched_probed = false;       // `sched` came out of a probe (here or earlier in the process), not from defaults
     bool tuning = false;             // inside a probe: run_stages must not start another one
     bool sync_call = false;          // the run being scheduled is a synchronous drop-in call (its own probe key: latency)
-    Schedule ab_list[8];             // lock-step loop: the candidates being timed over real steps (vo_seq_step): up to four nominees
-                                     // + (round 6, from 32 sequences on) every (pose_streams, prepare) pair once more with the OTHER register budget
-    long long ab_key[8] = {};
-    // what the last probe of this context measured: candidates and their steady-state ms per run (vo_get_probe_log)
+    // Lock-step loop: the comparison of schedules over REAL steps (capi_sched.hip: sched_before_step starts it, sched_after_step
+    // drives it, sched_abandon drops it).  phase 1 = timing list[0] (the dry probe's pick), 2 = timing list[1], ... (cnt
+    // candidates), cnt + 1 = decided; `left` counts down the phase's steps (VO_AB_RAMP untimed ramp steps + n timed).
+    struct Compare {
+        Schedule list[8]; // up to four nominees + (round 6, from 32 sequences on) every (pose_streams, prepare) pair once more
+                          // with the OTHER register budget
+        long long key[8] = {};
+        int phase = 0, left = 0, n = 0, cnt = 0;
+        bool extra = false;      // the twins with the other pose_waves have been appended
+        hipEvent_t ev[16] = {};  // start / end of every candidate's timed window (events of the loop's configuration: Seq::own)
+        bool running() const { return phase >= 1 && phase <= cnt; }
+    } cmp;
+    // what the last probe of this context measured: candidates and their steady-state ms per run (vo_get_probe_log; written
+    // through probe_log_find / probe_log_record, capi_sched.hip)
     int probe_n = 0;
     vo_schedule probe_cand[VO_PROBE_LOG_MAX] = {};
     float probe_ms[VO_PROBE_LOG_MAX] = {};
@@ -282,13 +323,10 @@ struct vo_ctx {
         std::vector<uint8_t> ever, gap;        // has had a pair since its reset / resumes after a pause (VO_SEQ_F_GAP)
         std::vector<int> h_rows;               // frames processed per sequence since its reset (host mirror of d_rows)
         bool broken = false;                   // a step failed after it had consumed its pairs: vo_seq_reset(-1) first
-        hipEvent_t ev_upload = nullptr, ev_carry = nullptr, ev_integ = nullptr;
-        bool integ_pending = false;
-        hipEvent_t ev_slot_free[VO_SEQ_MAX_RING] = {}; // the LK that read ring slot r as its t0 pair has finished
-        bool slot_busy[VO_SEQ_MAX_RING] = {};
-        bool carry_pending = false;
-        hipEvent_t ev_step[VO_SEQ_INFLIGHT] = {};
-        bool step_pending[VO_SEQ_INFLIGHT] = {};
+        hipEvent_t ev_upload = nullptr;
+        Signal carry, integ;                // the latest seq_carry / the latest integration has run
+        Signal slot_free[VO_SEQ_MAX_RING];  // the LK that read ring slot r as its t0 pair has finished
+        Signal step_end[VO_SEQ_INFLIGHT];   // end of the step that used this slot of the per-step tables
         // pinned staging for pageable host images: two generations of [S][2] pitched level-0 images
         uint8_t *h_stage = nullptr;
         // (round 6) the device twin of the staging area: when EVERY sequence's pair of a step is pageable, the step's half of
@@ -297,10 +335,8 @@ struct vo_ctx {
         uint8_t *d_stage = nullptr;
         int n_pageable = 0;             // pageable pairs among the pending step's n_ing
         size_t stage_img = 0;
-        hipEvent_t ev_stage[2] = {};
-        hipEvent_t ev_detect = nullptr; // (round 6) the latest step's detection has run: a PCIe ingest starts behind it
-        bool detect_pending = false;
-        bool stage_busy[2] = {};
+        Signal stage_free[2]; // the ingest kernel has read that half of the staging area
+        Signal detect;        // (round 6) the latest step's detection has run: a PCIe ingest starts behind it
         // "prepare" work of a step runs on the copy stream, off the tracking stream's critical path: ingest of the new pairs,
         // their pyramids, and FAST + non-maximum suppression of their LEFT images -- the corners the NEXT step's
         // appendNewFeatures needs (visualOdometry.cpp:95-101 detects on imageLeft_t0, i.e. on the pair that arrived one
@@ -310,20 +346,11 @@ struct vo_ctx {
         float2 *d_corners = nullptr;      // [ring][S][fcap] FAST corners of the left image in each ring slot
         int *d_ncorn = nullptr;           // [ring][S]
         hipEvent_t ev_pyr = nullptr;      // pyramids of the pending step built (prep stream)
-        hipEvent_t ev_fast[VO_SEQ_MAX_RING] = {}; // corners of ring slot r ready (prep stream)
-        bool fast_pending[VO_SEQ_MAX_RING] = {};
+        Signal fast[VO_SEQ_MAX_RING];     // corners of ring slot r ready (prep stream)
         bool have_corners[VO_SEQ_MAX_RING] = {}; // d_corners of ring slot r belongs to the pair now in that slot
         SeqIngest *h_ing = nullptr, *d_ing = nullptr; // [VO_SEQ_INFLIGHT][S] pairs pushed for a step (pinned / device)
         int n_ing = 0, n_active = 0;    // pairs pushed for / sequences active in the pending step
         bool ing_pcie = false;          // a pair of the pending step lives in host memory (launch_seq_ingest: grid size)
-        // A/B of the prepare stream over REAL steps (vo_seq_step): 1 = timing the dry probe's pick, 2 = timing its
-        // prepare-flipped twin, ... (ab_cnt candidates), ab_cnt + 1 = decided; ab_left counts down the phase's steps (VO_AB_RAMP
-        // untimed ramp steps + ab_n timed)
-        int ab_phase = 0, ab_left = 0, ab_n = 0, ab_cnt = 0;
-        bool ab_extra = false; // the twins with the other pose_waves have been appended
-        hipEvent_t ev_ab[16] = {};
-        bool ab_running() const { return ab_phase >= 1 && ab_phase <= ab_cnt; }
-
         bool begun = false, staged = false;
     } seq;
 };
@@ -352,6 +379,8 @@ inline int fail_hip(vo_ctx *ctx, const char *what, hipError_t e)
             return fail_hip(ctx, #call, e_);                                                          \
     } while (0)
 
+// the detection grid's bucket edge in pixels (vo_detect_params.bucket_size, 0 = a tenth of the image height)
+inline int bucket_size(const vo_ctx *c) { return c->dprm.bucket_size > 0 ? c->dprm.bucket_size : c->h / 10; }
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 // register budget of the pose kernels for the stand-alone calls (vo_pnp_ransac, vo_essential_pose): nothing runs beside
 // them, so the full 512 registers unless the caller pinned the other variant
@@ -419,8 +448,7 @@ inline int pts_bucket(long long pts) { return pts <= 0 ? 0 : (int)floor(2.0 * lo
     } while (0)
 
 namespace vo_capi {
-extern std::mutex g_tune_mu;
-extern std::map<TuneKey, vo_ctx::Schedule> g_tuned; // per process: a second context of the same shape starts tuned
+bool tuned_lookup(const TuneKey &key, vo_ctx::Schedule *s); // the per-process table of settled schedules (capi_sched.hip)
 int plan_levels(vo_ctx *c, int w, int h);
 bool acquire_streams(int device, StreamSet *out);
 hipStream_t ensure_ingest_stream(vo_ctx *c, bool prepare);
@@ -441,6 +469,12 @@ bool all_pinned(const vo_ctx *c);
 bool wide_knob_live(const vo_ctx *c);
 int set_sched(vo_ctx *c, const vo_ctx::Schedule &s);
 int sched_resolve(vo_ctx *c, int stages);
+int sched_before_step(vo_ctx *c, int stages, hipEvent_t *evs);
+int sched_after_step(vo_ctx *c, hipStream_t end_stream);
+void sched_abandon(vo_ctx *c);
+enum { SIG_STEP = 1, SIG_INGEST = 2, SIG_CHAIN = 4 };
+void seq_forget(vo_ctx *c, int which);
+int refuse_detect_shape(vo_ctx *c, const char *who, const char *what);
 int seq_enqueue_inputs(vo_ctx *c, bool dry);
 int seq_lookahead(vo_ctx *c, int r);
 int probe_run(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry);
@@ -448,6 +482,8 @@ int probe_candidate(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry
 int tune_schedule(vo_ctx *c, int stages, bool timed, hipEvent_t *evs, bool dry, bool latency = false, bool publish = true);
 int run_stages_auto(vo_ctx *c, int stages, bool timed, hipEvent_t *evs = nullptr, bool sync_call = false);
 PnpParams pnp_params(const vo_ctx *c, const float *K = nullptr);
+LkParams lk_params(const vo_ctx *c);
+EmParams em_params(const vo_ctx *c);
 bool have_kept_pair(const vo_ctx *c, int w, int h);
 int deliver_pose(const vo_ctx *c, const PnpResult &r, const EmResult *e, double *rvec, double *tvec, double *R, bool pnp_rotation, bool io_pose);
 int fail_overflow(vo_ctx *c, int ovf);

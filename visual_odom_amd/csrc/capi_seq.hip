@@ -18,6 +18,37 @@ void seq_free(vo_ctx *c)
     if (q.S && ingest_stream(c))
         (void)hipStreamSynchronize(ingest_stream(c)); // belongs to the context's stream set, not to the loop
     q = vo_ctx::Seq();
+    c->cmp = vo_ctx::Compare(); // (its events were the loop's)
+}
+
+// The loop's signals are forgotten -- behind sync_all only -- in three groups, by what has been invalidated: SIG_STEP the end
+// of every step (vo_seq_sync), SIG_INGEST what orders the ingest stream against the tracking stream (set_sched moves the
+// ingest to another stream), SIG_CHAIN what one step hands to the next (vo_seq_reset(-1) forgets all three).  `detect` is in
+// none: the ingest of the first step after a drain still waits for it, which costs one call and orders nothing.
+void seq_forget(vo_ctx *c, int which)
+{
+    vo_ctx::Seq &q = c->seq;
+    if (which & SIG_STEP)
+        for (Signal &g : q.step_end)
+            g.forget();
+    if (which & SIG_INGEST) {
+        for (int r = 0; r < VO_SEQ_MAX_RING; r++)
+            q.slot_free[r].forget(), q.fast[r].forget();
+        q.stage_free[0].forget(), q.stage_free[1].forget();
+    }
+    if (which & SIG_CHAIN)
+        q.carry.forget(), q.integ.forget();
+}
+
+// a step failed after it had consumed its pairs, and part of it may be running: wait for the device, then refuse everything
+// until the caller starts over -- the ring / staging slots of this step must not be rewritten under it
+static int seq_step_failed(vo_ctx *c, int rc)
+{
+    const std::string why = c->err;
+    (void)sync_all(c);
+    c->err = why;
+    c->seq.broken = true;
+    return rc;
 }
 
 } // namespace vo_capi
@@ -67,15 +98,7 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
         const TuneKey key = tune_key(c, VO_STAGE_ALL | VO_STAGE_DETECT);
         c->seq.on = false;
         vo_ctx::Schedule sc;
-        bool found = false;
-        {
-            std::lock_guard<std::mutex> lk(g_tune_mu);
-            auto it = g_tuned.find(key);
-            if (it != g_tuned.end()) {
-                sc = it->second;
-                found = true;
-            }
-        }
+        const bool found = tuned_lookup(key, &sc);
         q.on = true;
         apply_pins(c, &sc);
         q.on = false;
@@ -91,8 +114,8 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
     ok = ok && o.device(&q.d_corners, (size_t)ring * S * c->fcap);
     ok = ok && o.device(&q.d_ncorn, (size_t)ring * S, /*zero*/ true);
     ok = ok && o.event(&q.ev_pyr);
-    for (auto &e : q.ev_fast)
-        ok = ok && o.event(&e);
+    for (Signal &g : q.fast)
+        ok = ok && o.signal(&g);
     ok = ok && o.device(&q.d_quads, (size_t)ring * S);
     ok = ok && o.device(&q.d_active, (size_t)VO_SEQ_INFLIGHT * S);
     ok = ok && o.pinned(&q.h_active, sizeof(int) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
@@ -104,15 +127,15 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
     ok = ok && o.device(&q.d_rows, S);
     ok = ok && o.device(&q.d_rows_carry, S);
     ok = ok && o.device(&q.d_nages, S);
-    for (hipEvent_t *e : {&q.ev_upload, &q.ev_detect, &q.ev_carry, &q.ev_integ})
+    for (hipEvent_t *e : {&q.ev_upload, &q.detect.ev, &q.carry.ev, &q.integ.ev})
         ok = ok && o.event(e);
-    for (auto &e : q.ev_slot_free)
-        ok = ok && o.event(&e);
-    for (auto &e : q.ev_step)
-        ok = ok && o.event(&e);
-    for (auto &e : q.ev_stage)
-        ok = ok && o.event(&e);
-    for (auto &e : q.ev_ab)
+    for (Signal &g : q.slot_free)
+        ok = ok && o.signal(&g);
+    for (Signal &g : q.step_end)
+        ok = ok && o.signal(&g);
+    for (Signal &g : q.stage_free)
+        ok = ok && o.signal(&g);
+    for (auto &e : c->cmp.ev)
         ok = ok && o.event(&e, /*timing*/ true);
     if (!ok) {
         seq_free(c);
@@ -163,20 +186,12 @@ int vo_seq_reset(vo_ctx *c, int seq)
         // slot 0, event slot 0, all max_steps trajectory rows available again (a long-lived context that recycles its
         // sequences never runs out of steps)
         q.step = 0;
-        if (q.ab_running())
-            q.ab_phase = 0; // an unfinished comparison is abandoned: the dry probe's pick stays
+        sched_abandon(c); // (the dry probe's pick stays)
         q.begun = q.staged = q.broken = false;
         q.n_ing = 0;
-        q.carry_pending = q.integ_pending = false;
-        for (auto &b : q.slot_busy)
-            b = false;
-        for (auto &b : q.fast_pending)
-            b = false;
+        seq_forget(c, SIG_STEP | SIG_INGEST | SIG_CHAIN);
         for (auto &b : q.have_corners)
             b = false;
-        for (auto &b : q.step_pending)
-            b = false;
-        q.stage_busy[0] = q.stage_busy[1] = false;
     }
     const size_t n = (size_t)(s1 - s0);
     VO_HIP_TRY(c, hipMemset(q.d_rows + s0, 0, sizeof(int) * n));
@@ -200,11 +215,7 @@ int seq_begin_step(vo_ctx *c)
     vo_ctx::Seq &q = c->seq;
     if (q.begun)
         return VO_OK;
-    const int slot = (int)(q.step % VO_SEQ_INFLIGHT);
-    if (q.step_pending[slot]) {
-        VO_HIP_TRY(c, hipEventSynchronize(q.ev_step[slot]));
-        q.step_pending[slot] = false;
-    }
+    VO_HIP_TRY(c, q.step_end[q.step % VO_SEQ_INFLIGHT].wait_host());
     // The host stays VO_SEQ_RUNAHEAD = 3 steps ahead of the device, not the VO_SEQ_INFLIGHT = 8 the per-step tables would allow
     // (late in round 6).  Found through the schedule comparison: a schedule whose pose chains cannot keep up with the tracking
     // stages fills a deep run-ahead with their backlog first and for ~50 steps reads as fast as its steps are issued (256
@@ -219,13 +230,8 @@ int seq_begin_step(vo_ctx *c)
     int ahead = q.ing_pcie ? VO_SEQ_RUNAHEAD + 1 : VO_SEQ_RUNAHEAD;
     if (dev_knob("VO_SEQ_RUNAHEAD", 0) > 0) // A/B: 1 .. 8
         ahead = dev_knob("VO_SEQ_RUNAHEAD", 0);
-    if (ahead < VO_SEQ_INFLIGHT && q.step >= ahead) {
-        const int s3 = (int)((q.step - ahead) % VO_SEQ_INFLIGHT);
-        if (q.step_pending[s3]) {
-            VO_HIP_TRY(c, hipEventSynchronize(q.ev_step[s3]));
-            q.step_pending[s3] = false;
-        }
-    }
+    if (ahead < VO_SEQ_INFLIGHT && q.step >= ahead)
+        VO_HIP_TRY(c, q.step_end[(q.step - ahead) % VO_SEQ_INFLIGHT].wait_host());
     q.n_ing = 0;
     q.begun = true;
     return VO_OK;
@@ -295,10 +301,7 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
             if (q.S >= 32 && !q.own.device(&q.d_stage, img * 2 * 2 * (size_t)q.S))
                 (void)hipGetLastError();
         }
-        if (q.stage_busy[g]) { // the ingest kernel of step - 2 still reads this half of the staging area
-            VO_HIP_TRY(c, hipEventSynchronize(q.ev_stage[g]));
-            q.stage_busy[g] = false;
-        }
+        VO_HIP_TRY(c, q.stage_free[g].wait_host()); // the ingest kernel of step - 2 still reads this half of the staging area
         uint8_t *sl = q.h_stage + (((size_t)g * q.S + seq) * 2) * img, *sr = sl + img;
         const uint8_t *srcs[2] = {(const uint8_t *)left, (const uint8_t *)right};
         uint8_t *dsts[2] = {sl, sr};
@@ -408,14 +411,6 @@ int vo_seq_push_pairs(vo_ctx *c, int n, const int32_t *seq_ids, const void *cons
     return rc;
 }
 
-// The comparison of schedules over real steps: untimed ramp steps behind a switch, and the shortest timed window.  3 and 12 until
-// late in round 6 -- with 256 sequences fed from page-locked memory (a step that is the PCIe link's) such a window measured
-// 5.14 ms per step for 2,2,0, which then sustains 5.7, against 5.17 for 1,1,0, which sustains 5.15; behind 10 ramp steps a
-// 24-step window reads 5.3-5.5 against 5.05-5.2 (gpurun_out/r6_abwin): the chains of two pose streams take that long to
-// overlap as they do sustained.
-#define VO_AB_RAMP 10
-#define VO_AB_MIN 24
-
 int vo_seq_step(vo_ctx *c)
 {
     if (!c)
@@ -428,14 +423,9 @@ int vo_seq_step(vo_ctx *c)
     if (q.broken)
         return fail(c, VO_ERR_STATE, "vo_seq_step: a previous step failed half-way; vo_seq_reset(ctx, -1) first");
     // everything that can be refused is refused BEFORE the step consumes its pairs
-    {
-        const int bs = c->dprm.bucket_size > 0 ? c->dprm.bucket_size : c->h / 10;
-        const int fpb = c->dprm.features_per_bucket;
-        if (!bucket_grid_ok(c->w, c->h, bs, fpb))
-            return fail(c, VO_ERR_ARG, "vo_seq_step: bucket grid beyond the limits of the device bucketing (vo_hip.h, vo_detect_params)");
-        if (c->w > 4096)
-            return fail(c, VO_ERR_ARG, "vo_seq_step: detection handles images up to 4096 pixels wide");
-    }
+    int rc = refuse_detect_shape(c, "vo_seq_step", "detection");
+    if (rc != VO_OK)
+        return rc;
     for (int s = 0; s < q.S; s++)
         if (q.pushed[s] && q.had_prev[s] && q.h_rows[s] >= q.max_steps) {
             // refuse the step and drop its pending pairs: the loop stays usable (trajectories can be read,
@@ -456,7 +446,7 @@ int vo_seq_step(vo_ctx *c)
                                          "vo_seq_reset(seq), or go on: the affected sequences resume as after a pause)");
         }
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    int rc = seq_begin_step(c);
+    rc = seq_begin_step(c);
     if (rc != VO_OK)
         return rc;
     const int slot = (int)(q.step % VO_SEQ_INFLIGHT);
@@ -483,13 +473,8 @@ int vo_seq_step(vo_ctx *c)
     }
     q.n_active = n_active;
     rc = seq_enqueue_inputs(c, /*dry*/ false);
-    if (rc != VO_OK) { // (the step's bookkeeping is already consumed: same treatment as a failure further down)
-        const std::string why = c->err;
-        (void)sync_all(c);
-        c->err = why;
-        q.broken = true;
-        return rc;
-    }
+    if (rc != VO_OK) // (the step's bookkeeping is already consumed: same treatment as a failure further down)
+        return seq_step_failed(c, rc);
     q.begun = false;
     c->pyr_first = r * q.S * 2;
     c->pyr_count = q.S * 2;
@@ -499,211 +484,21 @@ int vo_seq_step(vo_ctx *c)
         stages |= VO_STAGE_DETECT | VO_STAGE_LK | VO_STAGE_FILTER | VO_STAGE_TRIANGULATE | VO_STAGE_PNP;
     }
     hipEvent_t *step_evs = &c->ring[(size_t)(q.step % VO_EVENT_SLOTS) * (VO_EV_PER_RUN)];
-    rc = VO_OK;
-    if (n_active > 0 && 2 * n_active >= q.S && !c->tuning) {
-        // a step that shows the loop's real load: settle the schedule (cached / pinned / probed with dry runs of THIS
-        // step -- everything but seq_carry and seq_integrate, so the step can be repeated)
-        int need = sched_resolve(c, stages);
-        if (need < 0)
-            rc = need;
-        else if (need) {
-            rc = tune_schedule(c, stages, true, step_evs, /*dry*/ true, /*latency*/ false, /*publish*/ false);
-            bool ab_started = false;
-            if (rc == VO_OK && c->probe_n > 1) {
-                // The dry runs leave out the two kernels that advance the state, and with them some of what the streams
-                // hide: measured against every pinned schedule (tools/schedule_sweep.py) their verdict on the prepare knob was
-                // wrong by 8-25 % at 1-32 sequences, and once the pose chain got shorter (round 3) they ranked the other two
-                // knobs wrongly by 5-8 % in five of sixteen loops (two pose streams look better dry than real with one
-                // sequence, one stream with 128).  So the dry probe only NOMINATES; up to four candidates then run for a while
-                // each over REAL steps and end-of-step GPU timestamps decide.
-                auto dry_ms = [&](const vo_ctx::Schedule &x) {
-                    for (int i = 0; i < c->probe_n; i++)
-                        if (c->probe_cand[i].pose_waves == x.waves && c->probe_cand[i].pose_streams == x.streams &&
-                            c->probe_cand[i].prepare == x.prep && c->probe_cand[i].epnp_wide_frames == x.wide)
-                            return (double)c->probe_ms[i];
-                    return -1.0;
-                };
-                // The dry pick first (it stays if the loop ends before the comparison does).  Where the reach of the
-                // four-kernel EPnP is a choice (5 .. 16 sequences) the dry pick with the OTHER reach comes second: dry, the two
-                // differ by a per cent or two and the probe's choice between them is a coin flip, real steps differ by 17 %
-                // at 8 sequences (0.54 against 0.65 ms per step, gpurun r5 `S=8` runs: 14.3 k or 12.0 k frames/s by that
-                // flip).  Then one candidate per other (pose_streams, prepare) pair -- the two knobs the dry runs misjudge
-                // -- each with the register budget the dry runs prefer for it, best dry time first, until four are named.
-                int n = 0;
-                c->ab_list[n++] = c->sched;
-                if (wide_knob_live(c) && !c->pin.epnp_wide_frames) {
-                    c->ab_list[n] = c->sched;
-                    c->ab_list[n].wide = c->sched.wide == VO_EPNP_WS_MAX_FRAMES ? VO_EPNP_SPLIT_DEFAULT_FRAMES : VO_EPNP_WS_MAX_FRAMES;
-                    n++;
-                }
-                struct Pair {
-                    int st, pr, bi;
-                } pairs[4];
-                int np = 0;
-                for (int st = 1; st <= 2; st++)
-                    for (int pr = 1; pr >= 0; pr--) {
-                        if (st == c->sched.streams && pr == c->sched.prep)
-                            continue;
-                        int bi = -1;
-                        for (int i = 0; i < c->probe_n; i++)
-                            if (c->probe_cand[i].pose_streams == st && c->probe_cand[i].prepare == pr &&
-                                (bi < 0 || c->probe_ms[i] < c->probe_ms[bi]))
-                                bi = i;
-                        if (bi >= 0)
-                            pairs[np++] = Pair{st, pr, bi};
-                    }
-                std::sort(pairs, pairs + np, [&](const Pair &x, const Pair &y) { return c->probe_ms[x.bi] < c->probe_ms[y.bi]; });
-                for (int k = 0; k < np && n < 4; k++) {
-                    c->ab_list[n].waves = c->probe_cand[pairs[k].bi].pose_waves;
-                    // the reach of the four-kernel EPnP the dry probe preferred at ITS winner goes to every other nominee
-                    c->ab_list[n].wide = c->sched.wide;
-                    c->ab_list[n].streams = pairs[k].st;
-                    c->ab_list[n].prep = pairs[k].pr;
-                    n++;
-                }
-                if (n > 1) {
-                    double ms = dry_ms(c->sched);
-                    ms = ms > 0.02 ? ms : 0.02;
-                    q.ab_n = (int)ceil(25.0 / ms);
-                    q.ab_n = q.ab_n < VO_AB_MIN ? VO_AB_MIN : q.ab_n > 48 ? 48 : q.ab_n;
-                    q.ab_cnt = n;
-                    q.ab_extra = false;
-                    q.ab_phase = 1;
-                    q.ab_left = VO_AB_RAMP + q.ab_n;
-                    memcpy(c->ab_key, c->sched_key, sizeof(c->ab_key));
-                    c->sched_probed = false; // "in progress" (vo_get_schedule reports 2)
-                    ab_started = true;
-                }
-            }
-            if (rc == VO_OK && !ab_started) { // nothing to compare over real steps: the probe's pick is the settled schedule
-                TuneKey key;
-                memcpy(key.k, c->sched_key, sizeof(key.k));
-                std::lock_guard<std::mutex> lk(g_tune_mu);
-                g_tuned[key] = c->sched;
-            }
-        }
-    }
+    rc = sched_before_step(c, stages, step_evs); // settles the schedule, or starts to (capi_sched.hip)
     if (rc == VO_OK)
         rc = run_stages(c, stages, true, step_evs);
     if (rc == VO_OK && !c->sched.prep)
         q.have_corners[r] = false; // the pair now in slot r has no look-ahead corners
     if (rc == VO_OK && c->sched.prep)
         rc = seq_lookahead(c, r);
-    if (rc != VO_OK) {
-        // the step has consumed its pairs and part of it may be running: wait for the device, then refuse everything
-        // until the caller starts over -- the ring / staging slots of this step must not be rewritten under it
-        const std::string why = c->err;
-        (void)sync_all(c);
-        c->err = why;
-        q.broken = true;
-        return rc;
-    }
+    if (rc != VO_OK)
+        return seq_step_failed(c, rc);
     // end of the step = end of its last stream: the pose stream when a frame was processed; without a processed frame
     // the step's work is the ingest + pyramids (+ FAST) -- on the prepare stream when there is one
     hipStream_t end_stream = n_active > 0 && c->last_pose_stream ? c->last_pose_stream : c->sched.prep ? c->sel->prep : c->sel->stream;
-    VO_HIP_TRY(c, hipEventRecord(q.ev_step[slot], end_stream));
-    q.step_pending[slot] = true;
+    VO_HIP_TRY(c, q.step_end[slot].record(end_stream));
     q.step++;
-    if (q.ab_running() && n_active > 0 && 2 * n_active >= q.S) {
-        const int ph = q.ab_phase - 1;
-        q.ab_left--;
-        if (q.ab_left == q.ab_n) { // ramp over: the clock starts at the end of this step
-            VO_HIP_TRY(c, hipEventRecord(q.ev_ab[2 * ph], end_stream));
-        } else if (q.ab_left == 0) {
-            VO_HIP_TRY(c, hipEventRecord(q.ev_ab[2 * ph + 1], end_stream));
-            if (q.ab_phase < q.ab_cnt) {
-                rc = set_sched(c, c->ab_list[q.ab_phase]); // (drains every stream first when the prepare knob changes)
-                if (rc != VO_OK)
-                    return rc;
-                q.ab_phase++;
-                q.ab_left = VO_AB_RAMP + q.ab_n;
-            } else {
-                VO_HIP_TRY(c, hipEventSynchronize(q.ev_ab[2 * ph + 1]));
-                int best = 0;
-                float t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = 0; i < q.ab_cnt; i++) {
-                    VO_HIP_TRY(c, hipEventElapsedTime(&t[i], q.ev_ab[2 * i], q.ev_ab[2 * i + 1]));
-                    if (t[i] < t[best])
-                        best = i;
-                }
-                // Round 6: every nominee ran with the register budget the DRY runs prefer for its (pose_streams, prepare) pair --
-                // and at 64 sequences of 1241 x 376 they prefer the wrong one: 2,2,1 wins the comparison at 1.42 ms per step where
-                // 1,2,1 runs 1.29 (45.2 k against 49.6 k frames/s, gpurun_out/r6_s64; the loop was bimodal by that pick).  So the
-                // winner runs once more with the other budget before anything is settled -- from 32 sequences on: below, a window
-                // of ~30 steps flatters the 256-register kernels (16 sequences: 0.76 ms per step in the window, 0.85 once the
-                // pose stream's backlog has built up; 18.7 k frames/s where the untouched pick runs 20.9 k, gpurun_out/r6_twin).
-                // ... and (later in round 6) so does the nominee of every other (pose_streams, prepare) pair, fastest pair first: with
-                // 256 sequences of 340 points fed from page-locked memory the dry runs name 2,1,0 for the pair (1, 0) as often as
-                // 1,1,0 -- it sustains 41 k frames/s where 1,1,0 sustains 49.5 k and everything with two pose streams 45 k
-                // (gpurun_out/r6_pinsched), so the pair lost the comparison without its better half having run, and the loop was
-                // bimodal by that.  (Every pair, not the best two or three: 2,1,0, 2,1,1 and 1,2,1 all measure 6.3 ms there, 0.01-0.03
-                // apart -- gpurun_out/r6_ab2, r6_ab3.  From 32 sequences on the comparison is therefore exhaustive: all eight
-                // schedules over real steps, ~34 steps each.)
-                if (!q.ab_extra && !c->pin.pose_waves && q.S >= 32) {
-                    q.ab_extra = true;
-                    int order[8], no = 0; // best nominee of every (pose_streams, prepare) pair, fastest pair first
-                    for (int i = 0; i < q.ab_cnt; i++) {
-                        int k = 0;
-                        for (; k < no; k++)
-                            if (c->ab_list[order[k]].streams == c->ab_list[i].streams && c->ab_list[order[k]].prep == c->ab_list[i].prep)
-                                break;
-                        if (k == no)
-                            order[no++] = i;
-                        else if (t[i] < t[order[k]])
-                            order[k] = i;
-                    }
-                    std::sort(order, order + no, [&](int a, int b) { return t[a] < t[b]; });
-                    const int first_new = q.ab_cnt;
-                    for (int k = 0; k < no && q.ab_cnt < 8; k++) {
-                        vo_ctx::Schedule twin = c->ab_list[order[k]];
-                        twin.waves = twin.waves == 1 ? 2 : 1;
-                        bool have = false;
-                        for (int i = 0; i < q.ab_cnt; i++)
-                            have = have || (c->ab_list[i].waves == twin.waves && c->ab_list[i].streams == twin.streams &&
-                                            c->ab_list[i].prep == twin.prep && c->ab_list[i].wide == twin.wide);
-                        if (!have)
-                            c->ab_list[q.ab_cnt++] = twin;
-                    }
-                    if (q.ab_cnt > first_new) {
-                        rc = set_sched(c, c->ab_list[first_new]);
-                        if (rc != VO_OK)
-                            return rc;
-                        q.ab_phase++;
-                        q.ab_left = VO_AB_RAMP + q.ab_n;
-                        return VO_OK;
-                    }
-                }
-                rc = set_sched(c, c->ab_list[best]);
-                if (rc != VO_OK)
-                    return rc;
-                TuneKey key;
-                memcpy(key.k, c->ab_key, sizeof(key.k));
-                {
-                    std::lock_guard<std::mutex> lk(g_tune_mu);
-                    g_tuned[key] = c->ab_list[best];
-                }
-                for (int k = 0; k < q.ab_cnt; k++) { // the log shows what was measured over real steps
-                    bool logged = false;
-                    for (int i = 0; i < c->probe_n; i++)
-                        if (c->probe_cand[i].pose_waves == c->ab_list[k].waves && c->probe_cand[i].pose_streams == c->ab_list[k].streams &&
-                            c->probe_cand[i].prepare == c->ab_list[k].prep && c->probe_cand[i].epnp_wide_frames == c->ab_list[k].wide) {
-                            c->probe_ms[i] = t[k] / q.ab_n;
-                            c->probe_real[i] = 1;
-                            logged = true;
-                        }
-                    if (!logged && c->probe_n < VO_PROBE_LOG_MAX) { // a nominee the dry probe did not run in this form (the wide reach)
-                        const int i = c->probe_n++;
-                        c->probe_cand[i] = vo_schedule{c->ab_list[k].waves, c->ab_list[k].streams, c->ab_list[k].prep, c->ab_list[k].wide};
-                        c->probe_ms[i] = t[k] / q.ab_n;
-                        c->probe_real[i] = 1;
-                    }
-                }
-                q.ab_phase = q.ab_cnt + 1;
-                c->sched_probed = true;
-            }
-        }
-    }
-    return VO_OK;
+    return sched_after_step(c, end_stream); // a comparison of schedules over real steps counts this one
 }
 
 int vo_seq_sync(vo_ctx *c)
@@ -712,8 +507,7 @@ int vo_seq_sync(vo_ctx *c)
         return VO_ERR_ARG;
     int rc = sync_all(c);
     if (rc == VO_OK)
-        for (auto &p : c->seq.step_pending)
-            p = false;
+        seq_forget(c, SIG_STEP);
     return rc;
 }
 
