@@ -10,6 +10,28 @@
 #include "../../visual_odom_amd/csrc/vo_lkmath.h"
 #include "../../visual_odom_amd/csrc/vo_p3p.h"
 #include "../../visual_odom_amd/csrc/vo_tri.h"
+#include "unit_cases.h"
+
+// the case of unit_cases.h called `name` over n records; false if there is no such case
+template <class Op>
+static bool uc_try(const char *name, const void *in, int n, void *out, int *sizes)
+{
+    if (strcmp(name, Op::name()) != 0)
+        return false;
+    if (sizes) {
+        sizes[0] = Op::IN;
+        sizes[1] = Op::OUT;
+    } else {
+        for (int i = 0; i < n; i++)
+            Op::run((const char *)in + (size_t)i * Op::IN, (char *)out + (size_t)i * Op::OUT);
+    }
+    return true;
+}
+template <class... Ops>
+static bool uc_dispatch(uc::OpList<Ops...>, const char *name, const void *in, int n, void *out, int *sizes)
+{
+    return (uc_try<Ops>(name, in, n, out, sizes) || ...);
+}
 
 extern "C" {
 void hc_epnp5(const float *xyz5, const float *uv5, const float *K, double *rvec, double *tvec)
@@ -91,6 +113,10 @@ void hc_diff_dot(const int16_t *val7, const int16_t *I7, const int16_t *ix7, int
         b1[i] = acc;
     }
 }
+// The g++ build of tests/host_check/unit_cases.h: what tests/host_check/device_check.hip computes on gfx950 (and, with
+// --host, through the host pass of hipcc) is compared with this bit for bit.  hc_case_sizes: bytes per record in / out.
+int hc_case(const char *name, const void *in, int n, void *out) { return uc_dispatch(uc::AllOps(), name, in, n, out, nullptr) ? 0 : -1; }
+int hc_case_sizes(const char *name, int *in_out2) { return uc_dispatch(uc::AllOps(), name, nullptr, 0, nullptr, in_out2) ? 0 : -1; }
 uint32_t hc_scharr4(const int *p8)
 {
     return vo::scharr4_packed(p8[0], p8[1], p8[2], p8[3], p8[4], p8[5], p8[6], p8[7]);

@@ -1,13 +1,14 @@
 """The VO_HD headers the kernels are built from (vo_linalg.h / vo_epnp.h / vo_tri.h), compiled by
 g++ (tests/host_check) and compared with the oracle: same operation order + no FMA contraction =>
 bit-identical on the CPU -- except where the CPU path calls libm: since round 4 the headers take sin / cos / acos (Rodrigues)
-from csrc/vo_math.h (IEEE operations only, so that gfx950 and this host build compute the SAME bits; the GPU suite holds the
-device to this build bit for bit), while the oracle calls glibc's like OpenCV does: both are within one ulp of the exact
+from csrc/vo_math.h (IEEE operations only, so that gfx950 and this host build compute the SAME bits;
+tests/test_gpu_device_units.py runs every routine named here on the device and holds it to this build bit for bit), while the oracle calls glibc's like OpenCV does: both are within one ulp of the exact
 value, so those outputs agree to a few ulp instead of to the bit.  This is a unit test of device code, not a product path."""
 import ctypes as C
 
 import numpy as np
 
+import device_vectors as dv
 from conftest import vp
 
 K = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1]], np.float32)
@@ -59,69 +60,31 @@ def test_rodrigues_matches_oracle_to_a_few_ulp(orc, host_check):
 # ---------------------------------------------------------------------------------------------
 # vo_lkmath.h: the packed v_perm / v_dot2 pixel arithmetic of the LK kernel against the plain
 # DESCALE formulas of OpenCV's LKTrackerInvoker (lkpyramid.cpp), incl. the extreme operands
-def _weights(rng, n):
-    a, b = rng.random(n, dtype=np.float32), rng.random(n, dtype=np.float32)
-    a[:4], b[:4] = [0, 0, 1 - 2**-20, 0.5], [0, 1 - 2**-20, 0, 0.5]
-    one = np.float32(1)
-    s = np.float32(1 << 14)
-    w00 = np.rint((one - a) * (one - b) * s).astype(np.int32)
-    w01 = np.rint(a * (one - b) * s).astype(np.int32)
-    w10 = np.rint((one - a) * b * s).astype(np.int32)
-    w11 = (1 << 14) - w00 - w01 - w10
-    return np.ascontiguousarray(np.stack([w00, w01, w10, w11], 1).astype(np.int32))
-
-
-def _descale(x, n):
-    return (x + (1 << (n - 1))) >> n
-
-
 def test_lk_bilinear_u8_exact(host_check):
-    rng = np.random.default_rng(5)
-    n = 20000
-    top = rng.integers(0, 256, (n, 8), dtype=np.uint8)
-    bot = rng.integers(0, 256, (n, 8), dtype=np.uint8)
-    top[:8], bot[:8] = 255, 255
-    top[8:16], bot[8:16] = 0, 255
-    w = _weights(rng, n)
-    w[4:8] = [[16384, 0, 0, 0], [0, 16384, 0, 0], [0, 0, 16384, 0], [0, 0, 0, 16384]]
-    # three roundings can add up to 2^14 + 1, leaving iw11 = -1 (seen on the MI355X at a = b ~ 0.006)
-    w[8:12] = [[16385, 0, 0, -1], [16189, 98, 98, -1], [1, 16383, 1, -1], [8192, 8192, 1, -1]]
+    top, bot, w = dv.bilinear_operands()   # (rows 4 .. 11: one weight 2^14, and iw11 = -1 as seen on the MI355X)
+    n = len(top)
     assert (w.sum(1) == 16384).all()
     got = np.zeros((n, 7), np.int16)
     host_check.hc_bilinear7_u8(vp(top), vp(bot), vp(w), n, vp(got))
-    t, b = top.astype(np.int64), bot.astype(np.int64)
-    ref = _descale(t[:, :7] * w[:, [0]] + t[:, 1:] * w[:, [1]] + b[:, :7] * w[:, [2]] + b[:, 1:] * w[:, [3]], 9)
+    ref = dv.bilinear_reference(top, bot, w)
     assert np.array_equal(got, ref)
     assert ref.max() == 8160 and ref[8:12].min() >= 0
 
 
 def test_lk_bilinear_deriv_exact(host_check):
-    rng = np.random.default_rng(6)
-    n = 20000
-    # true Scharr samples are in [-4080, 4080]; stored pre-multiplied by 4
-    dx = rng.integers(-4080, 4081, (2, n, 8)).astype(np.int64)
-    dy = rng.integers(-4080, 4081, (2, n, 8)).astype(np.int64)
-    dx[:, :4], dy[:, :4] = 4080, -4080
-    dx[:, 4:8], dy[:, 4:8] = -4080, 4080
-    packed = (((dx * 4) & 0xffff) | (((dy * 4) & 0xffff) << 16)).astype(np.uint32)
-    w = _weights(rng, n)
+    dx, dy, packed, w = dv.deriv_operands()   # true Scharr samples in [-4080, 4080], stored pre-multiplied by 4
+    n = len(w)
     ix, iy = np.zeros((n, 7), np.int16), np.zeros((n, 7), np.int16)
     host_check.hc_bilinear7_deriv(vp(np.ascontiguousarray(packed[0])), vp(np.ascontiguousarray(packed[1])), vp(w), n,
                                   vp(ix), vp(iy))
     for got, d in ((ix, dx), (iy, dy)):
-        ref = _descale(d[0][:, :7] * w[:, [0]] + d[0][:, 1:] * w[:, [1]] + d[1][:, :7] * w[:, [2]] +
-                       d[1][:, 1:] * w[:, [3]], 14)
+        ref = dv.deriv_reference(d, w)
         assert np.array_equal(got, ref)
 
 
 def test_lk_diff_dot_exact(host_check):
-    rng = np.random.default_rng(7)
-    n = 5000
-    val = rng.integers(0, 8161, (n, 7)).astype(np.int16)
-    I = rng.integers(0, 8161, (n, 7)).astype(np.int16)
-    ix = rng.integers(-4080, 4081, (n, 7)).astype(np.int16)
-    val[0], I[0], ix[0] = 8160, 0, 4080       # largest per-lane partial: 7 * 8160 * 4080 < 2^28
-    val[1], I[1], ix[1] = 0, 8160, 4080
+    val, I, ix = dv.diff_dot_operands()       # rows 0, 1: the largest per-lane partial, 7 * 8160 * 4080 < 2^28
+    n = len(val)
     b1 = np.zeros(n, np.int32)
     host_check.hc_diff_dot(vp(val), vp(I), vp(ix), n, vp(b1))
     ref = ((val.astype(np.int64) - I) * ix).sum(1)

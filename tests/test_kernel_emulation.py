@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import device_vectors as dv
 from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
 
 
@@ -409,29 +410,7 @@ def test_row_cooperative_svd12_is_bit_identical_to_the_one_lane_routine(kemu):
     row broadcasts) + jacobi12_finish against jacobi_svd<12, 12, false>, the routine the one-hypothesis-per-lane kernel runs:
     the sorted, normalised rows must agree BIT FOR BIT -- on M^T M of EPnP-shaped 10 x 12 matrices (rank 10: two singular values
     at rounding level), on full-rank and on exactly singular matrices (zero rows: the pseudo-random fill of lapack.cpp)."""
-    rng = np.random.default_rng(7)
-    mats = []
-    for _ in range(14):  # M^T M with M's sparsity: rows (a fu, 0, a (uc - u)) / (0, a fv, a (vc - v)) per control point
-        M = np.zeros((10, 12))
-        al = rng.normal(0.25, 0.6, (5, 4))
-        uv = rng.uniform(0, 1241, (5, 2)) * [1, 0.3]
-        for p in range(5):
-            for q in range(4):
-                M[2 * p, 3 * q] = al[p, q] * 718.856
-                M[2 * p, 3 * q + 2] = al[p, q] * (607.19 - uv[p, 0])
-                M[2 * p + 1, 3 * q + 1] = al[p, q] * 718.856
-                M[2 * p + 1, 3 * q + 2] = al[p, q] * (185.2 - uv[p, 1])
-        mats.append(M.T @ M)
-    for _ in range(4):
-        A = rng.normal(size=(12, 12))
-        mats.append(A @ A.T)
-    Z = rng.normal(size=(12, 12))
-    Z[3] = 0
-    Z[:, 3] = 0
-    Z[7] = 0
-    Z[:, 7] = 0
-    mats += [(Z + Z.T) / 2 + 12 * np.diag((np.arange(12) % 4 != 3).astype(float)), np.zeros((12, 12)), np.eye(12)]
-    mats = np.ascontiguousarray(np.array(mats), np.float64)
+    mats = dv.svd12_matrices()
     n = len(mats)
     wide, serial = np.zeros_like(mats), np.zeros_like(mats)
     dp = C.POINTER(C.c_double)
@@ -448,19 +427,7 @@ def test_wavefront_6x6_solve_is_bit_identical_to_solve_svd(kemu):
     """the Levenberg-Marquardt step of the pose refinement: (J^T J + lambda diag) x = J^T e through the SVD, its Jacobi
     sweeps run by a wavefront (15 pairs in 9 steps, V accumulated) -- against solve_svd<6, 6> bit for bit, on normal
     matrices of projection Jacobians, on an ill-conditioned and on a singular system"""
-    rng = np.random.default_rng(11)
-    As, bs = [], []
-    for _ in range(40):
-        J = rng.normal(size=(rng.integers(8, 400), 6)) * [300, 300, 300, 40, 40, 8]
-        A = J.T @ J
-        A[np.diag_indices(6)] *= 1 + 10.0 ** rng.integers(-8, 2)
-        As.append(A)
-        bs.append(J.T @ rng.normal(size=len(J)))
-    H = np.vander(np.linspace(1, 2, 6), 6)
-    As += [H.T @ H, np.diag([4.0, 3.0, 0.0, 2.0, 0.0, 1.0]), np.zeros((6, 6))]
-    bs += [np.ones(6), np.arange(6.0), np.ones(6)]
-    A = np.ascontiguousarray(np.array(As), np.float64)
-    b = np.ascontiguousarray(np.array(bs), np.float64)
+    A, b = dv.solve6_systems()
     xw, xs = np.zeros_like(b), np.zeros_like(b)
     dp = C.POINTER(C.c_double)
     kemu.ke_solve6_wave(A.ctypes.data_as(dp), b.ctypes.data_as(dp), len(A), xw.ctypes.data_as(dp), xs.ctypes.data_as(dp))
@@ -474,20 +441,7 @@ def test_four_kernel_epnp_composition_is_bit_identical_to_the_one_piece_solver(k
     three approximations from the state the workspace holds, selection -- rvec and tvec BIT FOR BIT those of epnp5_solve (the
     one-kernel form, itself bit-identical to the oracle's EPnP: test_device_math_on_host.py), on noisy, exact, far and
     near-planar 5-point sets"""
-    rng = np.random.default_rng(21)
-    K = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1]], np.float32)
-    X, U = [], []
-    for case in range(28):
-        lo, hi = ([-8, -2, 4], [8, 2, 40]) if case % 4 else ([-30, -6, 60], [30, 6, 200])
-        xyz = rng.uniform(lo, hi, (5, 3)).astype(np.float32)
-        if case % 7 == 3:
-            xyz[:, 2] = xyz[0, 2] + rng.normal(0, 0.01, 5).astype(np.float32)  # almost fronto-parallel plane
-        rv, tv = rng.normal(0, 0.02, 3), rng.normal(0, 0.5, 3)
-        uv = orc.project_points(xyz, rv, tv, K) + (rng.normal(0, 0.4, (5, 2)) if case % 3 else 0)
-        X.append(xyz)
-        U.append(uv.astype(np.float32))
-    X = np.ascontiguousarray(np.array(X, np.float32))
-    U = np.ascontiguousarray(np.array(U, np.float32))
+    X, U, K = dv.epnp_split_sets(orc)
     split, mono = np.zeros((len(X), 6)), np.zeros((len(X), 6))
     dp, fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
     kemu.ke_epnp_split(X.ctypes.data_as(fp), U.ctypes.data_as(fp), K.ctypes.data_as(fp), len(X), split.ctypes.data_as(dp),

@@ -5,6 +5,8 @@ import ctypes as C
 
 import numpy as np
 
+import device_vectors as dv
+
 
 def _run(hc, what, x):
     x = np.ascontiguousarray(x, np.float64)
@@ -18,34 +20,29 @@ def _ulps(y, ref):
 
 
 def test_cbrt_within_one_ulp(host_check):
-    rng = np.random.default_rng(1)
-    x = np.concatenate([rng.uniform(0, 10, 200000), 10 ** rng.uniform(-300, 300, 200000), [1e-310, 5e-324]])
+    x = dv.cbrt_args()
     y = _run(host_check, 0, x)
     err = _ulps(y, np.cbrt(x.astype(np.longdouble)))
     assert float(err.max()) < 1.0, float(err.max())
-    edge = _run(host_check, 0, [0.0, -1.0, np.inf, np.nan, 8.0, 27.0, 1e-300 ** 3 if False else 1e-300])
+    edge = _run(host_check, 0, dv.CBRT_EDGES)
     assert edge[0] == 0 and np.isnan(edge[1]) and np.isinf(edge[2]) and np.isnan(edge[3]) and edge[4] == 2.0 and edge[5] == 3.0
     # like pow(x, 1 / 3.) it agrees with glibc's correctly rounded cbrt on most arguments (the rest: one ulp)
     assert np.mean(y == np.cbrt(x)) > 0.9
 
 
 def test_acos_within_one_ulp(host_check):
-    rng = np.random.default_rng(2)
-    x = np.concatenate([rng.uniform(-1, 1, 400000), 1 - 10 ** rng.uniform(-16, 0, 50000), -1 + 10 ** rng.uniform(-16, 0, 50000),
-                        [0.0, 0.5, -0.5, 1e-20, -1e-20]])
+    x = dv.acos_args()
     y = _run(host_check, 1, x)
     err = _ulps(y, np.arccos(x.astype(np.longdouble)))
     err = err[np.isfinite(err)]
     assert float(err.max()) < 1.0, float(err.max())
-    edge = _run(host_check, 1, [1.0, -1.0, 1.0000001, -2.0, np.nan])
+    edge = _run(host_check, 1, dv.ACOS_EDGES)
     assert edge[0] == 0 and edge[1] == np.pi and np.all(np.isnan(edge[2:]))
     assert np.mean(y == np.arccos(x)) > 0.9
 
 
 def test_cos_within_one_ulp(host_check):
-    rng = np.random.default_rng(3)
-    near = np.pi / 2 * np.arange(1, 64) + rng.uniform(-1e-9, 1e-9, 63)  # next to the multiples of pi / 2 (cancellation)
-    x = np.concatenate([rng.uniform(0, 5.3, 400000), rng.uniform(-1000, 1000, 100000), near, [0.0, np.pi / 2, np.pi, 2 * np.pi / 3]])
+    x = dv.cos_args()
     y = _run(host_check, 2, x)
     err = _ulps(y, np.cos(x.astype(np.longdouble)))
     assert float(err.max()) < 1.0, float(err.max())
@@ -55,9 +52,7 @@ def test_cos_within_one_ulp(host_check):
 
 
 def test_sin_within_one_ulp(host_check):
-    rng = np.random.default_rng(4)
-    near = np.pi / 2 * np.arange(1, 64) + rng.uniform(-1e-9, 1e-9, 63)
-    x = np.concatenate([rng.uniform(-3.2, 3.2, 400000), rng.uniform(-1000, 1000, 100000), near, -near, [0.0, 1e-300, -1e-10]])
+    x = dv.sin_args()
     y = _run(host_check, 3, x)
     err = _ulps(y, np.sin(x.astype(np.longdouble)))
     err = err[np.isfinite(err)]

@@ -14,8 +14,10 @@
 //     v_dot2_i32_i16 with initial accumulator 1 << 15 leave DESCALE(S, 14) in the top 16 bits;
 //   * results are re-packed two per register (v_perm_b32) so that diff = val - I is one v_pk_sub_i16
 //     and b1 += diff*Ix, b2 += diff*Iy are one v_dot2_i32_i16 each per pixel pair.
-// Every step is exact integer arithmetic, so the result is bit-identical to the scalar formula; the
-// host build of this header (tests/host_check) proves that against the plain restatement.
+// Every step is exact integer arithmetic, so the result is bit-identical to the scalar formula.  The
+// host build of this header (tests/test_device_math_on_host.py) shows that for the `#else` text of the
+// wrappers below; tests/test_gpu_device_units.py runs the instructions themselves on gfx950, every
+// wrapper and every composite, against that host text and the plain restatement.
 #pragma once
 
 #include <stdint.h>

@@ -16,9 +16,12 @@
 //     exactly the rows they would see in the serial order -- and the next sweep's early pairs do not have to wait for this
 //     sweep's late ones either (JacobiPipe below): 12 time slots per sweep instead of 66 pairs, each slot up to six pairs
 //     on the DPP rows of two wavefronts.
-// Bit-identical to jacobi_svd<12, 12, false> by construction and by tests/test_kernel_emulation.py (CPU emulator: this
-// file against the serial routine on random, rank-deficient and degenerate matrices) and the GPU parity tests of the
-// pose solve.
+// Bit-identical to jacobi_svd<12, 12, false> by construction.  Two tests hold that: tests/test_kernel_emulation.py runs the
+// schedule (JacobiPipe, the row ownership, the barriers) on the CPU emulator, where the ordered sums go through
+// emu::exchange; tests/test_gpu_device_units.py runs the code the hardware executes -- the v_mov_b64_dpp row_newbcast +
+// v_add_f64 chains below, called directly with order-sensitive terms under a full and a partly masked EXEC, and the sweeps
+// in the launch shapes of pnp.hip -- against the serial routine on the device and against the host build, bit for bit, on
+// random, rank-deficient and degenerate matrices.
 //
 // Layout: At[144] (row i at At + 12 i) and W[12] (squared row norms) in LDS or any memory the wavefront shares; rows of
 // the matrix move between DPP rows through that memory, in program order of the one wavefront (VO_WAVE_SYNC keeps the
