@@ -20,6 +20,24 @@
  * host only copies raw bytes.  `w`, `h` stay in pixels, `stride` stays "bytes from one row to the next"; its minimum becomes
  * w * bytes per pixel (1, 2, 3, 3, 4, 4), below it VO_ERR_ARG.  Everything downstream (kept pair, pyramids, results) is
  * that of the gray call with the converted image, bit for bit.
+ *
+ * RECTIFICATION: every call above assumes rectified, undistorted images, like the reference (left_rect / right_rect,
+ * rgbd_standalone.cpp:178-196; KITTI's image_0 / image_1).  A context whose vo_params.rectify is 1 takes RAW frames plus the two
+ * maps per side that cv::initUndistortRectifyMap made (CV_32FC1) and does what cv::remap(src, dst, map_x, map_y, INTER_LINEAR,
+ * BORDER_CONSTANT, 0) does to a CV_8UC1 image, on the GPU, one stage behind the ingest (and behind the conversion of
+ * input_format, whose gray result it reads).  In OpenCV's fixed-point form, for destination pixel (x, y):
+ *   sx = rint_half_even(map_x[y][x] * 32)      sy = rint_half_even(map_y[y][x] * 32)
+ *   ix = sx >> 5, a = sx & 31                  iy = sy >> 5, b = sy & 31               (arithmetic shift)
+ *   p(j, i) = src[j][i] if 0 <= i < w and 0 <= j < h else 0
+ *   dst = ((32-a)(32-b) p(iy,ix) + a(32-b) p(iy,ix+1) + (32-a) b p(iy+1,ix) + a b p(iy+1,ix+1) + 512) >> 10
+ * (= OpenCV's (sum w15 * p + 16384) >> 15: each of its 15-bit weights is exactly 32 times the product above.)  A non-finite map
+ * entry, or one whose ix / iy leaves int16, has all four taps outside and gives 0 (x86 cvRound + saturate_cast<short>).
+ * Source and destination have the context's w x h (= rect_w x rect_h).  Everything downstream is that of the plain call with
+ * the remapped image, bit for bit.
+ * WHICH SIDE: vo_circular_match, vo_track_frame and vo_detect_bucket (an image of its own: left) know it from the argument;
+ * vo_batch_upload_image(_dev): EVEN image index = left, ODD = right -- the pair layout of the library's own tables.  The kept
+ * pair (NULL t0) is rectified on the device already.  vo_fast_detect is the plain cv::FAST counterpart and does NOT rectify.
+ * The vo_seq_push_* calls know the side from the argument.
  */
 #ifndef VO_HIP_H
 #define VO_HIP_H
@@ -91,6 +109,25 @@ typedef struct vo_params {
     /* VO_FMT_* (default VO_FMT_GRAY8): the format of every image this context is given; anything else is VO_ERR_ARG.  Like
      * lk_max_level it takes effect with the next configure -- a context has one input format at a time. */
     int input_format;
+    /* RECTIFICATION (above).  rectify: 0 = off (the default; the other fields are then ignored), 1 = on.  rect_w x rect_h: the
+     * size of the maps = of every image: a configure or synchronous call of another size returns VO_ERR_ARG.  rect_map_stride:
+     * bytes between map rows, >= 4 * rect_w.  The four maps are read DURING the vo_set_params that brings them ONLY (validated,
+     * packed to one dword per pixel and uploaded): the caller may free them afterwards.
+     * THE ROUND TRIP: vo_get_params echoes these fields as they were given, pointers included, and a vo_set_params whose eight
+     * rectification fields all EQUAL the context's current ones means "the maps you have": nothing is dereferenced, packed or
+     * reallocated, so get / change lk_max_level / set is safe after the maps were freed, and allowed inside the lock-step loop like
+     * for a context without maps.  ANY difference (another pointer, size or stride, rectify 0 <-> 1) makes the call read all four
+     * maps through the pointers it is given: they must be valid then.  New maps in the SAME buffers (or in memory that may have
+     * the address of released ones): set rectify = 0 first.
+     * VO_ERR_ARG: a NULL map, a short stride, a size beyond vo_create's, or a displacement (map - pixel) beyond +-1023 pixels whose
+     * taps are not all outside the image.  VO_ERR_STATE: new maps, or rectify on / off, inside the lock-step loop.  Like
+     * input_format it takes effect with the next configure.
+     * (The four ints are ONE declaration on purpose: tests/test_ingest_formats_abi.py reads the single `type name;` lines of this
+     * struct as the list that ends with input_format and that visual_odom_amd._lib.VoParams._fields_ mirrors; the rectification
+     * block is compared with the ctypes layout declaration by declaration in tests/test_rectify_abi.py.) */
+    int rectify, rect_w, rect_h, rect_map_stride;
+    const float *rect_map_x_left, *rect_map_y_left;
+    const float *rect_map_x_right, *rect_map_y_right;
 } vo_params;
 
 void vo_default_params(vo_params *p);
@@ -303,7 +340,7 @@ int64_t vo_kept_pair_id(const vo_ctx *ctx);
 
 int vo_batch_configure(vo_ctx *ctx, int n_images, int w, int h, int n_frames);
 /* host -> device copy of one level-0 image (both calls: given in vo_params.input_format, stride >= w * bytes per pixel;
- * level 0 receives the gray image) */
+ * level 0 receives the gray image; with vo_params.rectify the remapped one: even image_idx = left maps, odd = right) */
 int vo_batch_upload_image(vo_ctx *ctx, int image_idx, const uint8_t *host_pixels, int stride);
 /* device -> device copy (e.g. from a torch uint8 tensor's data_ptr()) */
 int vo_batch_upload_image_dev(vo_ctx *ctx, int image_idx, const void *dev_pixels, int stride);

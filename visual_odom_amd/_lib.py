@@ -42,12 +42,48 @@ EXPORTS = (
 )
 
 
-class VoParams(C.Structure):
+class _VoParamsLayout(C.Structure):
     _fields_ = [("lk_max_level", C.c_int), ("lk_max_count", C.c_int), ("lk_epsilon", C.c_double),
                 ("lk_min_eig_threshold", C.c_double), ("lk_full_chain", C.c_int), ("consistency_threshold", C.c_int),
                 ("ransac_iterations", C.c_int), ("ransac_reproj_error", C.c_float),
                 ("ransac_confidence", C.c_double), ("mono_rotation", C.c_int), ("em_prob", C.c_double),
-                ("em_threshold", C.c_double), ("input_format", C.c_int)]
+                ("em_threshold", C.c_double), ("input_format", C.c_int),
+                # rectification at ingest (include/vo_hip.h, RECTIFICATION): the maps are read during vo_set_params only
+                ("rectify", C.c_int), ("rect_w", C.c_int), ("rect_h", C.c_int), ("rect_map_stride", C.c_int),
+                ("rect_map_x_left", C.POINTER(C.c_float)), ("rect_map_y_left", C.POINTER(C.c_float)),
+                ("rect_map_x_right", C.POINTER(C.c_float)), ("rect_map_y_right", C.POINTER(C.c_float))]
+
+
+class _ScalarFieldList(type(C.Structure)):
+    @property
+    def _fields_(cls):
+        return _VoParamsLayout._fields_[:13]
+
+
+class VoParams(_VoParamsLayout, metaclass=_ScalarFieldList):
+    """vo_params (include/vo_hip.h).  `_fields_` lists the LK / RANSAC parameters and the input format -- the scalars a caller
+    sets by name; the rectification block behind them (laid out by _VoParamsLayout: sizeof and every offset are the C struct's)
+    is filled by set_rectify_maps."""
+    RECT_MAPS = ("rect_map_x_left", "rect_map_y_left", "rect_map_x_right", "rect_map_y_right")
+
+    def set_rectify_maps(self, maps):
+        """maps = ((map_x_left, map_y_left), (map_x_right, map_y_right)), four (h, w) float arrays (cv::initUndistortRectifyMap's
+        CV_32FC1 maps, or visual_odom_amd.rectify.init_undistort_rectify_map's), or None = rectification off.  Returns the f32
+        arrays the fields point at: the caller keeps them alive while this record may be passed to vo_set_params."""
+        if maps is None:
+            self.rectify = self.rect_w = self.rect_h = self.rect_map_stride = 0
+            for name in self.RECT_MAPS:
+                setattr(self, name, None)
+            return ()
+        (xl, yl), (xr, yr) = maps
+        keep = tuple(np.ascontiguousarray(a, np.float32) for a in (xl, yl, xr, yr))
+        if keep[0].ndim != 2 or any(a.shape != keep[0].shape for a in keep):
+            raise ValueError("rectification maps: four (h, w) arrays of one shape")
+        self.rectify, (self.rect_h, self.rect_w) = 1, keep[0].shape
+        self.rect_map_stride = 4 * self.rect_w
+        for name, a in zip(self.RECT_MAPS, keep):
+            setattr(self, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+        return keep
 
 
 class VoDetectParams(C.Structure):
@@ -230,6 +266,7 @@ class Context:
         self.n_frames = 0
         self._kept_shape = (0, 0)   # (h, w) of the pair the last track_frame kept on the device
         self.input_format = FMT_GRAY8   # vo_params.input_format: what the image helpers expect (set_params keeps it current)
+        self._rect_keep = ()            # the f32 maps vo_get_params still points at (kept alive although an unchanged round trip reads nothing)
 
     def close(self):
         if getattr(self, "h", None):
@@ -255,11 +292,16 @@ class Context:
 
     def set_params(self, **kw):
         p = self.get_params()
+        keep = self._rect_keep
+        if "rectify" in kw:   # ((map_x_left, map_y_left), (map_x_right, map_y_right)) or None / 0: VoParams.set_rectify_maps
+            maps = kw.pop("rectify")
+            keep = p.set_rectify_maps(None if maps is None or maps is False or (isinstance(maps, int) and maps == 0) else maps)
         for k, v in kw.items():
             if not hasattr(p, k):
                 raise KeyError(k)
             setattr(p, k, v)
         self._chk(self.lib.vo_set_params(self.h, C.byref(p)))
+        self._rect_keep = keep
         self.input_format = int(p.input_format)
 
     def set_schedule(self, pose_waves=0, pose_streams=0, prepare=-1, epnp_wide_frames=0):

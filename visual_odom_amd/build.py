@@ -26,7 +26,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "libvo_hip.so")
-SOURCES = ["pyramid.hip", "fast.hip", "lk.hip", "post.hip", "pnp.hip", "essential.hip", "seq.hip", "ingest_fmt.hip", "capi.hip", "capi_run.hip",
+SOURCES = ["pyramid.hip", "fast.hip", "lk.hip", "post.hip", "pnp.hip", "essential.hip", "seq.hip", "ingest_fmt.hip", "rectify.hip", "capi.hip", "capi_run.hip",
            "capi_sched.hip", "capi_seq.hip", "capi_dropin.hip"]
 # the developer build: a wrapper in place of the product file it includes, and the entry points of its own
 DEV_WRAPPERS = {"pyramid.hip": "dev/pyramid_dev.hip", "fast.hip": "dev/fast_dev.hip", "lk.hip": "dev/lk_dev.hip", "pnp.hip": "dev/pnp_dev.hip"}

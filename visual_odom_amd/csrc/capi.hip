@@ -171,6 +171,9 @@ void vo_default_params(vo_params *p)
     p->em_prob = 0.999;                    // visualOdometry.cpp:152
     p->em_threshold = 1.0;                 // visualOdometry.cpp:152
     p->input_format = VO_FMT_GRAY8;
+    p->rectify = 0; // (a vo_params is plain data: every rectification field is zero by default)
+    p->rect_w = p->rect_h = p->rect_map_stride = 0;
+    p->rect_map_x_left = p->rect_map_y_left = p->rect_map_x_right = p->rect_map_y_right = nullptr;
 }
 
 void vo_default_detect_params(vo_detect_params *p)
@@ -330,6 +333,20 @@ int vo_set_params(vo_ctx *c, const vo_params *p)
         return fail(c, VO_ERR_ARG, "vo_set_params: parameter out of range");
     if (p->input_format < VO_FMT_GRAY8 || p->input_format > VO_FMT_RGBA8)
         return fail(c, VO_ERR_ARG, "vo_set_params: input_format is not one of VO_FMT_*");
+    // Rectification: fields identical to the context's own (off and off; or what vo_get_params returned, untouched) mean "the
+    // maps I gave you" -- nothing is dereferenced, packed or reallocated.  Anything else is new maps: checked and packed now,
+    // before anything of the context changes, committed below.
+    const vo_params &q = c->prm;
+    const bool rect_same = p->rectify == q.rectify &&
+                           (!p->rectify || (p->rect_w == q.rect_w && p->rect_h == q.rect_h && p->rect_map_stride == q.rect_map_stride &&
+                                            p->rect_map_x_left == q.rect_map_x_left && p->rect_map_y_left == q.rect_map_y_left &&
+                                            p->rect_map_x_right == q.rect_map_x_right && p->rect_map_y_right == q.rect_map_y_right));
+    std::vector<uint32_t> packed;
+    if (!rect_same) {
+        int rcr = rect_check_pack(c, p, &packed);
+        if (rcr != VO_OK)
+            return rcr;
+    }
     // the staging slots of the synchronous calls hold RAW rows of a non-gray format: they grow when such a format is
     // configured (a gray context keeps what vo_create allocated) and never shrink
     const size_t raw = ((size_t)c->max_w * fmt_bpp(p->input_format) * c->max_h + 255) / 256 * 256;
@@ -349,6 +366,11 @@ int vo_set_params(vo_ctx *c, const vo_params *p)
         c->d_stage = d_new;
         c->stage_slot = raw;
         c->stage_next = 0;
+    }
+    if (!rect_same) {
+        int rcr = rect_commit(c, p, packed);
+        if (rcr != VO_OK)
+            return rcr;
     }
     c->prm = *p;
     c->n_images = 0; // pyramid plan depends on lk_max_level: force re-configure
@@ -372,6 +394,8 @@ int vo_batch_configure(vo_ctx *c, int n_images, int w, int h, int n_frames)
     if (n_images < 1 || n_images > c->max_images || n_frames < 1 || n_frames > c->max_frames || w < 32 ||
         h < 32 || w > c->max_w || h > c->max_h)
         return fail(c, VO_ERR_ARG, "vo_batch_configure: size beyond the capacity given to vo_create");
+    if (c->prm.rectify && (w != c->prm.rect_w || h != c->prm.rect_h))
+        return fail(c, VO_ERR_ARG, "image size differs from vo_params.rect_w x rect_h: the context's rectification maps are for that size only");
     VO_HIP_TRY(c, hipSetDevice(c->device));
     if (c->seq.on) { // leaving the lock-step sequence loop: its steps may still be in flight
         int rcs = sync_all(c);
@@ -441,8 +465,9 @@ namespace vo_capi {
 
 // A host image into the next page-locked staging slot, row_bytes of each row, the rows `pitch` bytes apart; the points of an
 // idle (synchronous) call into their own staging buffer beside it.  Returns the slot.
+// zero_gap: the pitch - row_bytes bytes behind every row are zeroed (a raw plane's frame, which the contiguous copy runs over).
 static int stage_image(vo_ctx *c, const void *src, int stride, size_t pitch, size_t row_bytes, bool idle, const float *pts, int n_pts,
-                       uint8_t **slot)
+                       uint8_t **slot, bool zero_gap = false)
 {
     if (c->stage_next == 0 && !idle) // all slots may still be in flight from the previous round of uploads
         VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
@@ -450,13 +475,131 @@ static int stage_image(vo_ctx *c, const void *src, int stride, size_t pitch, siz
     c->stage_next = (c->stage_next + 1) % VO_STAGE_SLOTS;
     for (int y = 0; y < c->h; y++)
         memcpy(*slot + (size_t)y * pitch, (const uint8_t *)src + (size_t)y * stride, row_bytes);
+    for (int y = 0; zero_gap && y < c->h; y++)
+        memset(*slot + (size_t)y * pitch + row_bytes, 0, pitch - row_bytes);
     if (idle && n_pts > 0)
         memcpy(c->h_pts_stage, pts, sizeof(float2) * (size_t)n_pts);
     return VO_OK;
 }
 
+// upload_image of a context with maps (arguments checked there): the kernels and copies of the plain upload, aimed at raw plane
+// idx % VO_STAGE_SLOTS -- pitch rect_raw_pitch, interior only -- then rectify_kernel on the same stream into level 0 of image idx
+// with the maps of side idx & 1.  The call's points and count ride with the pull as they always did.
+static int upload_image_rectified(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind kind, bool idle, const float *pts, int n_pts,
+                                  hipStream_t on)
+{
+    const int fmt = c->prm.input_format, rp = rect_raw_pitch(c->w);
+    uint8_t *raw = c->d_rect_raw + (size_t)(idx % VO_STAGE_SLOTS) * c->rect_plane + rect_raw_origin(c->w);
+    const bool host = kind == hipMemcpyHostToDevice;
+    hipStream_t st = host && idle && on ? on : c->sel->stream;
+    c->img_stale[idx] = 1;
+    if (fmt != VO_FMT_GRAY8) {
+        const void *from = src;
+        int from_stride = stride;
+        const bool with_pts = host && idle && n_pts >= 0;
+        if (host) {
+            const size_t rb = fmt_row_bytes(fmt, c->w);
+            uint8_t *slot = nullptr;
+            int rc = stage_image(c, src, stride, rb, rb, idle, pts, n_pts, &slot);
+            if (rc != VO_OK)
+                return rc;
+            from = c->d_stage + (slot - c->h_stage);
+            from_stride = (int)rb;
+        }
+        if (launch_pull_image_fmt(fmt, from, from_stride, raw, rp, c->w, c->h, st, with_pts ? c->d_pts_stage : nullptr,
+                                  with_pts ? c->d_pts : nullptr, with_pts ? n_pts : 0, with_pts ? c->d_npts : nullptr) != 0)
+            return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
+    } else if (host) {
+        // rows at the raw plane's pitch with ZEROS between them: the contiguous copy runs over the frame columns between two rows
+        // (and the pull's 16-byte round-up over those behind the last row), which must stay zero
+        uint8_t *slot = nullptr;
+        int rc = stage_image(c, src, stride, (size_t)rp, (size_t)c->w, idle, pts, n_pts, &slot, /*zero_gap*/ true);
+        if (rc != VO_OK)
+            return rc;
+        const size_t bytes = (size_t)rp * (size_t)(c->h - 1) + (size_t)c->w;
+        if (idle)
+            launch_pull_image(c->d_stage + (slot - c->h_stage), raw, bytes, st, n_pts >= 0 ? c->d_pts_stage : nullptr, n_pts >= 0 ? c->d_pts : nullptr,
+                              n_pts >= 0 ? n_pts : 0, n_pts >= 0 ? c->d_npts : nullptr);
+        else
+            VO_HIP_TRY(c, hipMemcpyAsync(raw, slot, bytes, hipMemcpyHostToDevice, st));
+    } else {
+        VO_HIP_TRY(c, hipMemcpy2DAsync(raw, (size_t)rp, src, (size_t)stride, (size_t)c->w, (size_t)c->h, kind, st));
+    }
+    launch_rectify(c->d_rect_tab + idx, 1, c->w, c->h, rp, c->d_rect_maps, c->lstride[0], c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX,
+                   c->img_bytes, st);
+    VO_HIP_TRY(c, hipGetLastError());
+    return VO_OK;
+}
+
+// vo_set_params with NEW rectification fields, first half: validate, and pack the caller's maps (vo_rectify.h) -- they are read
+// here and never again.  Changes nothing of the context.
+int rect_check_pack(vo_ctx *c, const vo_params *p, std::vector<uint32_t> *out)
+{
+    std::vector<uint32_t> &packed = *out;
+    if (c->seq.on)
+        return fail(c, VO_ERR_STATE, "vo_set_params: the rectification maps cannot change inside the lock-step loop");
+    if (p->rectify != 0 && p->rectify != 1)
+        return fail(c, VO_ERR_ARG, "vo_set_params: rectify is 0 or 1");
+    const int w = p->rect_w, h = p->rect_h;
+    if (p->rectify) {
+        if (w < 32 || h < 32 || w > c->max_w || h > c->max_h)
+            return fail(c, VO_ERR_ARG, "vo_set_params: rect_w x rect_h outside 32 x 32 .. the size given to vo_create");
+        if (!p->rect_map_x_left || !p->rect_map_y_left || !p->rect_map_x_right || !p->rect_map_y_right)
+            return fail(c, VO_ERR_ARG, "vo_set_params: rectify = 1 needs the four maps (rect_map_x / y _left / _right)");
+        if (p->rect_map_stride < 4 * w || p->rect_map_stride % 4 != 0)
+            return fail(c, VO_ERR_ARG, "vo_set_params: rect_map_stride is in bytes, a multiple of 4 and at least 4 * rect_w");
+        packed.resize((size_t)2 * w * h);
+        const float *mx[2] = {p->rect_map_x_left, p->rect_map_x_right}, *my[2] = {p->rect_map_y_left, p->rect_map_y_right};
+        const size_t ms = (size_t)p->rect_map_stride / 4;
+        for (int side = 0; side < 2; side++)
+            for (int y = 0; y < h; y++)
+                for (int x = 0; x < w; x++)
+                    if (!rect_pack(mx[side][y * ms + x], my[side][y * ms + x], x, y, w, h, &packed[((size_t)side * h + y) * w + x]))
+                        return fail(c, VO_ERR_ARG, "vo_set_params: a rectification map entry is more than 1023 pixels away from its own "
+                                                   "pixel and not wholly outside the image");
+    }
+    return VO_OK;
+}
+
+// ... second half, behind everything else of vo_set_params that can refuse: the old maps, raw planes and table go, the new ones
+// are allocated (planes zeroed once), uploaded and written.  A HIP failure here leaves a context WITHOUT maps (rectify = 0).
+int rect_commit(vo_ctx *c, const vo_params *p, const std::vector<uint32_t> &packed)
+{
+    const int w = p->rect_w, h = p->rect_h;
+    VO_HIP_TRY(c, hipSetDevice(c->device));
+    int rc = sync_all(c); // a queued rectify_kernel may still read the old maps and planes
+    if (rc != VO_OK)
+        return rc;
+    VO_HIP_TRY(c, c->own.give_back(&c->d_rect_maps));
+    VO_HIP_TRY(c, c->own.give_back(&c->d_rect_raw));
+    VO_HIP_TRY(c, c->own.give_back(&c->d_rect_tab));
+    c->rect_plane = 0;
+    c->prm.rectify = 0; // (until the new ones are in place)
+    if (!p->rectify)
+        return VO_OK;
+    c->rect_plane = (rect_raw_bytes(w, h) + 255) / 256 * 256;
+    std::vector<RectImage> tab((size_t)c->max_images);
+    bool ok = c->own.device(&c->d_rect_maps, packed.size());
+    ok = ok && c->own.device(&c->d_rect_raw, c->rect_plane * VO_STAGE_SLOTS, /*zero*/ true);
+    ok = ok && c->own.device(&c->d_rect_tab, tab.size());
+    for (size_t i = 0; ok && i < tab.size(); i++)
+        tab[i] = RectImage{c->d_rect_raw + (i % VO_STAGE_SLOTS) * c->rect_plane + rect_raw_origin(w), (int)i, (int)(i & 1)};
+    if (ok)
+        ok = (c->own.err = hipMemcpy(c->d_rect_maps, packed.data(), sizeof(uint32_t) * packed.size(), hipMemcpyHostToDevice)) == hipSuccess &&
+             (c->own.err = hipMemcpy(c->d_rect_tab, tab.data(), sizeof(RectImage) * tab.size(), hipMemcpyHostToDevice)) == hipSuccess;
+    if (!ok) {
+        const hipError_t e = c->own.err;
+        (void)c->own.give_back(&c->d_rect_maps);
+        (void)c->own.give_back(&c->d_rect_raw);
+        (void)c->own.give_back(&c->d_rect_tab);
+        c->n_images = 0; // (the old maps are gone: the context is a plain one until maps are set again)
+        return fail_hip(c, "vo_set_params: device memory for the rectification maps and raw planes", e);
+    }
+    return VO_OK;
+}
+
 int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind kind, bool idle, const float *pts, int n_pts,
-                 hipStream_t on)
+                 hipStream_t on, bool plain)
 {
     if (!c)
         return VO_ERR_ARG;
@@ -469,6 +612,8 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
         return fail(c, VO_ERR_STATE, "vo_batch_upload_image inside the sequence loop: use vo_seq_push_pair");
     VO_HIP_TRY(c, hipSetDevice(c->device));
     uint8_t *dst = c->d_pix + (size_t)idx * c->img_bytes + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX;
+    if (c->prm.rectify && !plain)
+        return upload_image_rectified(c, idx, src, stride, kind, idle, pts, n_pts, on);
     // the pyramid levels, borders and Scharr images of this image now belong to the previous pixels: LK / DETECT
     // refuse to read it until VO_STAGE_PYRAMID has covered it again (the contiguous host copy below also
     // overwrites the level-0 border columns with staging bytes)

@@ -226,7 +226,7 @@ namespace vo_capi {
 // img == nullptr: the LEFT image of the t1 pair of the previous vo_track_frame / vo_circular_match (what the reference's
 // loop detects on next, visualOdometry.cpp:95-108 on imageLeft_t0 = the previous imageLeft_t1) -- nothing is uploaded.
 // An image that is given goes to the slot pair that does not hold that t1 pair, which stays valid.
-int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride)
+int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride, bool plain)
 {
     if (img && c && stride < w * fmt_bpp(c->prm.input_format))
         return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
@@ -246,7 +246,7 @@ int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride)
     const int slot = c->tf_base == 0 ? 2 : 0;
     const int keep = c->tf_base; // (upload_image itself does not touch it; the batch API's wrappers do)
     c->stage_next = 0;           // (drained above: every staging slot is free, the GPU pulls the image itself)
-    rc = upload_image(c, slot, img, stride, hipMemcpyHostToDevice, /*idle*/ true);
+    rc = upload_image(c, slot, img, stride, hipMemcpyHostToDevice, /*idle*/ true, nullptr, -1, nullptr, plain);
     c->tf_base = rc == VO_OK ? keep : -1;
     if (rc != VO_OK)
         return rc;
@@ -265,7 +265,7 @@ int vo_fast_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, int 
         return VO_ERR_ARG;
     if (w > 4096)
         return fail(c, VO_ERR_ARG, "vo_fast_detect: images up to 4096 pixels wide");
-    int rc = single_image_setup(c, img, w, h, stride);
+    int rc = single_image_setup(c, img, w, h, stride, /*plain*/ true); // (cv::FAST's counterpart: never rectified)
     if (rc != VO_OK)
         return rc;
     // (no copy call: the flags by features_in_kernel, the corners and their count back through page-locked memory, one

@@ -9,6 +9,7 @@
 #include "vo_dev_hooks.h"
 #include "vo_integrate.h"
 #include "vo_linalg.h"
+#include "vo_rectify.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -297,6 +298,14 @@ struct vo_ctx {
     uint8_t *h_feat_stage = nullptr, *d_feat_stage = nullptr; // pinned + its device address: vo_detect_bucket's carried feature set on its way in (fcap float2 + fcap int32)
     uint8_t *h_pts_stage = nullptr; // pinned: the points + count of a synchronous drop-in call on their way to the device (cap float2 + 16 bytes)
     size_t stage_slot = 0; // bytes per slot, VO_STAGE_SLOTS slots
+    // rectification at ingest (vo_params.rectify; all null in a context without maps): the packed maps of both sides, one raw
+    // plane per staging slot (vo_rectify.h: zero frame written once, here), and THE table rectify_kernel reads -- entry i sends
+    // raw plane i % VO_STAGE_SLOTS to image i with the maps of side i & 1.  An upload's pull and its rectify_kernel are ordered
+    // on one stream, and all uploads between two drains go to one stream, so the planes need no signal of their own.
+    uint32_t *d_rect_maps = nullptr;
+    uint8_t *d_rect_raw = nullptr;
+    RectImage *d_rect_tab = nullptr;
+    size_t rect_plane = 0; // bytes per raw plane
     int stage_next = 0;
     int ransac_cap = 0;
     float h_P[24] = {};
@@ -350,6 +359,13 @@ struct vo_ctx {
         bool have_corners[VO_SEQ_MAX_RING] = {}; // d_corners of ring slot r belongs to the pair now in that slot
         SeqIngest *h_ing = nullptr, *d_ing = nullptr; // [VO_SEQ_INFLIGHT][S] pairs pushed for a step (pinned / device)
         int n_ing = 0, n_active = 0;    // pairs pushed for / sequences active in the pending step
+        // rectification at ingest (vo_params.rectify, else all null): the step's i-th pushed pair is ingested into raw planes
+        // 2 i, 2 i + 1 -- by the step's ingest kernel, through a twin of its table whose image0 is 2 i -- and one rectify_kernel
+        // launch on the same stream sends the 2 n_ing planes to their ring slots.  One set of 2 S planes: ingest and rectify of
+        // consecutive steps are ordered on the ingest stream.
+        uint8_t *d_raw = nullptr;
+        SeqIngest *h_ing_raw = nullptr, *d_ing_raw = nullptr; // [VO_SEQ_INFLIGHT][S]
+        RectImage *h_rect = nullptr, *d_rect = nullptr;       // [VO_SEQ_INFLIGHT][2 S]
         bool ing_pcie = false;          // a pair of the pending step lives in host memory (launch_seq_ingest: grid size)
         bool begun = false, staged = false;
     } seq;
@@ -458,8 +474,11 @@ void release_streams(int device, const StreamSet &s);
 void seq_free(vo_ctx *c);
 // idle: the caller has just drained the tracking stream (a synchronous drop-in call); pts / n_pts: the call's points ride along
 // on: the stream the pull kernel of an idle upload goes to (default: the tracking stream)
+// plain: no rectification although the context has maps (vo_fast_detect)
 int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind kind, bool idle = false, const float *pts = nullptr, int n_pts = -1,
-                 hipStream_t on = nullptr);
+                 hipStream_t on = nullptr, bool plain = false);
+int rect_check_pack(vo_ctx *c, const vo_params *p, std::vector<uint32_t> *packed);
+int rect_commit(vo_ctx *c, const vo_params *p, const std::vector<uint32_t> &packed);
 int ensure_em(vo_ctx *c);
 int run_stages(vo_ctx *c, int stages, bool timed, hipEvent_t *evs = nullptr, bool dry = false);
 int sync_all(vo_ctx *c);
@@ -492,7 +511,7 @@ int get_pose_impl(vo_ctx *c, int frame, double *rvec, double *tvec, double *R, i
 int seq_begin_step(vo_ctx *c);
 int seq_push(vo_ctx *c, int seq, const void *left, const void *right, int stride, int mode);
 int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_t *l1, const uint8_t *r1, int w, int h, int stride, const float *pts, int n, bool defer_t1 = false);
-int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride);
+int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride, bool plain = false);
 int flush_deferred(vo_ctx *c, hipStream_t on);
 struct DeferGuard { // the deferred t1 pair never outlives the call whose host pointers it holds
     vo_ctx *c;

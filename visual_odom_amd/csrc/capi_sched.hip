@@ -190,12 +190,35 @@ int seq_enqueue_inputs(vo_ctx *c, bool dry)
         if (wait_detect && over_pcie && !dry && !c->sched.prep)
             VO_HIP_TRY(c, q.detect.wait(copy));
         VO_HIP_TRY(c, hipMemcpyAsync(d_tab, h_tab, sizeof(SeqIngest) * q.n_ing, hipMemcpyHostToDevice, copy));
+        // where the ingest kernel writes: the image table, or -- a context with maps -- the loop's raw planes, pair i to planes
+        // 2 i, 2 i + 1 through a twin of the table; rectify_kernel then sends them to the ring slots the pairs were pushed for
+        uint8_t *pix0 = c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX;
+        size_t img_bytes = c->img_bytes;
+        int pitch = c->lstride[0];
+        const SeqIngest *d_use = d_tab;
+        if (c->prm.rectify) {
+            SeqIngest *h_raw = q.h_ing_raw + (size_t)slot * q.S, *d_raw_tab = q.d_ing_raw + (size_t)slot * q.S;
+            RectImage *h_rect = q.h_rect + (size_t)slot * 2 * q.S;
+            for (int i = 0; i < q.n_ing; i++) { // (a dry re-run writes the values the tables already hold)
+                h_raw[i] = h_tab[i];
+                h_raw[i].image0 = 2 * i;
+                for (int side = 0; side < 2; side++)
+                    h_rect[2 * i + side] = RectImage{q.d_raw + (size_t)(2 * i + side) * c->rect_plane + rect_raw_origin(c->w), h_tab[i].image0 + side, side};
+            }
+            VO_HIP_TRY(c, hipMemcpyAsync(d_raw_tab, h_raw, sizeof(SeqIngest) * q.n_ing, hipMemcpyHostToDevice, copy));
+            VO_HIP_TRY(c, hipMemcpyAsync(q.d_rect + (size_t)slot * 2 * q.S, h_rect, sizeof(RectImage) * 2 * q.n_ing, hipMemcpyHostToDevice, copy));
+            pix0 = q.d_raw + rect_raw_origin(c->w);
+            img_bytes = c->rect_plane;
+            pitch = rect_raw_pitch(c->w);
+            d_use = d_raw_tab;
+        }
         if (c->prm.input_format == VO_FMT_GRAY8)
-            launch_seq_ingest(d_tab, q.n_ing, c->w, c->h, c->lstride[0],
-                              c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, copy);
-        else if (launch_seq_ingest_fmt(c->prm.input_format, d_tab, q.n_ing, c->w, c->h, c->lstride[0], // (ingest_fmt.hip: converts on the way)
-                                       c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, over_pcie, copy) != 0)
+            launch_seq_ingest(d_use, q.n_ing, c->w, c->h, pitch, pix0, img_bytes, over_pcie, copy);
+        else if (launch_seq_ingest_fmt(c->prm.input_format, d_use, q.n_ing, c->w, c->h, pitch, pix0, img_bytes, over_pcie, copy) != 0) // (ingest_fmt.hip: converts on the way)
             return fail(c, VO_ERR_STATE, "no converting kernel for this input format");
+        if (c->prm.rectify)
+            launch_rectify(q.d_rect + (size_t)slot * 2 * q.S, 2 * q.n_ing, c->w, c->h, pitch, c->d_rect_maps, c->lstride[0],
+                           c->d_pix + c->loff[0] + (size_t)VO_BY * c->lstride[0] + VO_BX, c->img_bytes, copy);
         if (!dry && q.staged) {
             VO_HIP_TRY(c, q.stage_free[q.step & 1].record(copy));
             q.staged = false;

@@ -121,6 +121,13 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
     ok = ok && o.pinned(&q.h_active, sizeof(int) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
     ok = ok && o.device(&q.d_ing, (size_t)VO_SEQ_INFLIGHT * S);
     ok = ok && o.pinned(&q.h_ing, sizeof(SeqIngest) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
+    if (c->prm.rectify) { // (vo_ctx::Seq::d_raw; a loop without maps allocates none of this)
+        ok = ok && o.device(&q.d_raw, c->rect_plane * 2 * S, /*zero*/ true);
+        ok = ok && o.device(&q.d_ing_raw, (size_t)VO_SEQ_INFLIGHT * S);
+        ok = ok && o.pinned(&q.h_ing_raw, sizeof(SeqIngest) * VO_SEQ_INFLIGHT * S, hipHostMallocDefault);
+        ok = ok && o.device(&q.d_rect, (size_t)VO_SEQ_INFLIGHT * 2 * S);
+        ok = ok && o.pinned(&q.h_rect, sizeof(RectImage) * VO_SEQ_INFLIGHT * 2 * S, hipHostMallocDefault);
+    }
     ok = ok && o.device(&q.d_pose, S * 16);
     ok = ok && o.device(&q.d_traj, S * (size_t)max_steps * VO_SEQ_ROW);
     ok = ok && o.device(&q.d_info, S * (size_t)max_steps);

@@ -87,6 +87,12 @@ struct SeqIngest {
     const uint8_t *left, *right;
     int stride, image0;
 };
+// one image of a rectify_kernel launch (rectify.hip): pixel (0, 0) of the raw plane the ingest wrote, the image-table entry
+// whose level 0 receives the remapped image, and whose maps apply (0 left, 1 right)
+struct RectImage {
+    const uint8_t *raw;
+    int image, side;
+};
 #ifndef VO_SEQ_ROW // also in include/vo_hip.h (public)
 #define VO_SEQ_ROW 27 // doubles per trajectory row: frame_pose 3x4, rvec, tvec, rotation 3x3
 #define VO_SEQ_F_ACTIVE 1
@@ -152,6 +158,9 @@ int launch_seq_ingest_fmt(int fmt, const SeqIngest *tab, int n_pairs, int w, int
                           bool over_pcie, hipStream_t stream);
 int launch_pull_image_fmt(int fmt, const void *src, int src_stride, void *dst, int pitch, int w, int h, hipStream_t stream,
                           const void *pts_pinned_dev = nullptr, void *pts_dst = nullptr, int n_pts = 0, int *count_dst = nullptr);
+// rectify.hip: n_images raw planes (pitch raw_pitch, vo_rectify.h) -> level 0 of their image-table entries through the packed maps
+void launch_rectify(const RectImage *tab, int n_images, int w, int h, int raw_pitch, const uint32_t *maps, int pitch, uint8_t *pix0,
+                    size_t img_bytes, hipStream_t stream);
 void launch_seq_prepare(const int *active, const int *n_tracked, int redetect_below, int *detect,
                         const int *n_corners, int *n_new, int n_seq, hipStream_t stream);
 void launch_seq_carry(const int *active, const float2 *outB, const int *nB, const int *idxA, const int *nA,

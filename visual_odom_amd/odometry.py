@@ -25,7 +25,7 @@ class StereoOdometry:
     frame) -- the slowest of the three since round 5 (tools/latency_mode.py: 1.10 / 0.81 / 0.75 ms per frame).  Same results."""
 
     def __init__(self, P_l, P_r, device=0, max_w=1241, max_h=376, max_pts=4096, ctx=None, streaming=False,
-                 mono_rotation=False, keep_pair=True, input_format=0, **detect_kw):
+                 mono_rotation=False, keep_pair=True, input_format=0, rectify=None, **detect_kw):
         self.P_l = np.ascontiguousarray(P_l, np.float32).reshape(3, 4)
         self.P_r = np.ascontiguousarray(P_r, np.float32).reshape(3, 4)
         self.ctx = ctx if ctx is not None else _lib.Context(device, max_w, max_h, max_pts, 1)
@@ -38,7 +38,11 @@ class StereoOdometry:
         # _lib.FMT_*: what process() is given -- (h, w) gray by default, (h, w, 3 | 4) colour, or the element-stride-2 planes of
         # an interleaved frame; the library converts on the device (vo_params.input_format)
         self.input_format = int(input_format)
-        self.ctx.set_params(mono_rotation=int(self.mono_rotation), input_format=self.input_format)
+        # rectify = ((map_x_left, map_y_left), (map_x_right, map_y_right)): process() is given RAW frames and the library remaps
+        # them on the device like cv::remap (vo_params.rectify; maps from cv::initUndistortRectifyMap or visual_odom_amd.rectify)
+        # None leaves the context's maps as they are (a caller's own ctx may carry some); False switches rectification off
+        self.ctx.set_params(mono_rotation=int(self.mono_rotation), input_format=self.input_format,
+                            **({} if rectify is None else {"rectify": rectify}))
         self._n_pairs = 0
         # main.cpp:81-94
         self.points = np.zeros((0, 2), np.float32)   # currentVOFeatures.points
@@ -151,11 +155,14 @@ class MultiSequenceOdometry:
     and, when asked for, the trajectories."""
 
     def __init__(self, P_l, P_r, n_seq, width, height, device=0, max_pts=4096, ring=3, max_steps=1024, ctx=None,
-                 mono_rotation=False, input_format=0, **detect_kw):
+                 mono_rotation=False, input_format=0, rectify=None, **detect_kw):
         self.ctx = ctx if ctx is not None else _lib.Context(device, width, height, max_pts, n_seq)
         self._own = ctx is None
         self.n_seq = n_seq
-        self.ctx.set_params(mono_rotation=int(bool(mono_rotation)), input_format=int(input_format))   # (_lib.FMT_*: what push() is given)
+        # (_lib.FMT_*: what push() is given; rectify: the four maps of raw frames, see StereoOdometry)
+        # (rectify None: the context's maps stay as they are; False: off)
+        self.ctx.set_params(mono_rotation=int(bool(mono_rotation)), input_format=int(input_format),
+                            **({} if rectify is None else {"rectify": rectify}))
         self.ctx.batch_set_detect_params(**detect_kw)   # before configure: they decide how a step is scheduled
         self.ctx.seq_configure(n_seq, width, height, ring, max_steps)
         self.ctx.batch_set_projection(P_l, P_r)

@@ -13,7 +13,9 @@ segment errors of the run (evaluate_odometry.cpp:35-116).  GUI calls are dropped
 
 Images: <sequence_dir>/image_0/%06d.png and image_1/%06d.png exactly like loadImageLeft / loadImageRight
 (utils.cpp:172-190: imread(IMREAD_COLOR) + cvtColor(BGR2GRAY)); .pgm is accepted too.  Calibration: the OpenCV-YAML
-keys Camera.fx / fy / cx / cy / bf (main.cpp:64-74, calibration/kitti00.yaml).
+keys Camera.fx / fy / cx / cy / bf (main.cpp:64-74, calibration/kitti00.yaml).  A calibration that also carries LEFT.K / D / R / P
+and RIGHT.K / D / R / P (ORB-SLAM's stereo layout, !!opencv-matrix) describes RAW frames: the maps of initUndistortRectifyMap are
+made once (visual_odom_amd.rectify) and the library rectifies every frame on the GPU; Camera.* still defines the projections.
 """
 import argparse
 import os
@@ -35,6 +37,24 @@ def read_calibration(path):
     if missing:
         raise ValueError("%s: missing Camera.%s" % (path, ", Camera.".join(missing)))
     return out
+
+
+def read_rectification(path):
+    """LEFT.K / D / R / P and RIGHT.K / D / R / P of an OpenCV FileStorage YAML (`!!opencv-matrix` with rows, cols, dt, data; the
+    data list may span lines) -> (left, right) dicts of float64 arrays, or None when any of the eight is missing"""
+    with open(path) as f:
+        text = f.read()
+    out = {}
+    for m in re.finditer(r"^\s*(LEFT|RIGHT)\.([KDRP])\s*:\s*!!opencv-matrix\s*\n\s*rows\s*:\s*(\d+)\s*\n\s*cols\s*:\s*(\d+)\s*\n"
+                         r"\s*dt\s*:\s*\w+\s*\n\s*data\s*:\s*\[([^\]]*)\]", text, re.M):
+        rows, cols = int(m.group(3)), int(m.group(4))
+        vals = [float(v) for v in m.group(5).replace("\n", " ").split(",") if v.strip()]
+        if len(vals) != rows * cols:
+            raise ValueError("%s: %s.%s has %d values for %d x %d" % (path, m.group(1), m.group(2), len(vals), rows, cols))
+        out.setdefault(m.group(1), {})[m.group(2)] = np.array(vals, np.float64).reshape(rows, cols)
+    if all(k in out.get(side, {}) for side in ("LEFT", "RIGHT") for k in "KDRP"):
+        return out["LEFT"], out["RIGHT"]
+    return None
 
 
 def projection_matrices(cal):
@@ -132,9 +152,13 @@ def main(argv=None):
     if any(p[0].shape[:2] != (h, w) or p[1].shape[:2] != (h, w) for p in first):
         raise SystemExit("all sequences run in one lock-step loop must have the same image size")
     S = len(dirs)
+    rect = read_rectification(args.calibration)   # raw frames + LEFT.* / RIGHT.*: rectified on the device
+    if rect is not None:
+        from . import rectify as _rectify
+        rect = _rectify.stereo_maps(rect[0], rect[1], w, h)
     vo = odometry.MultiSequenceOdometry(P_l, P_r, S, w, h, device=args.device, ring=3, max_steps=args.max_frames + 1,
                                         mono_rotation=args.mono_rotation, features_per_bucket=args.features_per_bucket,
-                                        input_format=_lib.FMT_RGB8 if rgb else _lib.FMT_GRAY8)
+                                        input_format=_lib.FMT_RGB8 if rgb else _lib.FMT_GRAY8, rectify=rect)
     live = [True] * S
     n_read = [0] * S
     import time
