@@ -95,6 +95,25 @@ void circularMatching_hip(cv::Mat l0, cv::Mat r0, cv::Mat l1, cv::Mat r1, std::v
     p_l0_ret.swap(o_ret);
 }
 
+void featureTracking_hip(cv::Mat img_1, cv::Mat img_2, std::vector<cv::Point2f>& points1, std::vector<cv::Point2f>& points2,
+                         std::vector<uchar>& status)
+{
+    if (img_1.type() != CV_8UC1 || img_1.cols != img_2.cols || img_1.rows != img_2.rows || img_1.step != img_2.step)
+        throw std::runtime_error("featureTracking_hip: two 8-bit gray images of one size and one row step");
+    const int n = (int)points1.size();
+    vo_ctx* c = ctx_for(img_1.cols, img_1.rows, n);
+    std::vector<cv::Point2f> o1(n);
+    std::vector<uchar> st(n);
+    int m = 0;
+    g_last.id = 0; // (the call uses the image slots of the kept pair)
+    check(c, voflow_feature_tracking(c, img_1.data, img_2.data, img_1.cols, img_1.rows, (int)img_1.step, n ? &points1[0].x : nullptr, n,
+                                     n ? &o1[0].x : nullptr, n ? &st[0] : nullptr, /*err*/ nullptr, /*keep_idx*/ nullptr, &m));
+    points1.resize(m);
+    o1.resize(m);
+    points2.swap(o1);
+    status.swap(st);
+}
+
 void triangulate_hip(cv::Mat& Pl, cv::Mat& Pr, std::vector<cv::Point2f>& pl, std::vector<cv::Point2f>& pr, cv::Mat& points3D_t0)
 {
     if (Pl.type() != CV_32F || Pr.type() != CV_32F || Pl.rows != 3 || Pl.cols != 4 || Pr.rows != 3 || Pr.cols != 4)

@@ -5,6 +5,7 @@
 //   trackingFrame2Frame_hip   same signature as trackingFrame2Frame     visualOdometry.h:36-42 (body visualOdometry.cpp:132-193)
 //   triangulate_hip           replaces cv::triangulatePoints + cv::convertPointsFromHomogeneous   main.cpp:169-171
 //   detectAndBucket_hip       replaces the head of matchingFeatures     visualOdometry.cpp:95-108
+//   featureTracking_hip       same signature as featureTracking         feature.h:52      (body feature.cpp:64-74)
 //
 // Switch: -DUSE_HIP next to the reference's own USE_CUDA (CMakeLists.txt:5-9, visualOdometry.cpp:112-118); see
 // adapters/USE_HIP.cmake and INTEGRATION.md.  OpenCV is needed for the TYPES of the existing signatures only (cv::Mat,
@@ -24,6 +25,7 @@
 
 #include "feature.h"          // FeatureSet (feature.h:33-43), from the reference tree
 #include "vo_hip.h"           // C ABI of libvo_hip.so
+#include "vo_flow.h"          // ... and its two-image tracker
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -43,6 +45,12 @@ void triangulate_hip(cv::Mat& projMatrl, cv::Mat& projMatrr, std::vector<cv::Poi
 // replaces visualOdometry.cpp:95-108: appendNewFeatures when fewer than 2000 features are carried + bucketingFeatures
 // (bucket_size = rows / 10, one feature per bucket: the reference's literals)
 void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features);
+
+// same signature as featureTracking (feature.h:52): calcOpticalFlowPyrLK(img_1, img_2, ..., 21 x 21, 3, 30 / 0.01, 0, 0.001) +
+// deleteUnmatchFeatures.  points1 / points2 come back compacted, status keeps its length (0 also where a tracked point was
+// dropped for a negative coordinate), as the reference leaves them.  Drops the pair circularMatching_hip kept, if any.
+void featureTracking_hip(cv::Mat img_1, cv::Mat img_2, std::vector<cv::Point2f>& points1, std::vector<cv::Point2f>& points2,
+                         std::vector<uchar>& status);
 
 // OPT-IN, default off: the caller promises that the t0 pair of every circularMatching_hip call IS the t1 pair of the call
 // before it -- the reference's loop hands its frames over exactly so (main.cpp:157-158: imageLeft_t0 = imageLeft_t1 shares

@@ -40,6 +40,8 @@ EXPORTS = (
     "vo_seq_get_state", "vo_seq_get_trajectory", "vo_set_schedule", "vo_get_schedule", "vo_get_probe_log",
     "vo_export_schedule", "vo_import_schedule", "vo_kept_pair_id",
 )
+# every symbol include/vo_flow.h declares: the two-image tracker, exported by the same library beside the ABI above
+FLOW_EXPORTS = ("voflow_track", "voflow_feature_tracking", "voflow_batch_set_pairs", "voflow_batch_run", "voflow_batch_get")
 
 
 class _VoParamsLayout(C.Structure):
@@ -127,6 +129,14 @@ def load():
     lib.vo_default_detect_params.restype = None
     lib.vo_kept_pair_id.restype = C.c_int64
     lib.vo_kept_pair_id.argtypes = [C.c_void_p]
+    vp, i = C.c_void_p, C.c_int
+    lib.voflow_track.argtypes = [vp, vp, vp, i, i, i, vp, i, vp, vp, vp]
+    lib.voflow_feature_tracking.argtypes = [vp, vp, vp, i, i, i, vp, i, vp, vp, vp, vp, vp]
+    lib.voflow_batch_set_pairs.argtypes = [vp, vp, i]
+    lib.voflow_batch_run.argtypes = [vp]
+    lib.voflow_batch_get.argtypes = [vp, i, vp, vp, vp, i]
+    for name in FLOW_EXPORTS:
+        getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
 
@@ -350,6 +360,55 @@ class Context:
         return dict(l0=outs[0][:m].copy(), r0=outs[1][:m].copy(), r1=outs[2][:m].copy(),
                     l1=outs[3][:m].copy(), l0_ret=outs[4][:m].copy(), status4=st.copy(),
                     keep_idx=keep[:m].copy(), n_out=m)
+
+    # ---- two-image tracker (include/vo_flow.h) ------------------------------------------------
+    def flow_track(self, prev, nxt, pts, want_err=True):
+        """cv::calcOpticalFlowPyrLK(prev, nxt, pts, ...) with the context's LK parameters: (next [n, 2], status [n], err [n] or
+        None).  Afterwards the context holds no kept pair."""
+        imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
+        h, w = imgs[0].shape[:2]
+        self._kept_shape = (0, 0)
+        pts = _f32(pts, (-1, 2))
+        n = pts.shape[0]
+        out, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        err = np.zeros(max(n, 1), np.float32) if want_err else None
+        self._chk(self.lib.voflow_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, _p(out), _p(st), _pn(err)))
+        return out[:n], st[:n], (err[:n] if want_err else None)
+
+    def feature_tracking(self, prev, nxt, pts, want_err=True):
+        """the reference's featureTracking() (feature.cpp:64-74): calcOpticalFlowPyrLK + deleteUnmatchFeatures.  dict(points0,
+        points1: the survivors [n_out, 2]; status [n]: as the reference leaves it; err [n] or None; keep_idx [n_out]; n_out)"""
+        imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
+        h, w = imgs[0].shape[:2]
+        self._kept_shape = (0, 0)
+        pts = _f32(pts, (-1, 2))
+        n = pts.shape[0]
+        p0 = np.zeros((max(n, 1), 2), np.float32)
+        p0[:n] = pts
+        p1, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        err = np.zeros(max(n, 1), np.float32) if want_err else None
+        keep, n_out = np.zeros(max(n, 1), np.int32), C.c_int(0)
+        self._chk(self.lib.voflow_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, _p(p1), _p(st), _pn(err),
+                                                   _p(keep), C.addressof(n_out)))
+        m = n_out.value
+        return dict(points0=p0[:m].copy(), points1=p1[:m].copy(), status=st[:n], err=err[:n] if want_err else None,
+                    keep_idx=keep[:m].copy(), n_out=m)
+
+    def flow_batch_set_pairs(self, pairs):
+        """(prev, next) image-table indices of every configured frame"""
+        q = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self._chk(self.lib.voflow_batch_set_pairs(self.h, _p(q), q.shape[0]))
+
+    def flow_batch_run(self):
+        """one hop per frame over the pairs, asynchronous on the context's stream"""
+        self._chk(self.lib.voflow_batch_run(self.h))
+
+    def flow_batch_get(self, frame, n, want_err=True):
+        """(next [n, 2], status [n], err [n] or None) of a frame of the last flow_batch_run"""
+        out, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
+        err = np.zeros(max(n, 1), np.float32) if want_err else None
+        self._chk(self.lib.voflow_batch_get(self.h, frame, _p(out), _p(st), _pn(err), n))
+        return out[:n], st[:n], (err[:n] if want_err else None)
 
     def triangulate(self, P_l, P_r, pts_l, pts_r):
         P_l, P_r = _f32(P_l, (3, 4)), _f32(P_r, (3, 4))

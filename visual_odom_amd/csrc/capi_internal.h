@@ -315,6 +315,20 @@ struct vo_ctx {
     Quad *quads_cur = nullptr;     // the quad table the launches read: d_quads, or one phase of seq.d_quads
     std::vector<Quad> h_quads;     // host copy of d_quads (stale-pyramid check)
     std::vector<uint8_t> img_stale; // image re-uploaded since its pyramid was last built
+    // ---- two-image tracker (voflow_*, include/vo_flow.h, capi_flow.hip): allocated by the first such call ----
+    struct Flow {
+        bool ready = false;
+        Quad *d_pairs = nullptr;     // [max_frames] (prev, next) of voflow_batch_set_pairs as (l0, r0), then VO_FLOW_CONST_PAIRS
+        float2 *d_next = nullptr;    // [B][cap]
+        uint8_t *d_status = nullptr; // [B][cap]
+        float *d_err = nullptr;      // [B][cap]
+        float2 *d_out0 = nullptr, *d_out1 = nullptr; // [cap] survivors of deleteUnmatchFeatures (synchronous calls: one frame)
+        int32_t *d_idx = nullptr;    // [cap]
+        int *d_nout = nullptr;       // [1]
+        std::vector<Quad> h_pairs;   // host copy of the pairs (stale-pyramid check)
+        int n_pairs = 0;             // 0: no pairs set (or the table has been configured again since)
+        int cfg[4] = {0, 0, 0, 0};   // n_images, w, h, n_frames of the table the pairs were set for
+    } flow;
     // ---- lock-step sequence loop (vo_seq_*): S sequences x 1 frame per step, state carried on the device ----
     struct Seq {
         bool on = false;

@@ -27,6 +27,8 @@
 // Batches of fewer than 8 frames split each frame's feature list into contiguous parts over 8/fpg XCDs.
 // lk_hops_kernel (round 6): the same body for hops [begin, end) of the chain -- the synchronous drop-in calls on the kept pair
 // launch hop 0 while the new pair is still crossing PCIe (capi_run.hip); lk_circular_kernel is what every other launch runs.
+// lk_flow_kernel: the same body for ONE hop between an arbitrary (prev, next) pair of the image table, with the err output of
+// cv::calcOpticalFlowPyrLK -- the reference's featureTracking() (feature.cpp:64-74; voflow_*, capi_flow.hip).
 #include "vo_kernels.h"
 #include "vo_lkmath.h"
 
@@ -65,6 +67,19 @@ __device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint3
     wb = perm_b32(iw11, r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
 }
 
+// |a - b| of the two int16 lanes (v_pk_sub_i16, v_pk_max_i16): the err epilogue's residuals, |Jp - Ip| <= 8160
+__device__ __forceinline__ uint32_t pk_absdiff_i16(uint32_t a, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef short i16x2 __attribute__((ext_vector_type(2)));
+    const i16x2 d = __builtin_bit_cast(i16x2, a) - __builtin_bit_cast(i16x2, b);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(d, (i16x2)(-d)));
+#else
+    const int lo = (int16_t)(a & 0xffff) - (int16_t)(b & 0xffff), hi = (int16_t)(a >> 16) - (int16_t)(b >> 16);
+    return (uint32_t)((lo < 0 ? -lo : lo) & 0xffff) | ((uint32_t)((hi < 0 ? -hi : hi) & 0xffff) << 16);
+#endif
+}
+
 // 7 waves per SIMD = at most 72 VGPRs.  Round 1 had the bound at 6 waves and the allocator happened to land on 70
 // registers (so 7 waves were resident anyway); with the round-2 loop it took 78 under that bound -- one wave fewer per
 // SIMD, LK 11.9 -> 12.2 ms (gpurun_out/r2_04) -- so the bound now says what is meant: 71 registers, no spills.
@@ -76,13 +91,16 @@ __device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint3
 // (lk_hops_kernel, round 6, the synchronous drop-in calls only): hops hop_begin .. hop_end - 1 of the chain -- a launch that does
 // not start at hop 0 continues from what the launch before it wrote for hop_begin - 1 (position, status), with the same "this
 // feature is going to be dropped anyway" rule, so two launches [0, 1) + [1, 4) write bit for bit what one launch writes.
-template <bool SPLIT>
+// ERR = true (lk_flow_kernel): ONE hop, frame = (prev, next) = (Quad::l0, Quad::r0); trk / status are [B][cap], nothing retires
+// early, and the level-0 template stays in registers for the err epilogue: err [B][cap] = sum |J(final corner) - I| / (32 * 21 * 21)
+// of a point that ends with status 1, else 0 (err == nullptr: not computed).  Everything ERR adds is behind `if constexpr`.
+template <bool SPLIT, bool ERR>
 __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads,
                                                  const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
                                                  int n_frames, int fpg /* 1, 2, 4 or 8 */, int ppp /* features per part */,
                                                  float2 *__restrict__ trk,     // [B][4][cap]
                                                  uint8_t *__restrict__ status, // [B][4][cap]
-                                                 const LkParams prm, int hop_begin, int hop_end)
+                                                 const LkParams prm, int hop_begin, int hop_end, float *__restrict__ err = nullptr)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_jt[LK_JT_H * LK_JT_W];
 
@@ -122,7 +140,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
         prevPtY = unif(q0.y);
     }
 
-    for (int hop = SPLIT ? hop_begin : 0; hop < (SPLIT ? hop_end : 4); hop++) {
+    for (int hop = SPLIT ? hop_begin : 0; hop < (ERR ? 1 : SPLIT ? hop_end : 4); hop++) {
         // hop chain: l0 -> r0 -> r1 -> l1 -> l0
         const int pi = hop == 0 ? q.l0 : hop == 1 ? q.r0 : hop == 2 ? q.r1 : q.l1;
         const int ni = hop == 0 ? q.r0 : hop == 1 ? q.r1 : hop == 2 ? q.l1 : q.l0;
@@ -130,6 +148,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
         const PyrImage &J = imgs[ni];
         float outX = 0.f, outY = 0.f;
         int st = 1;
+        float errv = 0.f; // (ERR)
 
         for (int level = prm.max_level; level >= 0; level--) {
             const float scale = __int_as_float((127 - level) << 23); // 2^-level, exact (no divide)
@@ -173,6 +192,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // sum I * Ix is formed once per level and seeds the iteration's accumulator, so the inner loop
             // neither keeps I nor subtracts it
             uint32_t Ixp[4], Iyp[4];
+            uint32_t Ipe[ERR ? 4 : 1]; // (ERR) the template's pixels, kept for the err epilogue
             int a11 = 0, a12 = 0, a22 = 0, c1 = 0, c2 = 0;
             {
                 // Addresses as a wave-uniform base (first element of the bordered allocation, scalar registers) plus a
@@ -208,6 +228,11 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     a22 = sdot2(Iyp[m], Iyp[m], a22);
                     c1 = sdot2(Ip[m], Ixp[m], c1);
                     c2 = sdot2(Ip[m], Iyp[m], c2);
+                }
+                if constexpr (ERR) {
+#pragma unroll
+                    for (int m = 0; m < 4; m++)
+                        Ipe[m] = Ip[m];
                 }
             }
             float A11, A12, A22;
@@ -374,9 +399,56 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                 const int fx = vo_f2i(floorf(outX - halfWin)), fy = vo_f2i(floorf(outY - halfWin));
                 if (fx < -LK_WIN || fx >= jw || fy < -LK_WIN || fy >= jh)
                     st = 0;
+                if constexpr (ERR) {
+                    // err of cv::calcOpticalFlowPyrLK (lkpyramid.cpp, the block behind the iterations): the window at the corner of
+                    // the FINAL position (after a possible half step back: another cell, possibly outside the tile) against the
+                    // template, sum |Jp - Ip| over the 441 pixels / (32 * 21 * 21).  The integer sum is below 441 * 8160 < 2^24, so
+                    // rounding it once is the reference's running f32 sum bit for bit.
+                    if (st && err != nullptr) {
+                        const float ex = outX - halfWin, ey = outY - halfWin;
+                        const float fex = floorf(ex), fey = floorf(ey);
+                        const int inx = uni(fx), iny = uni(fy); // (admitted just above: inside [-21, jw) x [-21, jh))
+                        if (!have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 || iny + LK_WIN + 1 > jy0 + LK_JT_H) {
+                            jx0 = (inx - 12) & ~3;
+                            jy0 = iny - 9;
+                            jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
+                            jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
+                            __syncthreads();
+                            const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
+                            for (int c = lane; c < LK_JT_H * (LK_JT_W / 16); c += 64) {
+                                const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
+                                const LkU4 v = *(const VO_GLOBAL LkU4 *)(tb + (uint32_t)(row * jstride + 16 * col));
+                                *reinterpret_cast<uint4 *>(&s_jt[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
+                            }
+                            __syncthreads();
+                        }
+                        uint32_t Jt[7], Jb[7], Jp[4];
+                        const int off = (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off;
+                        const LkU2 t = *reinterpret_cast<const LkU2 *>(&s_jt[off]);
+                        const LkU2 u = *reinterpret_cast<const LkU2 *>(&s_jt[off + LK_JT_W]);
+                        lift7(t.lo, t.hi, Jt);
+                        lift7(u.lo, u.hi, Jb);
+                        lk_weights(ex - fex, ey - fey, wt, wb);
+                        blend7(Jt, Jb, wt, wb, Jp);
+                        uint32_t e = 0; // lane 63 duplicates lane 62's pixels: it contributes nothing
+#pragma unroll
+                        for (int m = 0; m < 4; m++)
+                            e = udot2(pk_absdiff_i16(Jp[m], Ipe[m]), 0x00010001u, e);
+                        errv = wave_sum_exact_f32(live ? (int)e : 0) / (float)(32 * LK_WIN * LK_WIN);
+                    }
+                }
             }
         }
 
+        if constexpr (ERR) {
+            if (lane == 0) {
+                trk[(size_t)frame * cap + f] = make_float2(outX, outY);
+                status[(size_t)frame * cap + f] = (uint8_t)st;
+                if (err != nullptr)
+                    err[(size_t)frame * cap + f] = st ? errv : 0.f;
+            }
+            return;
+        }
         if (lane == 0) {
             trk[((size_t)frame * 4 + hop) * cap + f] = make_float2(outX, outY);
             status[((size_t)frame * 4 + hop) * cap + f] = (uint8_t)st;
@@ -408,7 +480,7 @@ __global__ VO_LK_ATTRS void lk_circular_kernel(const PyrImage *__restrict__ imgs
                                                           uint8_t *__restrict__ status,  // [B][4][cap]
                                                           LkParams prm)
 {
-    lk_circular_body<false>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, 0, 4);
+    lk_circular_body<false, false>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, 0, 4);
 }
 
 // Hops hop_begin .. hop_end - 1 only: the synchronous drop-in calls (capi_run.hip) launch hop 0 -- which reads the t0 pair
@@ -418,10 +490,38 @@ __global__ VO_LK_ATTRS void lk_hops_kernel(const PyrImage *__restrict__ imgs, co
                                            int n_frames, int fpg, int ppp, float2 *__restrict__ trk,
                                            uint8_t *__restrict__ status, LkParams prm, int hop_begin, int hop_end)
 {
-    lk_circular_body<true>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, hop_begin, hop_end);
+    lk_circular_body<true, false>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, hop_begin, hop_end);
+}
+
+// One hop between the images (Quad::l0 -> Quad::r0) of every frame with the err output (see lk_circular_body, ERR).  The err
+// epilogue needs the template's four registers beyond the iteration loop and a second blend: under the product kernels' bound of
+// 71 registers the allocator spills inside the loop, so this kernel takes 6 waves per SIMD (profiles/flow.md).
+#ifndef VO_LK_FLOW_ATTRS
+#define VO_LK_FLOW_ATTRS __launch_bounds__(64, 6)
+#endif
+__global__ VO_LK_FLOW_ATTRS void lk_flow_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ pairs,
+                                                const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
+                                                int n_frames, int fpg, int ppp, float2 *__restrict__ next, // [B][cap]
+                                                uint8_t *__restrict__ status,                               // [B][cap]
+                                                float *__restrict__ err /* [B][cap] or null */, LkParams prm)
+{
+    lk_circular_body<false, true>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err);
 }
 
 #ifndef VO_HOST_EMUL
+void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
+                    int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+{
+    if (max_pts <= 0 || n_frames <= 0)
+        return;
+    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
+    const int parts = 8 / fpg, ppp = (max_pts + parts - 1) / parts;
+    const int groups = (n_frames + fpg - 1) / fpg;
+    dim3 grid((unsigned)(8 * groups * ppp));
+    hipLaunchKernelGGL(lk_flow_kernel, grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, fpg, ppp, d_next,
+                       d_status, d_err, prm);
+}
+
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
                         int cap, int max_pts, int n_frames, float2 *d_trk, uint8_t *d_status,
                         const LkParams &prm, hipStream_t stream)

@@ -104,6 +104,66 @@ __global__ __launch_bounds__(1024) void compact_kernel(const float2 *__restrict_
     }
 }
 
+// deleteUnmatchFeatures (feature.cpp:20-37) behind the two-image tracker (lk_flow_kernel): point i of a frame survives iff
+// status[i] != 0 and its tracked position has no negative coordinate; a tracked point that is dropped for its coordinate gets
+// status 0, as the reference rewrites it, and the status array keeps its length.  points0 / points1 are compacted together in
+// erase order (ballot prefix sums), keep_idx says where each survivor came from.  One workgroup per frame, whole wavefronts.
+__global__ __launch_bounds__(1024) void flow_compact_kernel(const float2 *__restrict__ pts0, // [B][cap]
+                                                           const float2 *__restrict__ next, // [B][cap]
+                                                           uint8_t *__restrict__ status,    // [B][cap], rewritten
+                                                           const int *__restrict__ n_pts, int cap,
+                                                           float2 *__restrict__ out0,       // [B][cap]
+                                                           float2 *__restrict__ out1,       // [B][cap]
+                                                           int32_t *__restrict__ keep_idx,  // [B][cap]
+                                                           int *__restrict__ n_out)         // [B]
+{
+    __shared__ int s_wave[16];
+    __shared__ int s_base;
+    const int frame = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int nthr = blockDim.x, nwv = nthr >> 6;
+    const int n = n_pts[frame];
+    const size_t fo = (size_t)frame * cap;
+    if (tid == 0)
+        s_base = 0;
+    __syncthreads();
+    for (int start = 0; start < n; start += nthr) {
+        const int i = start + tid;
+        bool keep = false;
+        float2 p0 = {0, 0}, p1 = {0, 0};
+        if (i < n) {
+            p0 = pts0[fo + i];
+            p1 = next[fo + i];
+            const bool tracked = status[fo + i] != 0;
+            keep = tracked && !(p1.x < 0 || p1.y < 0);
+            if (tracked && !keep)
+                status[fo + i] = 0;
+        }
+        const unsigned long long m = __ballot(keep);
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0)
+            s_wave[wv] = __popcll(m);
+        __syncthreads();
+        int off = s_base;
+        for (int w = 0; w < wv; w++)
+            off += s_wave[w];
+        if (keep) {
+            out0[fo + off + rank] = p0;
+            out1[fo + off + rank] = p1;
+            keep_idx[fo + off + rank] = i;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int sum = s_base;
+            for (int w = 0; w < nwv; w++)
+                sum += s_wave[w];
+            s_base = sum;
+        }
+        __syncthreads();
+    }
+    if (tid == 0)
+        n_out[frame] = s_base;
+}
+
 // thread per point; pl/pr are rows 0 and 1 of the stage-B arrays of each frame
 __global__ __launch_bounds__(256) void triangulate_kernel(const float *__restrict__ Pl,
                                                           const float *__restrict__ Pr,
@@ -260,6 +320,47 @@ __global__ __launch_bounds__(256) void circ_gather_kernel(CircGather g, uint8_t 
 #pragma unroll
         for (int hop = 0; hop < 4; hop++)
             os[(size_t)hop * cap + i] = g.status[(size_t)hop * cap + i];
+}
+
+// the results of a synchronous voflow_* call (see FlowGather, vo_kernels.h)
+__global__ __launch_bounds__(256) void flow_gather_kernel(FlowGather g, uint8_t *__restrict__ out)
+{
+    const int count = g.compact ? g.n_out[0] : 0;
+    const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    const FlowGatherLayout L{(size_t)g.cap};
+    if (tid == 0)
+        *reinterpret_cast<int *>(out + L.count) = count;
+    float2 *on = reinterpret_cast<float2 *>(out + L.next()), *o0 = reinterpret_cast<float2 *>(out + L.out0()),
+           *o1 = reinterpret_cast<float2 *>(out + L.out1());
+    float *oe = reinterpret_cast<float *>(out + L.err());
+    int32_t *oi = reinterpret_cast<int32_t *>(out + L.keep_idx());
+    uint8_t *os = out + L.status();
+    for (int i = tid; i < g.n; i += nth) {
+        on[i] = g.next[i];
+        os[i] = g.status[i];
+        if (g.err)
+            oe[i] = g.err[i];
+    }
+    for (int i = tid; i < count; i += nth) {
+        o0[i] = g.out0[i];
+        o1[i] = g.out1[i];
+        oi[i] = g.keep_idx[i];
+    }
+}
+
+void launch_flow_gather(const FlowGather &g, uint8_t *out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(flow_gather_kernel, dim3(8), dim3(256), 0, stream, g, out);
+}
+
+void launch_flow_compact(const float2 *pts0, const float2 *next, uint8_t *status, const int *n_pts, int cap, float2 *out0, float2 *out1,
+                         int32_t *keep_idx, int *n_out, int n_frames, hipStream_t stream)
+{
+    if (n_frames <= 0)
+        return;
+    const int threads = n_frames <= 4 ? 1024 : 256; // (as launch_compact)
+    hipLaunchKernelGGL(flow_compact_kernel, dim3(n_frames), dim3(threads), 0, stream, pts0, next, status, n_pts, cap, out0, out1,
+                       keep_idx, n_out);
 }
 
 void launch_words_in(const void *src, int n0, void *dst0, int n1, void *dst1, int *count_dst, int count, hipStream_t stream)

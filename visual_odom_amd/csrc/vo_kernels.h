@@ -136,6 +136,10 @@ void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_trk, uint8_t *d_status, const LkParams &prm, int hop_begin, int hop_end,
                     hipStream_t stream);
+// one hop per frame between the images (Quad::l0 -> Quad::r0) of its pair, with cv::calcOpticalFlowPyrLK's err (lk_flow_kernel);
+// d_next / d_status / d_err: [B][cap], d_err may be null (the err epilogue is skipped)
+void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
+                    int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,
                           int h, int threshold, int nonmax, unsigned long long *d_nmsmask,
                           int *d_rowcnt, int *d_rowoff,
@@ -241,6 +245,33 @@ void launch_features_out(const float2 *pts, const int *ages, const int *n, const
 void launch_compact(const float2 *pts_in, const float2 *trk, const uint8_t *status, const int *n_pts, int cap,
                     int threshold, float2 *outA, int *idxA, int *nA, float2 *outB, int *idxB, int *nB,
                     int n_frames, hipStream_t stream);
+// deleteUnmatchFeatures (feature.cpp:20-37) of every frame (flow_compact_kernel, post.hip): all arrays [B][cap]; status is
+// rewritten in place (a tracked point with a negative coordinate becomes 0) and stays uncompacted
+void launch_flow_compact(const float2 *pts0, const float2 *next, uint8_t *status, const int *n_pts, int cap, float2 *out0, float2 *out1,
+                         int32_t *keep_idx, int *n_out, int n_frames, hipStream_t stream);
+// the results of a synchronous voflow_* call (frame 0) in one host-visible buffer: the raw track of n points and, with `compact`,
+// the survivors of deleteUnmatchFeatures.  Goes to the buffer vo_create sizes with frame_gather_bytes.
+struct FlowGatherLayout {
+    size_t cap;
+    static constexpr size_t count = 0;
+    constexpr size_t next() const { return 16; }                                     // [cap] float2, like the next two
+    constexpr size_t out0() const { return next() + cap * sizeof(float2); }
+    constexpr size_t out1() const { return out0() + cap * sizeof(float2); }
+    constexpr size_t err() const { return out1() + cap * sizeof(float2); }           // [cap] float
+    constexpr size_t keep_idx() const { return err() + cap * sizeof(float); }        // [cap] int32
+    constexpr size_t status() const { return keep_idx() + cap * sizeof(int32_t); }   // [cap] bytes
+    constexpr size_t bytes() const { return status() + cap; }
+};
+static_assert(FlowGatherLayout{1}.bytes() - 16 <= FrameGatherLayout{1}.bytes() - VO_GATHER_HEADER, "flow gather <= frame_gather_bytes(cap)");
+struct FlowGather {
+    const float2 *next, *out0, *out1;
+    const uint8_t *status;
+    const float *err; // null: not requested
+    const int32_t *keep_idx;
+    const int *n_out;
+    int n, cap, compact;
+};
+void launch_flow_gather(const FlowGather &g, uint8_t *out, hipStream_t stream);
 void launch_triangulate(const float *Pl, const float *Pr, const float2 *pl, const float2 *pr,
                         size_t frame_stride, const int *n_pts, int cap, int max_pts, int n_frames, float *xyz,
                         hipStream_t stream);
