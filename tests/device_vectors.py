@@ -1,4 +1,4 @@
-"""The unit vectors of the device-math headers (vo_math.h, vo_linalg.h, vo_svd_wide.h, vo_epnp.h, vo_lkmath.h): one set of
+"""The unit vectors of the device-math headers (vo_math.h, vo_linalg.h, vo_svd_wide.h, vo_epnp.h, vo_lkmath.h, vo_isa.h): one set of
 generators for the CPU tests (host build, emulator) and for the GPU test that runs the same vectors on gfx950
 (tests/test_gpu_device_units.py through tests/host_check/device_check.hip).  A plain module: no fixtures, no assertions about
 the code under test -- only inputs, each with a fixed seed."""
@@ -139,10 +139,10 @@ def scharr_patches():
 
 
 # ---------------------------------------------------------------------------------------------
-# vo_lkmath.h: the raw instruction wrappers.  (n, 3) uint32 operand triples a, b, c per wrapper: 2^20 random ones inside the
+# vo_isa.h (and pack_w of vo_lkmath.h): the raw instruction wrappers.  (n, 3) uint32 operand triples a, b, c per wrapper: 2^20 random ones inside the
 # range the header defines the wrapper on, after the edge rows.
 LK_RAW = ["perm_b32", "udot2", "sdot2", "sdot2_first", "pk_sub_i16", "pk_lshr1_u16", "udot4", "pk_add_u16", "pk_subsat_u16",
-          "pk_min_u16", "pk_mad_u16", "alignbyte", "pack_w"]
+          "pk_min_u16", "pk_mad_u16", "alignbyte", "pack_w", "pk_absdiff_i16"]
 N_RAW = 1 << 20
 
 
@@ -212,6 +212,13 @@ def lk_raw_operands(name):
         r[:, 0], r[:, 1] = (w[:, 0] & 0xffffffff).astype(np.uint32), (w[:, 1] & 0xffffffff).astype(np.uint32)
         ext = [-(1 << 14), 1 << 14, 0, -1, 1, 16383, -16383]
         edges = np.array([[p & 0xffffffff, q & 0xffffffff, 0] for p in ext for q in ext], np.uint32)
+    elif name == "pk_absdiff_i16":
+        # int16 lanes whose difference fits int16 (the kernel's |Jp - Ip| <= 8160): both lanes of both operands from
+        # [-2^14, 2^14 - 1]; the edge rows hold +-2^14, 0 and equal operands in every lane combination
+        v = rng.integers(-(1 << 14), 1 << 14, (N_RAW, 4))
+        r[:, 0], r[:, 1] = _pack16(v[:, 0], v[:, 1]), _pack16(v[:, 2], v[:, 3])
+        ext = [-(1 << 14), 1 << 14, 0, (1 << 14) - 1, -1, 1, 8160, -8160]
+        edges = np.array([[int(_pack16(p, q)), int(_pack16(u, v_)), 0] for p in ext for q in ext for u in ext for v_ in ext], np.uint32)
     return np.ascontiguousarray(np.concatenate([edges.astype(np.uint32), r]))
 
 

@@ -65,14 +65,7 @@ int ife_seq_ingest(int fmt, const uint8_t *const *left, const uint8_t *const *ri
         tab[i].image0 = 2 * i;
     }
     const int n_rows = 2 * n_pairs * h;
-    switch (fmt) {
-    case ING_GRAY8_X2: seq_go<ING_GRAY8_X2>(tab.data(), n_rows, n_waves, w, h, pitch, dst); return 0;
-    case ING_BGR8: seq_go<ING_BGR8>(tab.data(), n_rows, n_waves, w, h, pitch, dst); return 0;
-    case ING_RGB8: seq_go<ING_RGB8>(tab.data(), n_rows, n_waves, w, h, pitch, dst); return 0;
-    case ING_BGRA8: seq_go<ING_BGRA8>(tab.data(), n_rows, n_waves, w, h, pitch, dst); return 0;
-    case ING_RGBA8: seq_go<ING_RGBA8>(tab.data(), n_rows, n_waves, w, h, pitch, dst); return 0;
-    }
-    return -1;
+    return ingest_dispatch(fmt, [&](auto tag) { seq_go<decltype(tag)::value>(tab.data(), n_rows, n_waves, w, h, pitch, dst); });
 }
 
 // pull_image_fmt_kernel<fmt>: one image of src_bytes bytes -> gray rows at `pitch`; n_pts float2 ride along (pts_src -> pts_dst) with their count
@@ -84,14 +77,7 @@ int ife_pull(int fmt, const uint8_t *src, size_t src_bytes, int stride, uint8_t 
     const uint2 *p2 = (const uint2 *)pts_src;
     uint2 *d2 = (uint2 *)pts_dst;
     const uint32_t n8 = pts_dst ? (uint32_t)n_pts : 0u;
-    switch (fmt) {
-    case ING_GRAY8_X2: pull_go<ING_GRAY8_X2>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); return 0;
-    case ING_BGR8: pull_go<ING_BGR8>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); return 0;
-    case ING_RGB8: pull_go<ING_RGB8>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); return 0;
-    case ING_BGRA8: pull_go<ING_BGRA8>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); return 0;
-    case ING_RGBA8: pull_go<ING_RGBA8>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); return 0;
-    }
-    return -1;
+    return ingest_dispatch(fmt, [&](auto tag) { pull_go<decltype(tag)::value>(s.get(), stride, dst, pitch, w, h, p2, d2, n8, count_dst, n_pts); });
 }
 
 int ife_bpp(int fmt) { return vo::ingest_bpp(fmt); }

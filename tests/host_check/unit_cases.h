@@ -169,7 +169,7 @@ struct Svd12 {
     }
 };
 
-// ---- vo_lkmath.h, the raw instruction wrappers: u32 a, b, c -> u32
+// ---- vo_isa.h (and pack_w of vo_lkmath.h), the raw instruction wrappers: u32 a, b, c -> u32
 constexpr const char *lk_raw_name(int w)
 {
     return w == 0    ? "lk_perm_b32"
@@ -184,7 +184,8 @@ constexpr const char *lk_raw_name(int w)
            : w == 9  ? "lk_pk_min_u16"
            : w == 10 ? "lk_pk_mad_u16"
            : w == 11 ? "lk_alignbyte"
-                     : "lk_pack_w";
+           : w == 12 ? "lk_pack_w"
+                     : "lk_pk_absdiff_i16";
 }
 template <int W>
 struct LkRaw {
@@ -205,7 +206,8 @@ struct LkRaw {
                            : W == 9  ? vo::pk_min_u16(a, b)
                            : W == 10 ? vo::pk_mad_u16(a, b, c)
                            : W == 11 ? vo::alignbyte(a, b, c)
-                                     : vo::pack_w((int)a, (int)b);
+                           : W == 12 ? vo::pack_w((int)a, (int)b)
+                                     : vo::pk_absdiff_i16(a, b);
     }
 };
 
@@ -300,6 +302,6 @@ struct OpList {
 };
 using AllOps = OpList<Math<0>, Math<1>, Math<2>, Math<3>, Math<4>, Epnp5, P3p4, P3pDeg4, RodV2m, RodM2v, Triangulate, FivePoint, Sampson,
                       Decompose, Cheirality, Solve6, Svd12, LkRaw<0>, LkRaw<1>, LkRaw<2>, LkRaw<3>, LkRaw<4>, LkRaw<5>, LkRaw<6>, LkRaw<7>,
-                      LkRaw<8>, LkRaw<9>, LkRaw<10>, LkRaw<11>, LkRaw<12>, Bilinear<false>, Bilinear<true>, Deriv, DiffDot, Scharr>;
+                      LkRaw<8>, LkRaw<9>, LkRaw<10>, LkRaw<11>, LkRaw<12>, LkRaw<13>, Bilinear<false>, Bilinear<true>, Deriv, DiffDot, Scharr>;
 
 } // namespace uc

@@ -91,6 +91,21 @@ def test_lk_diff_dot_exact(host_check):
     assert np.array_equal(b1, ref) and abs(ref).max() < 2**28
 
 
+def test_pk_absdiff_i16_host_text_exact(host_check):
+    """the host text of vo_isa.h's pk_absdiff_i16 (what the emulator runs in the tracker's err epilogue) against |a - b| per
+    int16 lane in int64: lanes from [-2^14, 2^14 - 1] and the edge rows with +-2^14, 0 and equal operands -- every difference
+    fits int16.  tests/test_gpu_device_units.py holds v_pk_sub_i16 + v_pk_max_i16 on gfx950 to the same operands."""
+    op = dv.lk_raw_operands("pk_absdiff_i16")
+    assert len(op) > dv.N_RAW
+    got = dv.host_reference(host_check, {"lk_pk_absdiff_i16": op}, "lk_pk_absdiff_i16")[:, 0]
+    lanes = op[:, :2].copy().view(np.int16).astype(np.int64)      # (n, 4): a.lo, a.hi, b.lo, b.hi
+    assert lanes.min() == -(1 << 14) and lanes.max() == 1 << 14
+    d = np.abs(lanes[:, :2] - lanes[:, 2:])
+    assert d.max() == 1 << 15 and (d == 0).all(1).any()      # 2^14 - (-2^14): the largest difference the edge rows hold
+    ref = (d[:, 0] | (d[:, 1] << 16)).astype(np.uint32)
+    assert np.array_equal(got, ref)
+
+
 def test_scharr_packed_matches_oracle(orc, host_check):
     rng = np.random.default_rng(8)
     img = rng.integers(0, 256, (9, 11), dtype=np.uint8)

@@ -21,7 +21,7 @@ from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
 SRC_DIR = os.path.join(ROOT, "tests", "host_check")
 CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
 DEPS = [os.path.join(SRC_DIR, f) for f in ("flow_emu.cpp", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_tri.h")]
+       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_tri.h")]
 CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
 
 

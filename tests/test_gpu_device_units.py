@@ -1,7 +1,7 @@
 """The unit vectors of the device-math headers run ON gfx950 (tests/host_check/device_check.hip: one small program, compiled
 with the product's flags, started ONCE) -- the device branches of every `#if defined(__HIP_DEVICE_COMPILE__)` that the CPU
-suite can only compile the other side of: v_perm_b32 / v_dot2 / v_pk_* / v_cvt_pk_i16_i32 / v_alignbyte behind vo_lkmath.h's
-wrappers, the v_mov_b64_dpp row_newbcast + v_add_f64 chains of vo_svd_wide.h under a partly masked EXEC, and the f64 pose math
+suite can only compile the other side of: v_perm_b32 / v_dot2 / v_pk_* / v_cvt_pk_i16_i32 / v_alignbyte behind the wrappers
+of vo_isa.h and vo_lkmath.h, the v_mov_b64_dpp row_newbcast + v_add_f64 chains of vo_svd_wide.h under a partly masked EXEC, and the f64 pose math
 (vo_math.h, vo_linalg.h, vo_epnp.h, vo_p3p.h, vo_fivept.h, vo_tri.h) as gfx950 code.
 
 Three kinds of checks, all with margin ZERO unless said otherwise:
@@ -235,12 +235,18 @@ def _raw_restatement(name, a, b, c):
         return ((((a.astype(np.uint64) << np.uint64(32)) | b.astype(np.uint64)) >> (c.astype(np.uint64) * np.uint64(8))) & np.uint64(m32)).astype(np.uint32)
     if name == "pack_w":
         return _pk(A, B)                                      # |w| <= 2^14: int16 holds it, no saturation
+    if name == "pk_absdiff_i16":
+        (al, ah), (bl, bh) = _lanes(a, True), _lanes(b, True)
+        # 2^14 - (-2^14) = 2^15 is the one difference of the operands beyond int16; its lane reads 0x8000 either way: as the
+        # u16 the err epilogue's v_dot2_u32_u16 takes, the result is |a - b| up to and including 2^15
+        assert max(np.abs(al - bl).max(), np.abs(ah - bh).max()) <= 2 ** 15
+        return _pk(np.abs(al - bl), np.abs(ah - bh))
     raise KeyError(name)
 
 
 @pytest.mark.parametrize("name", dv.LK_RAW)
 def test_lk_instruction_wrappers_on_the_device(dev, host_check, name):
-    """the CDNA4 instruction behind each wrapper of vo_lkmath.h against the wrapper's host text (plain C) and against a numpy
+    """the CDNA4 instruction behind each wrapper of vo_isa.h (and pack_w of vo_lkmath.h) against the wrapper's host text (plain C) and against a numpy
     restatement, on 2^20 random operand triples and the edges (tests/device_vectors.py: lk_raw_operands)"""
     ins, outs = dev
     op = ins["lk_" + name]

@@ -30,7 +30,7 @@ def ife():
     so = os.path.join(BUILD_DIR, "libingest_fmt_emu.so")
     csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
     deps = [os.path.join(src_dir, f) for f in ("ingest_fmt_emu.cpp", "hip_emu.h")]
-    deps += [os.path.join(csrc, f) for f in ("ingest_fmt.hip", "vo_dev.h", "vo_kernels.h")]
+    deps += [os.path.join(csrc, f) for f in ("ingest_fmt.hip", "vo_isa.h", "vo_dev.h", "vo_kernels.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
                                "-Wno-unknown-pragmas", "-Wno-attributes"] + SAN_FLAGS + ["-o", so,

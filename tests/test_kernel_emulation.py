@@ -24,7 +24,7 @@ def kemu():
     csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
     deps = [os.path.join(src_dir, f) for f in ("kernel_emu.cpp", "hip_emu.h")]
     deps += [os.path.join(csrc, f) for f in ("lk.hip", "pyramid.hip", "fast.hip", "dev/lk_dev.hip", "dev/pyramid_dev.hip", "dev/fast_dev.hip",
-                                               "vo_dev_hooks.h", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_svd_wide.h",
+                                               "vo_dev_hooks.h", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_svd_wide.h",
                                                "vo_linalg.h", "vo_epnp.h", "pnp.hip", "vo_p3p.h", "vo_math.h",
                                                "vo_seqtail.h", "vo_integrate.h", "post.hip", "vo_tri.h",
                                                "essential.hip", "vo_fivept.h", "seq.hip")]

@@ -24,7 +24,7 @@ from rectify_cases import HEIGHTS, MAP_KINDS, WIDTHS, make_image, make_maps, rem
 GUARD = 0xA5
 SRC_DIR = os.path.join(ROOT, "tests", "host_check")
 CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("rectify_emu.cpp", "hip_emu.h")] + [os.path.join(CSRC, f) for f in ("rectify.hip", "vo_rectify.h", "vo_dev.h", "vo_kernels.h")]
+DEPS = [os.path.join(SRC_DIR, f) for f in ("rectify_emu.cpp", "hip_emu.h")] + [os.path.join(CSRC, f) for f in ("rectify.hip", "vo_rectify.h", "vo_isa.h", "vo_dev.h", "vo_kernels.h")]
 CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
 
 

@@ -349,7 +349,7 @@ int vo_set_params(vo_ctx *c, const vo_params *p)
     }
     // the staging slots of the synchronous calls hold RAW rows of a non-gray format: they grow when such a format is
     // configured (a gray context keeps what vo_create allocated) and never shrink
-    const size_t raw = ((size_t)c->max_w * fmt_bpp(p->input_format) * c->max_h + 255) / 256 * 256;
+    const size_t raw = ((size_t)c->max_w * ingest_bpp(p->input_format) * c->max_h + 255) / 256 * 256;
     if (p->input_format != VO_FMT_GRAY8 && raw > c->stage_slot) {
         VO_HIP_TRY(c, hipSetDevice(c->device));
         int rcs = sync_all(c); // a queued pull may still read the old slots
@@ -606,7 +606,7 @@ int upload_image(vo_ctx *c, int idx, const void *src, int stride, hipMemcpyKind 
     if (c->n_images == 0)
         return fail(c, VO_ERR_STATE, "upload before vo_batch_configure");
     const int fmt = c->prm.input_format;
-    if (idx < 0 || idx >= c->n_images || !src || stride < c->w * fmt_bpp(fmt))
+    if (idx < 0 || idx >= c->n_images || !src || stride < c->w * ingest_bpp(fmt))
         return fail(c, VO_ERR_ARG, "vo_batch_upload_image: bad index / stride (at least w * bytes per pixel of vo_params.input_format)");
     if (c->seq.on)
         return fail(c, VO_ERR_STATE, "vo_batch_upload_image inside the sequence loop: use vo_seq_push_pair");

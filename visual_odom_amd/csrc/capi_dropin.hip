@@ -23,7 +23,7 @@ int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const ui
         return fail(c, VO_ERR_ARG, "null image / points");
     if (n > c->cap)
         return fail(c, VO_ERR_ARG, "more points than max_pts given to vo_create");
-    if (stride < w * fmt_bpp(c->prm.input_format)) // (before anything changes: a refused call leaves the kept pair as it is)
+    if (stride < w * ingest_bpp(c->prm.input_format)) // (before anything changes: a refused call leaves the kept pair as it is)
         return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
     if (keep && !have_kept_pair(c, w, h))
         return fail(c, VO_ERR_STATE, "no t0 images given, and the context does not hold the t1 pair of a previous call of this "
@@ -228,7 +228,7 @@ namespace vo_capi {
 // An image that is given goes to the slot pair that does not hold that t1 pair, which stays valid.
 int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride, bool plain)
 {
-    if (img && c && stride < w * fmt_bpp(c->prm.input_format))
+    if (img && c && stride < w * ingest_bpp(c->prm.input_format))
         return fail(c, VO_ERR_ARG, "stride smaller than the width (x bytes per pixel of vo_params.input_format)");
     if (!img && !have_kept_pair(c, w, h))
         return fail(c, VO_ERR_STATE, "no image given, and the context does not hold the t1 pair of a previous vo_track_frame "

@@ -49,7 +49,7 @@ int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_
         return fail(c, VO_ERR_ARG, (std::string(who) + ": more points than max_pts given to vo_create").c_str());
     if (w < 32 || h < 32 || w > c->max_w || h > c->max_h)
         return fail(c, VO_ERR_ARG, (std::string(who) + ": image size beyond the capacity given to vo_create").c_str());
-    if (stride < w * fmt_bpp(c->prm.input_format))
+    if (stride < w * ingest_bpp(c->prm.input_format))
         return fail(c, VO_ERR_ARG, (std::string(who) + ": stride smaller than the width (x bytes per pixel of vo_params.input_format)").c_str());
     int rc = ensure_flow(c);
     if (rc != VO_OK)

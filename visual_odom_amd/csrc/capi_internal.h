@@ -427,11 +427,10 @@ inline int *cur_npts(vo_ctx *c) { return c->pts_sel < 0 ? c->d_npts : c->d_npts_
 inline int *cur_ages(vo_ctx *c) { return c->pts_sel < 0 ? c->d_ages : c->d_ages_det[c->pts_sel]; }
 // row pitch (pixels) of a bordered level: VO_BX left + w + at least VO_BY right, multiple of 16
 inline int level_stride(int w) { return align_up(VO_BX + w + VO_BY, 16); }
-// vo_params.input_format (VO_FMT_*): source bytes per pixel -- the minimum byte stride of an image is w * fmt_bpp -- and the
-// bytes of a source row that are ever read or copied: one plane of a two-byte interleave ends with its last pixel (the right
-// plane of an interleaved frame starts at byte 1: byte 2 w of its last row is outside the frame)
-inline int fmt_bpp(int fmt) { return fmt == VO_FMT_GRAY8 ? 1 : fmt == VO_FMT_GRAY8_X2 ? 2 : fmt <= VO_FMT_RGB8 ? 3 : 4; }
-inline size_t fmt_row_bytes(int fmt, int w) { return fmt == VO_FMT_GRAY8_X2 ? 2 * (size_t)w - 1 : (size_t)w * fmt_bpp(fmt); }
+// the bytes of a source row of vo_params.input_format that are ever read or copied (ingest_bpp: vo_kernels.h): one plane of a
+// two-byte interleave ends with its last pixel (the right plane of an interleaved frame starts at byte 1: byte 2 w of its last
+// row is outside the frame)
+inline size_t fmt_row_bytes(int fmt, int w) { return fmt == VO_FMT_GRAY8_X2 ? 2 * (size_t)w - 1 : (size_t)w * ingest_bpp(fmt); }
 
 // the stream the lock-step loop's ingest kernel goes to (created by ensure_ingest_stream; set_sched keeps it in existence)
 inline hipStream_t ingest_stream(const vo_ctx *c) { return c->sched.prep ? c->sel->prep : c->sel->copy; }

@@ -278,7 +278,7 @@ static int seq_push_impl(vo_ctx *c, int seq, const void *left, const void *right
         return fail(c, VO_ERR_STATE, "vo_seq_push_pair before vo_seq_configure");
     if (q.broken)
         return fail(c, VO_ERR_STATE, "vo_seq_push_pair: a previous vo_seq_step failed half-way; vo_seq_reset(ctx, -1) first");
-    const int fmt = c->prm.input_format, bpp = fmt_bpp(fmt);
+    const int fmt = c->prm.input_format, bpp = ingest_bpp(fmt);
     if (seq < 0 || seq >= q.S || !left || !right || stride < c->w * bpp)
         return fail(c, VO_ERR_ARG, "vo_seq_push_pair: bad sequence / image / stride (at least w * bytes per pixel of vo_params.input_format)");
     if (q.pushed[seq])

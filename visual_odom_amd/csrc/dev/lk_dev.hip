@@ -148,16 +148,16 @@ __global__ VO_LK_PAIR_ATTRS void lk_circular_pair_kernel(const PyrImage *__restr
     {                                                                                                                  \
         const uint32_t o = (uint32_t)((ipys + (r) + VO_BY) * istride + ipxs + (c0) + VO_BX);                           \
         const uint32_t od = (live) ? 4u * o : 0u;                                                                      \
-        const LkU2 t = *(const VO_GLOBAL LkU2 *)(Ib + o);                                                              \
-        const LkU2 u = *(const VO_GLOBAL LkU2 *)(Ib + (o + (uint32_t)istride));                                        \
-        const LkU4 dt0 = *(const VO_GLOBAL LkU4 *)(Db + od);                                                           \
-        const LkU4 dt1 = *(const VO_GLOBAL LkU4 *)(Db + (od + 16u));                                                   \
-        const LkU4 db0 = *(const VO_GLOBAL LkU4 *)(Db + (od + drow));                                                  \
-        const LkU4 db1 = *(const VO_GLOBAL LkU4 *)(Db + (od + drow + 16u));                                            \
+        const U32x2A1 t = *(const VO_GLOBAL U32x2A1 *)(Ib + o);                                                        \
+        const U32x2A1 u = *(const VO_GLOBAL U32x2A1 *)(Ib + (o + (uint32_t)istride));                                  \
+        const U32x4A4 dt0 = *(const VO_GLOBAL U32x4A4 *)(Db + od);                                                     \
+        const U32x4A4 dt1 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + 16u));                                             \
+        const U32x4A4 db0 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + drow));                                            \
+        const U32x4A4 db1 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + drow + 16u));                                      \
         const uint32_t dt[8] = {dt0.a, dt0.b, dt0.c, dt0.d, dt1.a, dt1.b, dt1.c, dt1.d};                               \
         const uint32_t db[8] = {db0.a, db0.b, db0.c, db0.d, db1.a, db1.b, db1.c, db1.d};                               \
         uint32_t Ip[4];                                                                                                \
-        bilinear7_u8(t.lo, t.hi, u.lo, u.hi, wt, wb, Ip);                                                              \
+        bilinear7_u8(t.a, t.b, u.a, u.b, wt, wb, Ip);                                                                  \
         bilinear7_deriv(dt, db, wt, wb, Ixp, Iyp);                                                                     \
         _Pragma("unroll") for (int m = 0; m < 4; m++)                                                                  \
         {                                                                                                              \
@@ -228,41 +228,23 @@ __global__ VO_LK_PAIR_ATTRS void lk_circular_pair_kernel(const PyrImage *__restr
                         run = false;
                     }
                     const bool e2 = entry && !oob;
-                    const bool need = e2 && (!have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 ||
-                                             iny + LK_WIN + 1 > jy0 + LK_JT_H);
+                    const bool need = e2 && lk_tile_misses(have_tile, jx0, jy0, inx, iny);
                     if (VO_BALLOT(need) != 0ull) {
-                        if (need) {
-                            jx0 = (inx - 12) & ~3;
-                            jy0 = iny - 9;
-                            jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
-                            jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
-                        }
                         __syncthreads(); // single-wave workgroup: orders the LDS reads before the refill
-                        if (need) {
-                            const VO_GLOBAL uint8_t *tb = Jimg + ((ptrdiff_t)jy0 * jstride + jx0);
-                            for (int c = hl; c < LK_JT_H * (LK_JT_W / 16); c += 32) {
-                                const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
-                                const LkU4 v = *(const VO_GLOBAL LkU4 *)(tb + (uint32_t)(row * jstride + 16 * col));
-                                *reinterpret_cast<uint4 *>(&tile[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
-                            }
+                        if (need) { // this half's own tile, filled by its 32 lanes
+                            const LkOrigin o = lk_tile_refill(tile, Jimg, jstride, jx_max, jy_max, inx, iny, hl, 32);
+                            jx0 = o.x;
+                            jy0 = o.y;
                             have_tile = true;
                         }
                         __syncthreads();
                     }
                     if (e2)
                         offT = (iny - jy0) * LK_JT_W + (inx - jx0);
-                    {
-                        // every lane lifts its current cell again (a half that did not move re-reads the same bytes; a
-                        // half without a tile reads offset 0 and never uses the result)
-                        const LkU2 tA = *reinterpret_cast<const LkU2 *>(&tile[offT + offA]);
-                        const LkU2 uA = *reinterpret_cast<const LkU2 *>(&tile[offT + offA + LK_JT_W]);
-                        const LkU2 tB = *reinterpret_cast<const LkU2 *>(&tile[offT + offB]);
-                        const LkU2 uB = *reinterpret_cast<const LkU2 *>(&tile[offT + offB + LK_JT_W]);
-                        lift7(tA.lo, tA.hi, JtA);
-                        lift7(uA.lo, uA.hi, JbA);
-                        lift7(tB.lo, tB.hi, JtB);
-                        lift7(uB.lo, uB.hi, JbB);
-                    }
+                    // every lane lifts its current cell again (a half that did not move re-reads the same bytes; a
+                    // half without a tile reads offset 0 and never uses the result)
+                    lk_cell_rows(tile, offT + offA, JtA, JbA);
+                    lk_cell_rows(tile, offT + offB, JtB, JbB);
                     entry = false;
                     if (VO_BALLOT(run) == 0ull)
                         break;
@@ -357,12 +339,9 @@ static void launch_lk_circular_pair(const PyrImage *d_imgs, const Quad *d_quads,
 {
     if (max_pts <= 0 || n_frames <= 0)
         return;
-    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
-    const int parts = 8 / fpg, pairs = (max_pts + 1) / 2, ppp = (pairs + parts - 1) / parts;
-    const int groups = (n_frames + fpg - 1) / fpg;
-    dim3 grid((unsigned)(8 * groups * ppp));
-    hipLaunchKernelGGL(lk_circular_pair_kernel, grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
-                       fpg, ppp, d_trk, d_status, prm);
+    const LkGrid g = lk_grid(n_frames, (max_pts + 1) / 2); // PAIRS per part
+    hipLaunchKernelGGL(lk_circular_pair_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
+                       g.fpg, g.ppp, d_trk, d_status, prm);
 }
 
 // VO_LK_PAIR=1: the pair kernel.  Read per launch (tools/dev_variants_check.py flips it between two contexts of one process).

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void border_fill_kernel(const PyrImage *__rest
     const VO_GLOBAL uint8_t *__restrict__ src = p + (ptrdiff_t)reflect101(y, h) * stride;
     uint32_t v[4];
     if (x0 >= 0 && x0 + 15 < w) {
-        const U32x4 t = *(const VO_GLOBAL U32x4 *)(src + x0);
+        const U32x4A4 t = *(const VO_GLOBAL U32x4A4 *)(src + x0);
         v[0] = t.a;
         v[1] = t.b;
         v[2] = t.c;
@@ -136,7 +136,7 @@ __device__ __forceinline__ uint2 pyr_hrow(const VO_GLOBAL uint8_t *__restrict__ 
 {
     uint32_t w0, w1, w2, w3;
     if (!EDGE) {
-        const U32x4 v = *(const VO_GLOBAL U32x4 *)(row + c0);
+        const U32x4A4 v = *(const VO_GLOBAL U32x4A4 *)(row + c0);
         w0 = v.a;
         w1 = v.b;
         w2 = v.c;
@@ -242,9 +242,9 @@ __global__ __launch_bounds__(256) void pyr_down_lds_kernel(const PyrImage *__res
         const int r = i / (PD_SW / 16), c = i - r * (PD_SW / 16);
         const int x = sx0 + 16 * c, y = reflect101(sy0 + r, sh);
         const VO_GLOBAL uint8_t *g = src + (ptrdiff_t)y * sstride + x;
-        U32x4 v = {0, 0, 0, 0};
+        U32x4A4 v = {0, 0, 0, 0};
         if (x + 16 <= xmax) {
-            v = *(const VO_GLOBAL U32x4 *)g;
+            v = *(const VO_GLOBAL U32x4A4 *)g;
         } else {
             if (x + 4 <= xmax)
                 v.a = *(const VO_GLOBAL uint32_t *)g;

@@ -37,21 +37,6 @@
 
 namespace vo {
 
-struct __attribute__((packed, aligned(4))) FastU32x4 {
-    uint32_t a, b, c, d;
-};
-
-// (acc << 1) | (x < 0): one v_alignbit_b32 shifts a comparison's sign bit into a ring mask (a compare + select + or
-// per bit cost 2.5 x as much issue time, profiles/r02_valu_issue_cost.txt)
-__device__ __forceinline__ uint32_t shift_in_sign(uint32_t acc, int x)
-{
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(VO_HOST_EMUL)
-    return __builtin_amdgcn_alignbit(acc, (uint32_t)x, 31);
-#else
-    return (acc << 1) | ((uint32_t)x >> 31);
-#endif
-}
-
 // the 16 differences centre - circle pixel: Bresenham circle of radius 3, the 16 offsets of FAST_t<16> starting at (0, 3),
 // clockwise
 __device__ __forceinline__ void fast_ring(const uint8_t *__restrict__ p, int stride, int *__restrict__ d)
@@ -231,8 +216,8 @@ __device__ __forceinline__ void fast_tile_body(const PyrImage *__restrict__ imgs
         const int row = i / (PW / 16), c = i - row * (PW / 16);
         const int gy = y0 - 4 + row < last_row ? y0 - 4 + row : last_row;
         const int gc = 16 * c < last_chunk ? 16 * c : last_chunk;
-        *reinterpret_cast<FastU32x4 *>(&s_px[row * PW + 16 * c]) =
-            *reinterpret_cast<const VO_GLOBAL FastU32x4 *>(base + ((ptrdiff_t)gy * stride + gc));
+        *reinterpret_cast<U32x4A4 *>(&s_px[row * PW + 16 * c]) =
+            *reinterpret_cast<const VO_GLOBAL U32x4A4 *>(base + ((ptrdiff_t)gy * stride + gc));
     }
     if (tid == 0)
         s_ncand = s_ncorner = 0;

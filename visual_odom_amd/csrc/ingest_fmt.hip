@@ -29,55 +29,16 @@
 // the three products by two v_dot4_u32_u8 against the weights split into byte halves (1868 = 7 * 256 + 76, 9617 = 37 * 256 +
 // 145, 4899 = 19 * 256 + 35; the fourth weight is 0, which is how alpha -- or the neighbour's first byte -- is ignored), i.e.
 // dot4(p, lo) + 8192 + (dot4(p, hi) << 8), exact in 32 bits (<= 255 * 16384 + 8192).
+#include "vo_isa.h"
 #include "vo_kernels.h"
+
+#include <type_traits>
 
 namespace vo {
 
-// (the values of VO_FMT_* in include/vo_hip.h)
-enum { ING_GRAY8 = 0, ING_GRAY8_X2 = 1, ING_BGR8 = 2, ING_RGB8 = 3, ING_BGRA8 = 4, ING_RGBA8 = 5 };
-
-__host__ __device__ constexpr int ingest_bpp(int fmt) { return fmt == ING_GRAY8 ? 1 : fmt == ING_GRAY8_X2 ? 2 : fmt <= ING_RGB8 ? 3 : 4; }
-
-// v_perm_b32: byte k of the result = byte sel[k] of {hi, lo} (0 .. 3 = lo, 4 .. 7 = hi)
-__device__ __forceinline__ uint32_t ing_perm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-#ifdef VO_HOST_EMUL
-    const uint64_t v = ((uint64_t)hi << 32) | lo;
-    uint32_t r = 0;
-    for (int k = 0; k < 4; k++)
-        r |= (uint32_t)((v >> (8 * ((sel >> (8 * k)) & 7))) & 0xff) << (8 * k); // (selectors 0 .. 7 only)
-    return r;
-#else
-    return __builtin_amdgcn_perm(hi, lo, sel);
-#endif
-}
-// v_alignbyte_b32: ({hi, lo} >> 8 * sh) & 0xffffffff
-__device__ __forceinline__ uint32_t ing_alignbyte(uint32_t hi, uint32_t lo, uint32_t sh)
-{
-#ifdef VO_HOST_EMUL
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * (sh & 3)));
-#else
-    return __builtin_amdgcn_alignbyte(hi, lo, sh);
-#endif
-}
-// v_dot4_u32_u8: a.b0 * b.b0 + a.b1 * b.b1 + a.b2 * b.b2 + a.b3 * b.b3 + c
-__device__ __forceinline__ uint32_t ing_dot4(uint32_t a, uint32_t b, uint32_t c)
-{
-#if defined(VO_HOST_EMUL) || !defined(__HIP_DEVICE_COMPILE__)
-    for (int k = 0; k < 4; k++)
-        c += ((a >> (8 * k)) & 0xff) * ((b >> (8 * k)) & 0xff);
-    return c;
-#else
-    return __builtin_amdgcn_udot4(a, b, c, false);
-#endif
-}
-
-struct __attribute__((packed, aligned(1))) IngW2 {
-    uint32_t a, b;
-};
-struct __attribute__((packed, aligned(1))) IngW4 {
-    uint32_t a, b, c, d;
-};
+// the kernels' names for the formats: the values of the public header
+enum { ING_GRAY8 = VO_FMT_GRAY8, ING_GRAY8_X2 = VO_FMT_GRAY8_X2, ING_BGR8 = VO_FMT_BGR8, ING_RGB8 = VO_FMT_RGB8, ING_BGRA8 = VO_FMT_BGRA8,
+       ING_RGBA8 = VO_FMT_RGBA8 };
 
 // gray of one pixel whose bytes 0 .. 2 are (B, G, R) -- or (R, G, B) with SWAP -- and whose byte 3 is ignored
 template <bool SWAP>
@@ -86,7 +47,7 @@ __device__ __forceinline__ uint32_t ing_gray(uint32_t p)
     constexpr uint32_t c0 = SWAP ? 4899u : 1868u, c2 = SWAP ? 1868u : 4899u;
     constexpr uint32_t lo = (c0 & 255u) | ((9617u & 255u) << 8) | ((c2 & 255u) << 16);
     constexpr uint32_t hi = (c0 >> 8) | ((9617u >> 8) << 8) | ((c2 >> 8) << 16);
-    return (ing_dot4(p, lo, 8192u) + (ing_dot4(p, hi, 0u) << 8)) >> 14;
+    return (udot4(p, lo, 8192u) + (udot4(p, hi, 0u) << 8)) >> 14;
 }
 __device__ __forceinline__ uint32_t ing_pack4(uint32_t y0, uint32_t y1, uint32_t y2, uint32_t y3)
 {
@@ -96,27 +57,27 @@ __device__ __forceinline__ uint32_t ing_pack4(uint32_t y0, uint32_t y1, uint32_t
 // 8 destination pixels from the source bytes of pixel x .. x + 7 of a row: s = row + x * bpp.  Reads [s, s + 8 * bpp), for
 // ING_GRAY8_X2 [s, s + 15).
 template <int FMT>
-__device__ __forceinline__ IngW2 ingest_row8(const VO_GLOBAL uint8_t *__restrict__ s)
+__device__ __forceinline__ U32x2A1 ingest_row8(const VO_GLOBAL uint8_t *__restrict__ s)
 {
-    IngW2 o;
+    U32x2A1 o;
     if constexpr (FMT == ING_GRAY8_X2) {
-        const IngW2 u = *reinterpret_cast<const VO_GLOBAL IngW2 *>(s);     // bytes 0 .. 7: pixels 0 .. 3 at 0, 2, 4, 6
-        const IngW2 v = *reinterpret_cast<const VO_GLOBAL IngW2 *>(s + 7); // bytes 7 .. 14: pixels 4 .. 7 at 1, 3, 5, 7
-        o.a = ing_perm(u.b, u.a, 0x06040200u);
-        o.b = ing_perm(v.b, v.a, 0x07050301u);
+        const U32x2A1 u = *reinterpret_cast<const VO_GLOBAL U32x2A1 *>(s);     // bytes 0 .. 7: pixels 0 .. 3 at 0, 2, 4, 6
+        const U32x2A1 v = *reinterpret_cast<const VO_GLOBAL U32x2A1 *>(s + 7); // bytes 7 .. 14: pixels 4 .. 7 at 1, 3, 5, 7
+        o.a = perm_b32(u.b, u.a, 0x06040200u);
+        o.b = perm_b32(v.b, v.a, 0x07050301u);
     } else if constexpr (FMT == ING_BGR8 || FMT == ING_RGB8) {
         constexpr bool SW = FMT == ING_RGB8;
-        const IngW4 u = *reinterpret_cast<const VO_GLOBAL IngW4 *>(s);      // bytes 0 .. 15
-        const IngW2 v = *reinterpret_cast<const VO_GLOBAL IngW2 *>(s + 16); // bytes 16 .. 23
-        o.a = ing_pack4(ing_gray<SW>(u.a), ing_gray<SW>(ing_alignbyte(u.b, u.a, 3)), ing_gray<SW>(ing_alignbyte(u.c, u.b, 2)),
+        const U32x4A1 u = *reinterpret_cast<const VO_GLOBAL U32x4A1 *>(s);      // bytes 0 .. 15
+        const U32x2A1 v = *reinterpret_cast<const VO_GLOBAL U32x2A1 *>(s + 16); // bytes 16 .. 23
+        o.a = ing_pack4(ing_gray<SW>(u.a), ing_gray<SW>(alignbyte(u.b, u.a, 3)), ing_gray<SW>(alignbyte(u.c, u.b, 2)),
                         ing_gray<SW>(u.c >> 8));
-        o.b = ing_pack4(ing_gray<SW>(u.d), ing_gray<SW>(ing_alignbyte(v.a, u.d, 3)), ing_gray<SW>(ing_alignbyte(v.b, v.a, 2)),
+        o.b = ing_pack4(ing_gray<SW>(u.d), ing_gray<SW>(alignbyte(v.a, u.d, 3)), ing_gray<SW>(alignbyte(v.b, v.a, 2)),
                         ing_gray<SW>(v.b >> 8));
     } else {
         static_assert(FMT == ING_BGRA8 || FMT == ING_RGBA8, "one of the VO_FMT_* formats that need a conversion");
         constexpr bool SW = FMT == ING_RGBA8;
-        const IngW4 u = *reinterpret_cast<const VO_GLOBAL IngW4 *>(s);
-        const IngW4 v = *reinterpret_cast<const VO_GLOBAL IngW4 *>(s + 16);
+        const U32x4A1 u = *reinterpret_cast<const VO_GLOBAL U32x4A1 *>(s);
+        const U32x4A1 v = *reinterpret_cast<const VO_GLOBAL U32x4A1 *>(s + 16);
         o.a = ing_pack4(ing_gray<SW>(u.a), ing_gray<SW>(u.b), ing_gray<SW>(u.c), ing_gray<SW>(u.d));
         o.b = ing_pack4(ing_gray<SW>(v.a), ing_gray<SW>(v.b), ing_gray<SW>(v.c), ing_gray<SW>(v.d));
     }
@@ -124,13 +85,13 @@ __device__ __forceinline__ IngW2 ingest_row8(const VO_GLOBAL uint8_t *__restrict
 }
 
 // both planes of eight 16-bit words (an interleaved pair, right == left + 1): reads [s, s + 16)
-__device__ __forceinline__ void ingest_split8(const VO_GLOBAL uint8_t *__restrict__ s, IngW2 &lo, IngW2 &hi)
+__device__ __forceinline__ void ingest_split8(const VO_GLOBAL uint8_t *__restrict__ s, U32x2A1 &lo, U32x2A1 &hi)
 {
-    const IngW4 u = *reinterpret_cast<const VO_GLOBAL IngW4 *>(s);
-    lo.a = ing_perm(u.b, u.a, 0x06040200u);
-    lo.b = ing_perm(u.d, u.c, 0x06040200u);
-    hi.a = ing_perm(u.b, u.a, 0x07050301u);
-    hi.b = ing_perm(u.d, u.c, 0x07050301u);
+    const U32x4A1 u = *reinterpret_cast<const VO_GLOBAL U32x4A1 *>(s);
+    lo.a = perm_b32(u.b, u.a, 0x06040200u);
+    lo.b = perm_b32(u.d, u.c, 0x06040200u);
+    hi.a = perm_b32(u.b, u.a, 0x07050301u);
+    hi.b = perm_b32(u.d, u.c, 0x07050301u);
 }
 
 // The converting twin of seq_ingest_kernel (seq.hip; the discipline and its reasons are written down there): row r =
@@ -156,12 +117,12 @@ __global__ __launch_bounds__(64) void seq_ingest_fmt_kernel(const SeqIngest *__r
             if (x < w) {
                 x = x < last ? x : last;
                 if (both) {
-                    IngW2 lo, hi;
+                    U32x2A1 lo, hi;
                     ingest_split8(s + (uint32_t)x * 2u, lo, hi);
-                    *reinterpret_cast<VO_GLOBAL IngW2 *>(d + (uint32_t)x) = lo;
-                    *reinterpret_cast<VO_GLOBAL IngW2 *>(d + img_bytes + (uint32_t)x) = hi;
+                    *reinterpret_cast<VO_GLOBAL U32x2A1 *>(d + (uint32_t)x) = lo;
+                    *reinterpret_cast<VO_GLOBAL U32x2A1 *>(d + img_bytes + (uint32_t)x) = hi;
                 } else {
-                    *reinterpret_cast<VO_GLOBAL IngW2 *>(d + (uint32_t)x) = ingest_row8<FMT>(s + (uint32_t)x * (uint32_t)BPP);
+                    *reinterpret_cast<VO_GLOBAL U32x2A1 *>(d + (uint32_t)x) = ingest_row8<FMT>(s + (uint32_t)x * (uint32_t)BPP);
                 }
             }
         }
@@ -185,7 +146,7 @@ __global__ __launch_bounds__(256) void pull_image_fmt_kernel(const uint8_t *__re
         if (row < h && x < w) {
             x = x < w - 8 ? x : w - 8;
             const VO_GLOBAL uint8_t *__restrict__ s = (const VO_GLOBAL uint8_t *)src + (size_t)row * src_stride + (uint32_t)x * (uint32_t)BPP;
-            *reinterpret_cast<VO_GLOBAL IngW2 *>((VO_GLOBAL uint8_t *)dst + (size_t)row * pitch + (uint32_t)x) = ingest_row8<FMT>(s);
+            *reinterpret_cast<VO_GLOBAL U32x2A1 *>((VO_GLOBAL uint8_t *)dst + (size_t)row * pitch + (uint32_t)x) = ingest_row8<FMT>(s);
         }
     } else {
         const uint32_t i = (blockIdx.x - img_blocks) * 256u + threadIdx.x;
@@ -196,14 +157,22 @@ __global__ __launch_bounds__(256) void pull_image_fmt_kernel(const uint8_t *__re
         *count_dst = count;
 }
 
-#ifndef VO_HOST_EMUL // (the CPU emulator of tests/host_check launches the kernels above itself)
-template <int FMT>
-static void seq_ingest_fmt_go(const SeqIngest *tab, int n_rows, int n_waves, int w, int h, int pitch, uint8_t *pix0, size_t img_bytes,
-                              hipStream_t stream)
+// ONE dispatch over the formats that have kernels here: f(std::integral_constant<int, FMT>) for the format, 0; -1 where there
+// is none -- the caller reports it, nothing is copied.  (The launchers below and the CPU emulator's, tests/host_check.)
+template <class F>
+static int ingest_dispatch(int fmt, F &&f)
 {
-    hipLaunchKernelGGL(seq_ingest_fmt_kernel<FMT>, dim3(n_waves), dim3(64), 0, stream, tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes);
+    switch (fmt) {
+    case ING_GRAY8_X2: f(std::integral_constant<int, ING_GRAY8_X2>()); return 0;
+    case ING_BGR8: f(std::integral_constant<int, ING_BGR8>()); return 0;
+    case ING_RGB8: f(std::integral_constant<int, ING_RGB8>()); return 0;
+    case ING_BGRA8: f(std::integral_constant<int, ING_BGRA8>()); return 0;
+    case ING_RGBA8: f(std::integral_constant<int, ING_RGBA8>()); return 0;
+    }
+    return -1;
 }
 
+#ifndef VO_HOST_EMUL // (the CPU emulator of tests/host_check launches the kernels above itself)
 int launch_seq_ingest_fmt(int fmt, const SeqIngest *tab, int n_pairs, int w, int h, int pitch, uint8_t *pix0, size_t img_bytes,
                           bool over_pcie, hipStream_t stream)
 {
@@ -212,37 +181,22 @@ int launch_seq_ingest_fmt(int fmt, const SeqIngest *tab, int n_pairs, int w, int
     const int want = over_pcie ? 192 : 8192; // (launch_seq_ingest's grids, seq.hip)
     const int n_rows = 2 * n_pairs * h;
     const int n_waves = n_rows < want ? n_rows : want;
-    switch (fmt) {
-    case ING_GRAY8_X2: seq_ingest_fmt_go<ING_GRAY8_X2>(tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes, stream); return 0;
-    case ING_BGR8: seq_ingest_fmt_go<ING_BGR8>(tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes, stream); return 0;
-    case ING_RGB8: seq_ingest_fmt_go<ING_RGB8>(tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes, stream); return 0;
-    case ING_BGRA8: seq_ingest_fmt_go<ING_BGRA8>(tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes, stream); return 0;
-    case ING_RGBA8: seq_ingest_fmt_go<ING_RGBA8>(tab, n_rows, n_waves, w, h, pitch, pix0, img_bytes, stream); return 0;
-    }
-    return -1; // no kernel for this format: the caller reports it, nothing is copied
-}
-
-template <int FMT>
-static void pull_image_fmt_go(const void *src, int src_stride, void *dst, int pitch, int w, int h, hipStream_t stream, const void *pts_src,
-                              void *pts_dst, int n_pts, int *count_dst)
-{
-    const uint32_t waves = (uint32_t)h * (uint32_t)((w + 511) / 512), img_blocks = (waves + 3) / 4;
-    const uint32_t n8 = pts_dst ? (uint32_t)n_pts : 0u;
-    hipLaunchKernelGGL(pull_image_fmt_kernel<FMT>, dim3(img_blocks + (n8 + 255) / 256), dim3(256), 0, stream, (const uint8_t *)src, src_stride,
-                       (uint8_t *)dst, pitch, w, h, img_blocks, (const uint2 *)pts_src, (uint2 *)pts_dst, n8, count_dst, n_pts);
+    return ingest_dispatch(fmt, [&](auto tag) {
+        hipLaunchKernelGGL(seq_ingest_fmt_kernel<decltype(tag)::value>, dim3(n_waves), dim3(64), 0, stream, tab, n_rows, n_waves, w, h, pitch,
+                           pix0, img_bytes);
+    });
 }
 
 int launch_pull_image_fmt(int fmt, const void *src, int src_stride, void *dst, int pitch, int w, int h, hipStream_t stream,
                           const void *pts_pinned_dev, void *pts_dst, int n_pts, int *count_dst)
 {
-    switch (fmt) {
-    case ING_GRAY8_X2: pull_image_fmt_go<ING_GRAY8_X2>(src, src_stride, dst, pitch, w, h, stream, pts_pinned_dev, pts_dst, n_pts, count_dst); return 0;
-    case ING_BGR8: pull_image_fmt_go<ING_BGR8>(src, src_stride, dst, pitch, w, h, stream, pts_pinned_dev, pts_dst, n_pts, count_dst); return 0;
-    case ING_RGB8: pull_image_fmt_go<ING_RGB8>(src, src_stride, dst, pitch, w, h, stream, pts_pinned_dev, pts_dst, n_pts, count_dst); return 0;
-    case ING_BGRA8: pull_image_fmt_go<ING_BGRA8>(src, src_stride, dst, pitch, w, h, stream, pts_pinned_dev, pts_dst, n_pts, count_dst); return 0;
-    case ING_RGBA8: pull_image_fmt_go<ING_RGBA8>(src, src_stride, dst, pitch, w, h, stream, pts_pinned_dev, pts_dst, n_pts, count_dst); return 0;
-    }
-    return -1;
+    const uint32_t waves = (uint32_t)h * (uint32_t)((w + 511) / 512), img_blocks = (waves + 3) / 4;
+    const uint32_t n8 = pts_dst ? (uint32_t)n_pts : 0u;
+    return ingest_dispatch(fmt, [&](auto tag) {
+        hipLaunchKernelGGL(pull_image_fmt_kernel<decltype(tag)::value>, dim3(img_blocks + (n8 + 255) / 256), dim3(256), 0, stream,
+                           (const uint8_t *)src, src_stride, (uint8_t *)dst, pitch, w, h, img_blocks, (const uint2 *)pts_pinned_dev,
+                           (uint2 *)pts_dst, n8, count_dst, n_pts);
+    });
 }
 #endif // VO_HOST_EMUL
 

@@ -1,4 +1,5 @@
-// lk.hip -- fused 4-hop pyramidal Lucas-Kanade "circular matching" kernel.
+// lk.hip -- the pyramidal Lucas-Kanade kernels: the fused 4-hop "circular matching" chain, the same body for a range of its
+// hops, and for ONE hop between two images with the err output (the two-image tracker).
 //
 // Replaces the four chained cv::calcOpticalFlowPyrLK calls of circularMatching()
 // (reference src/feature.cpp:136-139: l0->r0, r0->r1, r1->l1, l1->l0; winSize 21x21, maxLevel 3,
@@ -40,13 +41,6 @@ constexpr int LK_WIN = 21;
 constexpr int LK_JT_W = 48, LK_JT_H = 40; // search tile (bytes x rows), LDS row stride = LK_JT_W
 constexpr int LK_W_BITS = 14;
 
-struct __attribute__((packed, aligned(1))) LkU2 {
-    uint32_t lo, hi;
-};
-struct __attribute__((packed, aligned(4))) LkU4 {
-    uint32_t a, b, c, d;
-};
-
 // 14-bit fixed-point bilinear weights of OpenCV's LKTrackerInvoker from the fractional parts of the
 // window corner: iw00 = cvRound((1-a)*(1-b)*2^14), iw01 = cvRound(a*(1-b)*2^14), iw10 = cvRound((1-a)*b*2^14),
 // iw11 = 2^14 - iw00 - iw01 - iw10, returned as the packed int16 pairs wt = (iw00, iw01), wb = (iw10, iw11).
@@ -67,17 +61,56 @@ __device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint3
     wb = perm_b32(iw11, r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
 }
 
-// |a - b| of the two int16 lanes (v_pk_sub_i16, v_pk_max_i16): the err epilogue's residuals, |Jp - Ip| <= 8160
-__device__ __forceinline__ uint32_t pk_absdiff_i16(uint32_t a, uint32_t b)
+// ---- the search tile: LK_JT_H rows of LK_JT_W bytes of J in LDS, origin (jx0, jy0) -------------------------------------
+// The helpers take and return the origin BY VALUE: a local whose address goes into a call stays in memory until the call is
+// inlined, and the kernels' scalar control flow then comes out differently (profiles/kernel_sources.md).
+struct LkOrigin {
+    int x, y;
+};
+// is there no tile yet, or does it miss part of the window of corner (inx, iny): columns inx .. inx + 21, rows iny .. iny + 21
+__device__ __forceinline__ bool lk_tile_misses(bool have_tile, int jx0, int jy0, int inx, int iny)
 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef short i16x2 __attribute__((ext_vector_type(2)));
-    const i16x2 d = __builtin_bit_cast(i16x2, a) - __builtin_bit_cast(i16x2, b);
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(d, (i16x2)(-d)));
-#else
-    const int lo = (int16_t)(a & 0xffff) - (int16_t)(b & 0xffff), hi = (int16_t)(a >> 16) - (int16_t)(b >> 16);
-    return (uint32_t)((lo < 0 ? -lo : lo) & 0xffff) | ((uint32_t)((hi < 0 ? -hi : hi) & 0xffff) << 16);
-#endif
+    return !have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 || iny + LK_WIN + 1 > jy0 + LK_JT_H;
+}
+// a new tile around corner (inx, iny): the origin -- 4-byte aligned, clamped to [-VO_BX, jx_max] x [-VO_BY, jy_max], which keeps
+// the tile inside the level's rectangle -- and the fill, 16-byte chunks c0, c0 + step, ... of the tile's LK_JT_H * LK_JT_W / 16.
+// Returns the origin.  No barrier in here: the caller orders the fill against the LDS reads around it.
+__device__ __forceinline__ LkOrigin lk_tile_refill(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
+                                               int inx, int iny, int c0, int step)
+{
+    int jx0 = (inx - 12) & ~3;
+    int jy0 = iny - 9;
+    jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
+    jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
+    const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
+    for (int c = c0; c < LK_JT_H * (LK_JT_W / 16); c += step) {
+        const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
+        const U32x4A4 v = *(const VO_GLOBAL U32x4A4 *)(tb + (uint32_t)(row * jstride + 16 * col));
+        *reinterpret_cast<uint4 *>(&tile[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
+    }
+    return LkOrigin{jx0, jy0};
+}
+// the one-feature kernels: the origin of a tile that covers the window of corner (inx, iny) -- the wave's own if it does, else a
+// new one, fetched between two barriers
+__device__ __forceinline__ LkOrigin lk_tile_cover(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
+                                              int inx, int iny, int lane, bool have_tile, int jx0, int jy0)
+{
+    if (!lk_tile_misses(have_tile, jx0, jy0, inx, iny))
+        return LkOrigin{jx0, jy0};
+    __syncthreads(); // single-wave workgroup: orders the LDS reads before the refill
+    const LkOrigin o = lk_tile_refill(tile, Jimg, jstride, jx_max, jy_max, inx, iny, lane, 64);
+    __syncthreads();
+    return o;
+}
+// the pixel pairs of a lane's row segment in the cell at tile offset `off`, upper and lower row: two unaligned 8-byte LDS reads
+// (gfx950 handles misaligned ds_read_b64; measured equal to three aligned dwords + v_alignbyte_b32 per row, profiles/r01 notes)
+// and the 14 v_perm_b32 of lift7
+__device__ __forceinline__ void lk_cell_rows(const uint8_t *tile, int off, uint32_t Jt[7], uint32_t Jb[7])
+{
+    const U32x2A1 t = *reinterpret_cast<const U32x2A1 *>(&tile[off]);
+    const U32x2A1 u = *reinterpret_cast<const U32x2A1 *>(&tile[off + LK_JT_W]);
+    lift7(t.a, t.b, Jt);
+    lift7(u.a, u.b, Jb);
 }
 
 // 7 waves per SIMD = at most 72 VGPRs.  Round 1 had the bound at 6 waves and the allocator happened to land on 70
@@ -205,16 +238,16 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                 // lane 63 owns no pixel: it reads its Scharr samples from the (all-zero) top-left border
                 // corner, so Ix = Iy = 0 there and every sum it feeds is 0 without any select
                 const uint32_t od = live ? 4u * o : 0u, drow = 4u * (uint32_t)istride;
-                const LkU2 t = *(const VO_GLOBAL LkU2 *)(Ib + o);
-                const LkU2 u = *(const VO_GLOBAL LkU2 *)(Ib + (o + (uint32_t)istride));
-                const LkU4 dt0 = *(const VO_GLOBAL LkU4 *)(Db + od);
-                const LkU4 dt1 = *(const VO_GLOBAL LkU4 *)(Db + (od + 16u));
-                const LkU4 db0 = *(const VO_GLOBAL LkU4 *)(Db + (od + drow));
-                const LkU4 db1 = *(const VO_GLOBAL LkU4 *)(Db + (od + drow + 16u));
+                const U32x2A1 t = *(const VO_GLOBAL U32x2A1 *)(Ib + o);
+                const U32x2A1 u = *(const VO_GLOBAL U32x2A1 *)(Ib + (o + (uint32_t)istride));
+                const U32x4A4 dt0 = *(const VO_GLOBAL U32x4A4 *)(Db + od);
+                const U32x4A4 dt1 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + 16u));
+                const U32x4A4 db0 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + drow));
+                const U32x4A4 db1 = *(const VO_GLOBAL U32x4A4 *)(Db + (od + drow + 16u));
                 const uint32_t dt[8] = {dt0.a, dt0.b, dt0.c, dt0.d, dt1.a, dt1.b, dt1.c, dt1.d};
                 const uint32_t db[8] = {db0.a, db0.b, db0.c, db0.d, db1.a, db1.b, db1.c, db1.d};
                 uint32_t Ip[4];
-                bilinear7_u8(t.lo, t.hi, u.lo, u.hi, wt, wb, Ip);
+                bilinear7_u8(t.a, t.b, u.a, u.b, wt, wb, Ip);
                 bilinear7_deriv(dt, db, wt, wb, Ixp, Iyp);
                 a11 = sdot2_first(Ixp[0], Ixp[0], 0);
                 a12 = sdot2_first(Ixp[0], Iyp[0], 0);
@@ -297,33 +330,14 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                         st = 0;
                     break;
                 }
-                // search tile must cover cols inx..inx+21, rows iny..iny+21
-                if (!have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 ||
-                    iny + LK_WIN + 1 > jy0 + LK_JT_H) {
-                    jx0 = (inx - 12) & ~3;
-                    jy0 = iny - 9;
-                    jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
-                    jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
-                    __syncthreads(); // single-wave workgroup: orders the LDS reads before the refill
-                    const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
-                    for (int c = lane; c < LK_JT_H * (LK_JT_W / 16); c += 64) {
-                        const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
-                        const LkU4 v = *(const VO_GLOBAL LkU4 *)(tb + (uint32_t)(row * jstride + 16 * col));
-                        *reinterpret_cast<uint4 *>(&s_jt[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
-                    }
-                    __syncthreads();
+                {
+                    const LkOrigin o = lk_tile_cover(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
+                    jx0 = o.x;
+                    jy0 = o.y;
                     have_tile = true;
                 }
                 uint32_t Jt[7], Jb[7]; // the cell's pixel pairs (two window rows per lane)
-                {
-                    const int off = (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off; // uniform part on the scalar unit
-                    // two unaligned 8-byte LDS reads (gfx950 handles misaligned ds_read_b64; measured
-                    // equal to three aligned dwords + v_alignbyte_b32 per row, profiles/r01 notes)
-                    const LkU2 t = *reinterpret_cast<const LkU2 *>(&s_jt[off]);
-                    const LkU2 u = *reinterpret_cast<const LkU2 *>(&s_jt[off + LK_JT_W]);
-                    lift7(t.lo, t.hi, Jt);
-                    lift7(u.lo, u.hi, Jb);
-                }
+                lk_cell_rows(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jt, Jb); // uniform part on the scalar unit
                 // fractional position of the window corner inside its pixel cell: the bilinear weights come from it, and
                 // the corner is still inside the cell exactly as long as both parts are in [0, 1).  fl(nextX - fnx) is what
                 // OpenCV itself computes (nextPt.x - inextPt.x); a true difference >= 1 or < 0 can never round into [0, 1),
@@ -408,26 +422,11 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                         const float ex = outX - halfWin, ey = outY - halfWin;
                         const float fex = floorf(ex), fey = floorf(ey);
                         const int inx = uni(fx), iny = uni(fy); // (admitted just above: inside [-21, jw) x [-21, jh))
-                        if (!have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 || iny + LK_WIN + 1 > jy0 + LK_JT_H) {
-                            jx0 = (inx - 12) & ~3;
-                            jy0 = iny - 9;
-                            jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
-                            jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
-                            __syncthreads();
-                            const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
-                            for (int c = lane; c < LK_JT_H * (LK_JT_W / 16); c += 64) {
-                                const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
-                                const LkU4 v = *(const VO_GLOBAL LkU4 *)(tb + (uint32_t)(row * jstride + 16 * col));
-                                *reinterpret_cast<uint4 *>(&s_jt[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
-                            }
-                            __syncthreads();
-                        }
+                        const LkOrigin o = lk_tile_cover(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
+                        jx0 = o.x;
+                        jy0 = o.y;
                         uint32_t Jt[7], Jb[7], Jp[4];
-                        const int off = (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off;
-                        const LkU2 t = *reinterpret_cast<const LkU2 *>(&s_jt[off]);
-                        const LkU2 u = *reinterpret_cast<const LkU2 *>(&s_jt[off + LK_JT_W]);
-                        lift7(t.lo, t.hi, Jt);
-                        lift7(u.lo, u.hi, Jb);
+                        lk_cell_rows(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jt, Jb);
                         lk_weights(ex - fex, ey - fey, wt, wb);
                         blend7(Jt, Jb, wt, wb, Jp);
                         uint32_t e = 0; // lane 63 duplicates lane 62's pixels: it contributes nothing
@@ -509,16 +508,27 @@ __global__ VO_LK_FLOW_ATTRS void lk_flow_kernel(const PyrImage *__restrict__ img
 }
 
 #ifndef VO_HOST_EMUL
+// The launch geometry of the block numbering above: frames per group of 8 XCDs (the largest power of two <= min(8, n_frames)),
+// work items -- features, or the pair kernel's pairs of features (dev/lk_dev.hip) -- per part of a frame's list, and the grid.
+struct LkGrid {
+    int fpg, ppp;
+    dim3 grid;
+};
+static LkGrid lk_grid(int n_frames, int n_items)
+{
+    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
+    const int parts = 8 / fpg, ppp = (n_items + parts - 1) / parts;
+    const int groups = (n_frames + fpg - 1) / fpg;
+    return {fpg, ppp, dim3((unsigned)(8 * groups * ppp))};
+}
+
 void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
 {
     if (max_pts <= 0 || n_frames <= 0)
         return;
-    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
-    const int parts = 8 / fpg, ppp = (max_pts + parts - 1) / parts;
-    const int groups = (n_frames + fpg - 1) / fpg;
-    dim3 grid((unsigned)(8 * groups * ppp));
-    hipLaunchKernelGGL(lk_flow_kernel, grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, fpg, ppp, d_next,
+    const LkGrid g = lk_grid(n_frames, max_pts);
+    hipLaunchKernelGGL(lk_flow_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp, d_next,
                        d_status, d_err, prm);
 }
 
@@ -528,13 +538,9 @@ void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float
 {
     if (max_pts <= 0 || n_frames <= 0)
         return;
-    // frames per group of 8 XCDs: largest power of two <= min(8, n_frames)
-    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
-    const int parts = 8 / fpg, ppp = (max_pts + parts - 1) / parts;
-    const int groups = (n_frames + fpg - 1) / fpg;
-    dim3 grid((unsigned)(8 * groups * ppp));
-    hipLaunchKernelGGL(lk_circular_kernel, grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
-                       fpg, ppp, d_trk, d_status, prm);
+    const LkGrid g = lk_grid(n_frames, max_pts);
+    hipLaunchKernelGGL(lk_circular_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
+                       g.fpg, g.ppp, d_trk, d_status, prm);
 }
 
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
@@ -543,11 +549,8 @@ void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d
 {
     if (max_pts <= 0 || n_frames <= 0 || hop_begin < 0 || hop_end > 4 || hop_begin >= hop_end)
         return;
-    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
-    const int parts = 8 / fpg, ppp = (max_pts + parts - 1) / parts;
-    const int groups = (n_frames + fpg - 1) / fpg;
-    dim3 grid((unsigned)(8 * groups * ppp));
-    hipLaunchKernelGGL(lk_hops_kernel, grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames, fpg, ppp,
+    const LkGrid g = lk_grid(n_frames, max_pts);
+    hipLaunchKernelGGL(lk_hops_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
                        d_trk, d_status, prm, hop_begin, hop_end);
 }
 

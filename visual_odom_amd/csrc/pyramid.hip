@@ -16,13 +16,6 @@
 
 namespace vo {
 
-struct __attribute__((packed, aligned(4))) U32x4 {
-    uint32_t a, b, c, d;
-};
-struct __attribute__((packed, aligned(1))) U8x16 { // 16 bytes at any address
-    uint32_t a, b, c, d;
-};
-
 // ---------------------------------------------------------------------------------------------------
 // FUSED PYRAMID PASS (round 4).  One pass over a level reads it ONCE and emits everything that depends on it: its Scharr
 // image, the next level (pyrDown) and its own REFLECT_101 border -- the three kernels of round 3 (dev/pyramid_dev.hip) each fetched level 0 from memory
@@ -55,9 +48,6 @@ struct PassPlan {
     int wide;                  // border work items: 1 = four rows / all side chunks of a row per lane, 0 = one 16-byte chunk per lane
     uint64_t m_img[VO_MAX_LEVELS], m_row[VO_MAX_LEVELS]; // floor(2^64 / (nci gy)) + 1, floor(2^64 / nci) + 1: id -> (image, y, x) by
                                                          // multiply-high, exact for every 32-bit id (pass_div)
-};
-struct __attribute__((packed, aligned(2))) LkU2x { // an 8-byte row window at an even column
-    uint32_t lo, hi;
 };
 
 // Border work items of the fused pass (round 5): a lane takes one 16-byte chunk column of FOUR rows above / below the image
@@ -159,13 +149,13 @@ __device__ __forceinline__ void border_chunk(VO_GLOBAL uint8_t *__restrict__ p, 
     uint32_t v[4];
     const int xm = x0 + 15 < 0 ? -(x0 + 15) : x0 >= w ? 2 * (w - 1) - (x0 + 15) : -1; // first column of the mirrored run
     if (x0 >= 0 && x0 + 15 < w) {
-        const U32x4 t = *(const VO_GLOBAL U32x4 *)(src + x0);
+        const U32x4A4 t = *(const VO_GLOBAL U32x4A4 *)(src + x0);
         v[0] = t.a;
         v[1] = t.b;
         v[2] = t.c;
         v[3] = t.d;
     } else if (xm >= 0 && xm + 15 < w) {
-        const U8x16 t = *(const VO_GLOBAL U8x16 *)(src + xm); // columns xm .. xm + 15 = the chunk's columns in reverse order
+        const U32x4A1 t = *(const VO_GLOBAL U32x4A1 *)(src + xm); // columns xm .. xm + 15 = the chunk's columns in reverse order
         v[0] = perm_b32(0, t.d, 0x00010203u);
         v[1] = perm_b32(0, t.c, 0x00010203u);
         v[2] = perm_b32(0, t.b, 0x00010203u);
@@ -178,8 +168,8 @@ __device__ __forceinline__ void border_chunk(VO_GLOBAL uint8_t *__restrict__ p, 
         // this one chunk made the lane that owns a row's side chunks the slowest of its wavefront: KITTI level 2 43 us against
         // 26 without any border work, gpurun_out/r5_14.)
         const int k = w - x0; // 1 .. 15
-        const U32x4 a = *(const VO_GLOBAL U32x4 *)(src + x0);
-        const U8x16 t = *(const VO_GLOBAL U8x16 *)(src + (2 * (w - 1) - (x0 + 15)));
+        const U32x4A4 a = *(const VO_GLOBAL U32x4A4 *)(src + x0);
+        const U32x4A1 t = *(const VO_GLOBAL U32x4A1 *)(src + (2 * (w - 1) - (x0 + 15)));
         const uint32_t img[4] = {a.a, a.b, a.c, a.d};
         const uint32_t rev[4] = {perm_b32(0, t.d, 0x00010203u), perm_b32(0, t.c, 0x00010203u), perm_b32(0, t.b, 0x00010203u),
                                  perm_b32(0, t.a, 0x00010203u)};
@@ -326,9 +316,9 @@ __device__ __forceinline__ void pass_item(const PyrImage &im, int level, int g, 
         }
 #pragma unroll
         for (int r = 0; r < PF_ROWS + 3; r++) {
-            const LkU2x v = *(const VO_GLOBAL LkU2x *)(rows[r] + (uint32_t)x4 - 2);
-            W0[r] = v.lo;
-            W1[r] = v.hi;
+            const U32x2A2 v = *(const VO_GLOBAL U32x2A2 *)(rows[r] + (uint32_t)x4 - 2);
+            W0[r] = v.a;
+            W1[r] = v.b;
         }
         // group 0 (in the first wavefront of a row block): its window starts two bytes left of the row -- memory of the
         // level's border, which this launch is also writing; the two bytes are replaced here, whatever they hold: columns -2,
@@ -353,9 +343,9 @@ __device__ __forceinline__ void pass_item(const PyrImage &im, int level, int g, 
 #pragma unroll
         for (int r = 0; r < PF_ROWS + 3; r++) {
             const VO_GLOBAL uint8_t *__restrict__ row = src + (ptrdiff_t)reflect101(y0 - 2 + r, h) * stride;
-            const LkU2x v = *(const VO_GLOBAL LkU2x *)(row + xs);
-            W0[r] = perm_b32(v.hi, v.lo, sel[0]);
-            W1[r] = perm_b32(v.hi, v.lo, sel[1]);
+            const U32x2A2 v = *(const VO_GLOBAL U32x2A2 *)(row + xs);
+            W0[r] = perm_b32(v.b, v.a, sel[0]);
+            W1[r] = perm_b32(v.b, v.a, sel[1]);
         }
     }
 #pragma unroll

@@ -21,9 +21,7 @@
 
 namespace vo {
 
-struct __attribute__((packed, aligned(4))) RectM4 { // four packed map entries: dword-aligned (w need not be a multiple of 4)
-    uint32_t m[4];
-};
+// the two bytes of a tap pair and the four destination bytes of a lane, at any address
 struct __attribute__((packed, aligned(1))) RectB2 {
     uint16_t v;
 };
@@ -46,11 +44,13 @@ __global__ __launch_bounds__(64) void rectify_kernel(const RectImage *__restrict
             continue;
         x = x < w - 4 ? x : w - 4; // the lane that would cross the row end makes the row's last 4 pixels again
         const VO_GLOBAL uint32_t *__restrict__ mrow = (const VO_GLOBAL uint32_t *)maps + ((size_t)e.side * h + row) * w;
-        const RectM4 m4 = *reinterpret_cast<const VO_GLOBAL RectM4 *>(mrow + x);
+        // four packed map entries: dword-aligned (w need not be a multiple of 4)
+        const U32x4A4 m4 = *reinterpret_cast<const VO_GLOBAL U32x4A4 *>(mrow + x);
         const VO_GLOBAL uint8_t *__restrict__ s = (const VO_GLOBAL uint8_t *)e.raw;
         uint32_t out = 0;
         for (int j = 0; j < 4; j++) {
-            const RectTap t = rect_tap(m4.m[j], x + j, row, w, h);
+            const uint32_t m = j == 0 ? m4.a : j == 1 ? m4.b : j == 2 ? m4.c : m4.d; // (unrolled: no select is left)
+            const RectTap t = rect_tap(m, x + j, row, w, h);
             const VO_GLOBAL uint8_t *__restrict__ p = s + (ptrdiff_t)t.iy * raw_pitch + t.ix;
             const uint32_t r0 = reinterpret_cast<const VO_GLOBAL RectB2 *>(p)->v;
             const uint32_t r1 = reinterpret_cast<const VO_GLOBAL RectB2 *>(p + raw_pitch)->v;

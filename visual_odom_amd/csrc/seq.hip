@@ -104,10 +104,6 @@ __global__ __launch_bounds__(256) void seq_carry_kernel(const int *__restrict__ 
 // So: G single-wave workgroups walk over the rows, row r = blockIdx.x, + G, ...; G = 192 when any pair of the step comes
 // over PCIe, 8192 for a step of device-resident pairs (an HBM-to-HBM copy wants more loads in flight, they are short, and it
 // is over in a fraction of a millisecond).
-struct __attribute__((packed, aligned(1))) IngU2 {
-    uint32_t lo, hi;
-};
-
 __global__ __launch_bounds__(64) void seq_ingest_kernel(const SeqIngest *__restrict__ tab, int n_rows /* 2 * pairs * h */,
                                                         int n_waves /* = the grid */, int w, int h, int pitch,
                                                         uint8_t *__restrict__ pix0 /* pixel (0,0) of image 0 */, size_t img_bytes)
@@ -122,8 +118,8 @@ __global__ __launch_bounds__(64) void seq_ingest_kernel(const SeqIngest *__restr
             int x = x0 + (int)threadIdx.x * 8;
             if (x < w) {
                 x = x < last ? x : last;
-                const IngU2 v = *reinterpret_cast<const VO_GLOBAL IngU2 *>(s + (uint32_t)x);
-                *reinterpret_cast<VO_GLOBAL IngU2 *>(d + (uint32_t)x) = v;
+                const U32x2A1 v = *reinterpret_cast<const VO_GLOBAL U32x2A1 *>(s + (uint32_t)x);
+                *reinterpret_cast<VO_GLOBAL U32x2A1 *>(d + (uint32_t)x) = v;
             }
         }
     }

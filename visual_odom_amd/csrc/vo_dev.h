@@ -1,4 +1,5 @@
-// vo_dev.h -- device-side data layout shared by the HIP kernels and the C-ABI host code.
+// vo_dev.h -- device-side data layout shared by the HIP kernels and the C-ABI host code, the cross-lane primitives and the
+// packed word types of the kernels' unaligned vector accesses (U32x2A1 .. U32x4A4).
 //
 // HBM layout (see DESIGN.md "Data layout"):
 //   * image table: every 8-bit image owns its whole pyramid.  Level l is stored WITH a border, the
@@ -92,6 +93,22 @@ struct PyrImage {
 
 struct Quad {
     int l0, r0, l1, r1;
+};
+
+// Two and four dwords moved as ONE 8- or 16-byte access at less than their natural alignment (the A<n> of the name: what the
+// address is known to be a multiple of).  Rows of pixels start anywhere; the hardware takes unaligned vector accesses to
+// global memory and to LDS, and the packed struct is how the compiler is told that it may emit one.
+struct __attribute__((packed, aligned(1))) U32x2A1 {
+    uint32_t a, b;
+};
+struct __attribute__((packed, aligned(2))) U32x2A2 {
+    uint32_t a, b;
+};
+struct __attribute__((packed, aligned(1))) U32x4A1 {
+    uint32_t a, b, c, d;
+};
+struct __attribute__((packed, aligned(4))) U32x4A4 {
+    uint32_t a, b, c, d;
 };
 
 __device__ __forceinline__ int reflect101(int p, int len)

@@ -1,10 +1,14 @@
-// vo_kernels.h -- parameter / result records and launch wrappers shared by the kernel
-// translation units (pyramid.hip, lk.hip, post.hip, pnp.hip) and the C-ABI host code (capi.hip).
+// vo_kernels.h -- parameter / result records, launch wrappers and what the public header's constants mean to a kernel
+// (ingest_bpp), shared by the kernel translation units (csrc/*.hip) and the C-ABI host code (capi*.hip).
 #pragma once
 
+#include "../../include/vo_hip.h" // VO_FMT_*, VO_SEQ_ROW, VO_SEQ_F_*
 #include "vo_dev.h"
 
 namespace vo {
+
+// vo_params.input_format (VO_FMT_*): source bytes per pixel -- the minimum byte stride of an image is w * ingest_bpp
+constexpr int ingest_bpp(int fmt) { return fmt == VO_FMT_GRAY8 ? 1 : fmt == VO_FMT_GRAY8_X2 ? 2 : fmt <= VO_FMT_RGB8 ? 3 : 4; }
 
 struct LkParams {
     int max_level;   // 3 in the reference (feature.cpp:136) -> 4 pyramid levels
@@ -93,14 +97,6 @@ struct RectImage {
     const uint8_t *raw;
     int image, side;
 };
-#ifndef VO_SEQ_ROW // also in include/vo_hip.h (public)
-#define VO_SEQ_ROW 27 // doubles per trajectory row: frame_pose 3x4, rvec, tvec, rotation 3x3
-#define VO_SEQ_F_ACTIVE 1
-#define VO_SEQ_F_INTEGRATED 2
-#define VO_SEQ_F_TOO_FEW 4
-#define VO_SEQ_F_NO_ESSENTIAL 8
-#define VO_SEQ_F_GAP 16
-#endif
 
 // workspace of the four-kernel EPnP used for small launches (pnp.hip): VO_EPNP_WS_DOUBLES doubles per hypothesis of the first
 // RANSAC chunk (VO_EPNP_WS_HYPS hypotheses per frame), allocated for up to VO_EPNP_WS_MAX_FRAMES frames

@@ -1,4 +1,5 @@
-// vo_lkmath.h -- packed integer pixel arithmetic of the Lucas-Kanade kernel (lk.hip).
+// vo_lkmath.h -- packed integer pixel arithmetic of the Lucas-Kanade kernels (lk.hip): the composites over the instruction
+// wrappers of vo_isa.h.
 //
 // OpenCV's LKTrackerInvoker (the arithmetic behind the reference's cv::calcOpticalFlowPyrLK calls,
 // feature.cpp:136-139) samples 21 x 21 windows with 14-bit fixed-point bilinear weights:
@@ -16,164 +17,13 @@
 //     and b1 += diff*Ix, b2 += diff*Iy are one v_dot2_i32_i16 each per pixel pair.
 // Every step is exact integer arithmetic, so the result is bit-identical to the scalar formula.  The
 // host build of this header (tests/test_device_math_on_host.py) shows that for the `#else` text of the
-// wrappers below; tests/test_gpu_device_units.py runs the instructions themselves on gfx950, every
+// wrappers (vo_isa.h); tests/test_gpu_device_units.py runs the instructions themselves on gfx950, every
 // wrapper and every composite, against that host text and the plain restatement.
 #pragma once
 
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
-#include <hip/hip_runtime.h>
-#define VO_HD __host__ __device__ __forceinline__
-#else
-#define VO_HD static inline
-#endif
+#include "vo_isa.h" // the instruction wrappers (device: the CDNA4 instruction; host: its definition) and VO_HD
 
 namespace vo {
-
-// ---- instruction wrappers (device: the CDNA4 instruction; host: its definition) -------------------
-// v_perm_b32: result byte i = byte sel[i] of the 8-byte value {hi:lo} (0..3 -> lo, 4..7 -> hi), 0x0c -> 0
-VO_HD uint32_t perm_b32(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_perm(hi, lo, sel);
-#else
-    uint64_t v = ((uint64_t)hi << 32) | lo;
-    uint32_t out = 0;
-    for (int i = 0; i < 4; i++) {
-        uint32_t s = (sel >> (8 * i)) & 0xff;
-        uint32_t b = s <= 7 ? (uint32_t)((v >> (8 * s)) & 0xff) : 0u; // only selectors 0..7 and 0x0c are used
-        out |= b << (8 * i);
-    }
-    return out;
-#endif
-}
-
-// v_dot2_u32_u16: a.lo*b.lo + a.hi*b.hi + c (unsigned 16-bit lanes)
-VO_HD uint32_t udot2(uint32_t a, uint32_t b, uint32_t c)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b), c, false);
-#else
-    return (a & 0xffff) * (b & 0xffff) + (a >> 16) * (b >> 16) + c;
-#endif
-}
-
-// v_dot2_i32_i16: signed 16-bit lanes
-VO_HD int32_t sdot2(uint32_t a, uint32_t b, int32_t c)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef short i16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b), c, false);
-#else
-    return (int32_t)(int16_t)(a & 0xffff) * (int16_t)(b & 0xffff) + (int32_t)(int16_t)(a >> 16) * (int16_t)(b >> 16) + c;
-#endif
-}
-
-// The same dot product as the first link of an accumulation chain.  v_dot2c_i32_i16 (what the compiler picks for
-// sdot2) accumulates in place, so a chain that starts from a constant or from a value that must survive costs a
-// v_mov per chain; the clamped variant only exists in the three-address VOP3P form, which takes the start value
-// from any operand.  No chain here gets anywhere near the int32 range, so the clamp never acts.
-VO_HD int32_t sdot2_first(uint32_t a, uint32_t b, int32_t c)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef short i16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(i16x2, a), __builtin_bit_cast(i16x2, b), c, true);
-#else
-    return sdot2(a, b, c);
-#endif
-}
-
-// v_pk_sub_i16 (wrapping) and v_pk_lshrrev_b16 by 1
-VO_HD uint32_t pk_sub_i16(uint32_t a, uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef short i16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, (i16x2)(__builtin_bit_cast(i16x2, a) - __builtin_bit_cast(i16x2, b)));
-#else
-    return (((a & 0xffff) - (b & 0xffff)) & 0xffff) | (((a >> 16) - (b >> 16)) << 16);
-#endif
-}
-
-VO_HD uint32_t pk_lshr1_u16(uint32_t a)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) >> (unsigned short)1));
-#else
-    return (a >> 1) & 0x7fff7fffu;
-#endif
-}
-
-// v_dot4_u32_u8: sum of the four unsigned byte products + c
-VO_HD uint32_t udot4(uint32_t a, uint32_t b, uint32_t c)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_udot4(a, b, c, false);
-#else
-    uint32_t r = c;
-    for (int i = 0; i < 4; i++)
-        r += ((a >> (8 * i)) & 0xff) * ((b >> (8 * i)) & 0xff);
-    return r;
-#endif
-}
-
-// packed 16-bit lanes, wrapping: v_pk_add_u16, v_pk_mul_lo_u16, v_pk_mad_u16 (the low 16 bits of a product or sum do
-// not depend on signedness, so the same instructions serve int16 lanes)
-VO_HD uint32_t pk_add_u16(uint32_t a, uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)));
-#else
-    return (((a & 0xffff) + (b & 0xffff)) & 0xffff) | (((a >> 16) + (b >> 16)) << 16);
-#endif
-}
-
-// v_pk_sub_u16 clamp (saturating at 0) and v_pk_min_u16
-VO_HD uint32_t pk_subsat_u16(uint32_t a, uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-#else
-    const uint32_t al = a & 0xffff, bl = b & 0xffff, ah = a >> 16, bh = b >> 16;
-    return (al > bl ? al - bl : 0) | (ah > bh ? ah - bh : 0) << 16;
-#endif
-}
-
-VO_HD uint32_t pk_min_u16(uint32_t a, uint32_t b)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
-#else
-    const uint32_t al = a & 0xffff, bl = b & 0xffff, ah = a >> 16, bh = b >> 16;
-    return (al < bl ? al : bl) | (ah < bh ? ah : bh) << 16;
-#endif
-}
-
-VO_HD uint32_t pk_mad_u16(uint32_t a, uint32_t k /* both lanes */, uint32_t c)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    const u16x2 kk = {(unsigned short)k, (unsigned short)k};
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) * kk + __builtin_bit_cast(u16x2, c)));
-#else
-    return (((a & 0xffff) * k + (c & 0xffff)) & 0xffff) | ((((a >> 16) * k + (c >> 16)) & 0xffff) << 16);
-#endif
-}
-
-// v_alignbyte_b32 / v_alignbit_b32: the 8-byte value {hi:lo} shifted right by `bytes` bytes, low dword
-VO_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t bytes /* 0..3 */)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_alignbyte(hi, lo, bytes);
-#else
-    return (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * bytes));
-#endif
-}
 
 // ---- selectors ------------------------------------------------------------------------------------
 // bytes k and k+1 of the 8 loaded bytes into the high byte of the two u16 lanes (256*p[k], 256*p[k+1])

@@ -27,6 +27,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "vo_isa.h" // udot4
+
 #if !defined(__HIPCC__) && !defined(__host__)
 #define __host__
 #define __device__
@@ -72,18 +74,6 @@ inline bool rect_pack(float mx, float my, int x, int y, int w, int h, uint32_t *
     return true;
 }
 
-// v_dot4_u32_u8: a.b0 * b.b0 + a.b1 * b.b1 + a.b2 * b.b2 + a.b3 * b.b3 + c
-__host__ __device__ inline uint32_t rect_dot4(uint32_t a, uint32_t b, uint32_t c)
-{
-#if defined(VO_HOST_EMUL) || !defined(__HIP_DEVICE_COMPILE__)
-    for (int k = 0; k < 4; k++)
-        c += ((a >> (8 * k)) & 0xff) * ((b >> (8 * k)) & 0xff);
-    return c;
-#else
-    return __builtin_amdgcn_udot4(a, b, c, false);
-#endif
-}
-
 // where the taps of a packed entry lie and how they are weighted: the entry of destination pixel (x, y)
 struct RectTap {
     int ix, iy;    // top-left tap, clamped to [-2, w] x [-2, h]
@@ -103,10 +93,10 @@ __host__ __device__ inline RectTap rect_tap(uint32_t m, int x, int y, int w, int
     return t;
 }
 // row0 / row1: the two bytes at (iy, ix), (iy, ix + 1) and at (iy + 1, ix), (iy + 1, ix + 1) as the low halves of a dword.
-// Horizontal first: h0, h1 <= 32 * 255 = 8160; the sum <= 32 * 8160 + 512.
+// Horizontal first (v_dot4_u32_u8): h0, h1 <= 32 * 255 = 8160; the sum <= 32 * 8160 + 512.
 __host__ __device__ inline uint32_t rect_blend(uint32_t row0, uint32_t row1, uint32_t wx, uint32_t b)
 {
-    const uint32_t h0 = rect_dot4(row0, wx, 0u), h1 = rect_dot4(row1, wx, 0u);
+    const uint32_t h0 = udot4(row0, wx, 0u), h1 = udot4(row1, wx, 0u);
     return (h0 * (32u - b) + h1 * b + 512u) >> 10;
 }
 
