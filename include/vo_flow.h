@@ -11,7 +11,8 @@
  * Everything of vo_hip.h holds here: the same vo_ctx (one per host thread per GPU), the same VO_OK / VO_ERR_* codes with
  * vo_last_error(), points as interleaved float32 (x, y), caller-allocated outputs, no exceptions.  Images are read as
  * vo_params.input_format says (byte stride, sub-views as everywhere).  The LK parameters are the context's vo_params:
- * lk_max_level, lk_max_count, lk_epsilon, lk_min_eig_threshold; the window is 21 x 21.
+ * lk_max_level, lk_max_count, lk_epsilon, lk_min_eig_threshold; the window is 21 x 21 (vo_flow_win.h: the same calls with a
+ * window of 5 x 5 .. 21 x 21).
  *
  * RESULTS, bit for bit those of OpenCV's CPU tracker with an err vector requested: next_pts, status (1 tracked, 0 not) and
  *   err = sum over the 21 x 21 window of |J(final position) - I| / (32 * 21 * 21)      (flags 0: the L1 residual per pixel)

@@ -9,7 +9,11 @@
   latency     one synchronous voflow_track (two uploads, two pyramids, one hop, one gather) next to vo_circular_match on four
               images (four uploads, four pyramids, four hops, filter, gather): median and min of `--calls` calls each.
 
-    python tools/flow_bench.py [--pairs 256] [--runs 20] [--repeats 5] [--calls 200] [--json out.json]
+  --win W ...  adds one throughput leg per window: vowin_batch_run(W) (include/vo_flow_win.h) on the same table, alternating with
+              the others.  W = 21 there is voflow_batch_run's kernel through the other entry point: the two legs are to agree
+              within the spread of `flow`.  With --win the latency part also times vowin_track for each window.
+
+    python tools/flow_bench.py [--pairs 256] [--runs 20] [--repeats 5] [--calls 200] [--win 7 15 21] [--json out.json]
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--frames", type=int, default=4, help="distinct rendered frames the pairs walk over")
+    ap.add_argument("--win", type=int, nargs="*", default=[], help="windows to time through vowin_batch_run / vowin_track")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     from visual_odom_amd import _lib, synth
@@ -63,6 +68,8 @@ def main():
         ctx.batch_run(_lib.STAGE_LK)
 
     legs = dict(flow=leg_flow, chain4=leg_chain)
+    for win in args.win:
+        legs["win%d" % win] = lambda win=win: ctx.flow_batch_run(win=win)
     runs = {k: [] for k in legs}
     for rep in range(args.repeats + 1):   # (repeat 0 is the warm-up and is not kept)
         for name, fn in legs.items():
@@ -100,7 +107,9 @@ def main():
     def call_circ():
         ctx.circular_match(L[0], R[0], L[1], R[1], pts[0])
 
-    for name, fn in (("voflow_track", call_flow), ("voflow_track_no_err", call_flow_noerr), ("vo_circular_match", call_circ)):
+    calls = [("voflow_track", call_flow), ("voflow_track_no_err", call_flow_noerr), ("vo_circular_match", call_circ)]
+    calls += [("vowin_track_%d" % win, lambda win=win: ctx.flow_track(L[0], L[1], pts[0], win=win)) for win in args.win]
+    for name, fn in calls:
         for _ in range(20):
             fn()
         t = []

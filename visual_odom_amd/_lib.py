@@ -42,6 +42,8 @@ EXPORTS = (
 )
 # every symbol include/vo_flow.h declares: the two-image tracker, exported by the same library beside the ABI above
 FLOW_EXPORTS = ("voflow_track", "voflow_feature_tracking", "voflow_batch_set_pairs", "voflow_batch_run", "voflow_batch_get")
+# every symbol include/vo_flow_win.h declares: the same tracker with a window of 5 x 5 .. 21 x 21
+WIN_EXPORTS = ("vowin_track", "vowin_feature_tracking", "vowin_batch_run", "vowin_max_level")
 
 
 class _VoParamsLayout(C.Structure):
@@ -135,7 +137,11 @@ def load():
     lib.voflow_batch_set_pairs.argtypes = [vp, vp, i]
     lib.voflow_batch_run.argtypes = [vp]
     lib.voflow_batch_get.argtypes = [vp, i, vp, vp, vp, i]
-    for name in FLOW_EXPORTS:
+    lib.vowin_track.argtypes = [vp, vp, vp, i, i, i, vp, i, i, vp, vp, vp]
+    lib.vowin_feature_tracking.argtypes = [vp, vp, vp, i, i, i, vp, i, i, vp, vp, vp, vp, vp]
+    lib.vowin_batch_run.argtypes = [vp, i]
+    lib.vowin_max_level.argtypes = [vp, i, i, vp]
+    for name in FLOW_EXPORTS + WIN_EXPORTS:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -362,9 +368,10 @@ class Context:
                     keep_idx=keep[:m].copy(), n_out=m)
 
     # ---- two-image tracker (include/vo_flow.h) ------------------------------------------------
-    def flow_track(self, prev, nxt, pts, want_err=True):
+    def flow_track(self, prev, nxt, pts, want_err=True, win=None):
         """cv::calcOpticalFlowPyrLK(prev, nxt, pts, ...) with the context's LK parameters: (next [n, 2], status [n], err [n] or
-        None).  Afterwards the context holds no kept pair."""
+        None).  Afterwards the context holds no kept pair.  win: None = voflow_track (21 x 21), a number = vowin_track with that
+        window (include/vo_flow_win.h: odd, 5 .. 21, on the levels flow_max_level gives)."""
         imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
         h, w = imgs[0].shape[:2]
         self._kept_shape = (0, 0)
@@ -372,12 +379,16 @@ class Context:
         n = pts.shape[0]
         out, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
         err = np.zeros(max(n, 1), np.float32) if want_err else None
-        self._chk(self.lib.voflow_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, _p(out), _p(st), _pn(err)))
+        if win is None:
+            self._chk(self.lib.voflow_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, _p(out), _p(st), _pn(err)))
+        else:
+            self._chk(self.lib.vowin_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, int(win), _p(out), _p(st), _pn(err)))
         return out[:n], st[:n], (err[:n] if want_err else None)
 
-    def feature_tracking(self, prev, nxt, pts, want_err=True):
+    def feature_tracking(self, prev, nxt, pts, want_err=True, win=None):
         """the reference's featureTracking() (feature.cpp:64-74): calcOpticalFlowPyrLK + deleteUnmatchFeatures.  dict(points0,
-        points1: the survivors [n_out, 2]; status [n]: as the reference leaves it; err [n] or None; keep_idx [n_out]; n_out)"""
+        points1: the survivors [n_out, 2]; status [n]: as the reference leaves it; err [n] or None; keep_idx [n_out]; n_out).
+        win: as in flow_track (a number = vowin_feature_tracking)"""
         imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
         h, w = imgs[0].shape[:2]
         self._kept_shape = (0, 0)
@@ -388,8 +399,12 @@ class Context:
         p1, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
         err = np.zeros(max(n, 1), np.float32) if want_err else None
         keep, n_out = np.zeros(max(n, 1), np.int32), C.c_int(0)
-        self._chk(self.lib.voflow_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, _p(p1), _p(st), _pn(err),
-                                                   _p(keep), C.addressof(n_out)))
+        if win is None:
+            self._chk(self.lib.voflow_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, _p(p1), _p(st), _pn(err),
+                                                       _p(keep), C.addressof(n_out)))
+        else:
+            self._chk(self.lib.vowin_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, int(win), _p(p1), _p(st),
+                                                      _pn(err), _p(keep), C.addressof(n_out)))
         m = n_out.value
         return dict(points0=p0[:m].copy(), points1=p1[:m].copy(), status=st[:n], err=err[:n] if want_err else None,
                     keep_idx=keep[:m].copy(), n_out=m)
@@ -399,9 +414,16 @@ class Context:
         q = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         self._chk(self.lib.voflow_batch_set_pairs(self.h, _p(q), q.shape[0]))
 
-    def flow_batch_run(self):
-        """one hop per frame over the pairs, asynchronous on the context's stream"""
-        self._chk(self.lib.voflow_batch_run(self.h))
+    def flow_batch_run(self, win=None):
+        """one hop per frame over the pairs, asynchronous on the context's stream (win: a number = vowin_batch_run)"""
+        self._chk(self.lib.voflow_batch_run(self.h) if win is None else self.lib.vowin_batch_run(self.h, int(win)))
+
+    def flow_max_level(self, w, h):
+        """the deepest pyramid level the context tracks on for a w x h image under its lk_max_level: the maxLevel of the OpenCV
+        call a windowed flow call equals (vowin_max_level)"""
+        e = C.c_int(-1)
+        self._chk(self.lib.vowin_max_level(self.h, int(w), int(h), C.addressof(e)))
+        return e.value
 
     def flow_batch_get(self, frame, n, want_err=True):
         """(next [n, 2], status [n], err [n] or None) of a frame of the last flow_batch_run"""

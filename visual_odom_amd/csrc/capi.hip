@@ -6,25 +6,23 @@
 namespace vo_capi {
 
 // pyramid geometry exactly as buildOpticalFlowPyramid: stop when the next level would not be
-// larger than the 21 x 21 window
+// larger than the 21 x 21 window (plan_depth)
 int plan_levels(vo_ctx *c, int w, int h)
 {
-    int cw = w, ch = h, l = 0;
+    const int levels = plan_depth(w, h, c->prm.lk_max_level) + 1;
+    int cw = w, ch = h;
     size_t off = 0;
-    for (;; l++) {
+    for (int l = 0; l < levels; l++) {
         c->lw[l] = cw;
         c->lh[l] = ch;
         c->lstride[l] = level_stride(cw);
         c->loff[l] = off;
         off += (size_t)c->lstride[l] * (ch + 2 * VO_BY);
         off = (off + 255) / 256 * 256;
-        int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-        if (l == c->prm.lk_max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
-            break;
-        cw = nw;
-        ch = nh;
+        cw = (cw + 1) / 2;
+        ch = (ch + 1) / 2;
     }
-    c->levels = l + 1;
+    c->levels = levels;
     c->img_bytes = off;
     return 0;
 }

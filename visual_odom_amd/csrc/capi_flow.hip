@@ -3,8 +3,10 @@
 // (prev, next) pair with the err output (lk.hip: lk_flow_kernel), deleteUnmatchFeatures on the device (post.hip:
 // flow_compact_kernel).  Its device memory comes from the context's Owner at the first voflow_* call: a context that never makes
 // one allocates and launches what it always did.
+// The calls of include/vo_flow_win.h (vowin_*) are the same host code with a window: every call below takes `win`, voflow_* pass
+// 21 (lk_flow_kernel), vowin_* the caller's (lk_flow_win_kernel<win>, refused before anything is launched if there is none).
 #include "capi_internal.h"
-#include "../../include/vo_flow.h"
+#include "../../include/vo_flow_win.h"
 
 namespace {
 
@@ -41,7 +43,7 @@ int ensure_flow(vo_ctx *c)
 // Both synchronous calls: two uploads through the pull path (the points ride with the second), two pyramids, one hop, with
 // `compact` deleteUnmatchFeatures, one gather into the host-visible result buffer, one synchronisation.
 int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, const float *pts, int n,
-                   bool want_err, bool compact)
+                   int win, bool want_err, bool compact)
 {
     if (c->seq.on)
         return fail(c, VO_ERR_STATE, (std::string(who) + " inside the sequence loop (vo_seq_*)").c_str());
@@ -81,8 +83,8 @@ int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_
     hipStream_t st = c->sel->stream;
     launch_pyramid_fused(c->d_imgs, slot1 + 1, c->levels, c->lw, c->lh, c->lstride, st); // (slot 1 of a rectifying context: rebuilt as it is)
     std::fill(c->img_stale.begin(), c->img_stale.begin() + slot1 + 1, (uint8_t)0);
-    launch_lk_flow(c->d_imgs, fl.d_pairs + c->max_frames + k, c->d_pts, c->d_npts, c->cap, n, 1, fl.d_next, fl.d_status,
-                   want_err ? fl.d_err : nullptr, lk_params(c), st);
+    launch_lk_flow_win(win, c->d_imgs, fl.d_pairs + c->max_frames + k, c->d_pts, c->d_npts, c->cap, n, 1, fl.d_next, fl.d_status,
+                       want_err ? fl.d_err : nullptr, lk_params(c), st);
     if (compact)
         launch_flow_compact(c->d_pts, fl.d_next, fl.d_status, c->d_npts, c->cap, fl.d_out0, fl.d_out1, fl.d_idx, fl.d_nout, 1, st);
     FlowGather g;
@@ -102,20 +104,23 @@ int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_
     return VO_OK;
 }
 
-} // namespace
+// the windows with a kernel: odd, 5 .. 21 (vo_flow_win.h says why 23 and above are out) -- launch_lk_flow_win's precondition,
+// checked by every entry point before anything else happens
+bool win_ok(int win) { return win >= 5 && win <= 21 && (win & 1); }
+int bad_win(vo_ctx *c, const char *who) { return fail(c, VO_ERR_ARG, (std::string(who) + ": win is not an odd number of 5 .. 21").c_str()); }
 
-extern "C" {
-
-int voflow_track(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, const float *prev_pts_xy, int n,
-                 float *next_pts_xy, uint8_t *status, float *err)
+int track(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, const float *prev_pts_xy, int n,
+          int win, float *next_pts_xy, uint8_t *status, float *err)
 {
     if (!c)
         return VO_ERR_ARG;
     if (!prev || !next || n < 0 || (n > 0 && (!prev_pts_xy || !next_pts_xy || !status)))
-        return fail(c, VO_ERR_ARG, "voflow_track: null image / points / output, or n < 0");
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": null image / points / output, or n < 0").c_str());
+    if (!win_ok(win))
+        return bad_win(c, who);
     if (n == 0 && !c->seq.on)
         return VO_OK;
-    int rc = flow_sync_call(c, "voflow_track", prev, next, w, h, stride, prev_pts_xy, n, err != nullptr, /*compact*/ false);
+    int rc = flow_sync_call(c, who, prev, next, w, h, stride, prev_pts_xy, n, win, err != nullptr, /*compact*/ false);
     if (rc != VO_OK)
         return rc;
     const uint8_t *hb = c->h_gather;
@@ -127,16 +132,18 @@ int voflow_track(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int
     return VO_OK;
 }
 
-int voflow_feature_tracking(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, float *pts0_io, int n,
-                            float *pts1_out, uint8_t *status, float *err, int32_t *keep_idx, int *n_out)
+int feature_tracking(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, float *pts0_io, int n,
+                     int win, float *pts1_out, uint8_t *status, float *err, int32_t *keep_idx, int *n_out)
 {
     if (!c)
         return VO_ERR_ARG;
     if (!prev || !next || !n_out || n < 0 || (n > 0 && (!pts0_io || !pts1_out || !status)))
-        return fail(c, VO_ERR_ARG, "voflow_feature_tracking: null image / points / output, or n < 0");
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": null image / points / output, or n < 0").c_str());
+    if (!win_ok(win))
+        return bad_win(c, who);
     if (n == 0 && !c->seq.on)
         return VO_OK;
-    int rc = flow_sync_call(c, "voflow_feature_tracking", prev, next, w, h, stride, pts0_io, n, err != nullptr, /*compact*/ true);
+    int rc = flow_sync_call(c, who, prev, next, w, h, stride, pts0_io, n, win, err != nullptr, /*compact*/ true);
     if (rc != VO_OK)
         return rc;
     const uint8_t *hb = c->h_gather;
@@ -153,6 +160,70 @@ int voflow_feature_tracking(vo_ctx *c, const uint8_t *prev, const uint8_t *next,
     if (err)
         memcpy(err, hb + L.err(), sizeof(float) * (size_t)n);
     *n_out = count;
+    return VO_OK;
+}
+
+int batch_run(vo_ctx *c, const char *who, int win)
+{
+    if (!c)
+        return VO_ERR_ARG;
+    const std::string me(who);
+    if (!win_ok(win))
+        return bad_win(c, who);
+    if (c->seq.on)
+        return fail(c, VO_ERR_STATE, (me + " inside the sequence loop (vo_seq_*)").c_str());
+    vo_ctx::Flow &fl = c->flow;
+    if (c->n_images == 0)
+        return fail(c, VO_ERR_STATE, (me + " before vo_batch_configure").c_str());
+    if (!fl.ready || fl.n_pairs == 0 || fl.cfg[0] != c->n_images || fl.cfg[1] != c->w || fl.cfg[2] != c->h || fl.cfg[3] != c->n_frames)
+        return fail(c, VO_ERR_STATE, (me + ": no pairs set for this table (voflow_batch_set_pairs after vo_batch_configure)").c_str());
+    for (int f = 0; f < fl.n_pairs; f++)
+        if (c->img_stale[fl.h_pairs[f].l0] | c->img_stale[fl.h_pairs[f].r0])
+            return fail(c, VO_ERR_STATE, (me + ": an image uploaded after its pyramid was last built (run VO_STAGE_PYRAMID over it first)").c_str());
+    VO_HIP_TRY(c, hipSetDevice(c->device));
+    launch_lk_flow_win(win, c->d_imgs, fl.d_pairs, cur_pts(c), cur_npts(c), c->cap, c->max_pts_set, fl.n_pairs, fl.d_next, fl.d_status,
+                       fl.d_err, lk_params(c), c->sel->stream);
+    VO_HIP_TRY(c, hipGetLastError());
+    return VO_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int voflow_track(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, const float *prev_pts_xy, int n,
+                 float *next_pts_xy, uint8_t *status, float *err)
+{
+    return track(c, "voflow_track", prev, next, w, h, stride, prev_pts_xy, n, 21, next_pts_xy, status, err);
+}
+
+int voflow_feature_tracking(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, float *pts0_io, int n,
+                            float *pts1_out, uint8_t *status, float *err, int32_t *keep_idx, int *n_out)
+{
+    return feature_tracking(c, "voflow_feature_tracking", prev, next, w, h, stride, pts0_io, n, 21, pts1_out, status, err, keep_idx, n_out);
+}
+
+int vowin_track(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, const float *prev_pts_xy, int n, int win,
+                float *next_pts_xy, uint8_t *status, float *err)
+{
+    return track(c, "vowin_track", prev, next, w, h, stride, prev_pts_xy, n, win, next_pts_xy, status, err);
+}
+
+int vowin_feature_tracking(vo_ctx *c, const uint8_t *prev, const uint8_t *next, int w, int h, int stride, float *pts0_io, int n, int win,
+                           float *pts1_out, uint8_t *status, float *err, int32_t *keep_idx, int *n_out)
+{
+    return feature_tracking(c, "vowin_feature_tracking", prev, next, w, h, stride, pts0_io, n, win, pts1_out, status, err, keep_idx, n_out);
+}
+
+int vowin_batch_run(vo_ctx *c, int win) { return batch_run(c, "vowin_batch_run", win); }
+
+// the deepest level plan_levels gives an image of this size under the context's lk_max_level.  The context is const, as in
+// vo_model_bytes: a refusal leaves vo_last_error as it was.
+int vowin_max_level(const vo_ctx *c, int w, int h, int *max_level)
+{
+    if (!c || !max_level || w < 32 || h < 32 || w > c->max_w || h > c->max_h)
+        return VO_ERR_ARG;
+    *max_level = plan_depth(w, h, c->prm.lk_max_level);
     return VO_OK;
 }
 
@@ -186,27 +257,7 @@ int voflow_batch_set_pairs(vo_ctx *c, const int32_t *pairs2, int n_frames)
     return VO_OK;
 }
 
-int voflow_batch_run(vo_ctx *c)
-{
-    if (!c)
-        return VO_ERR_ARG;
-    if (c->seq.on)
-        return fail(c, VO_ERR_STATE, "voflow_batch_run inside the sequence loop (vo_seq_*)");
-    vo_ctx::Flow &fl = c->flow;
-    if (c->n_images == 0)
-        return fail(c, VO_ERR_STATE, "voflow_batch_run before vo_batch_configure");
-    if (!fl.ready || fl.n_pairs == 0 || fl.cfg[0] != c->n_images || fl.cfg[1] != c->w || fl.cfg[2] != c->h || fl.cfg[3] != c->n_frames)
-        return fail(c, VO_ERR_STATE, "voflow_batch_run: no pairs set for this table (voflow_batch_set_pairs after vo_batch_configure)");
-    for (int f = 0; f < fl.n_pairs; f++)
-        if (c->img_stale[fl.h_pairs[f].l0] | c->img_stale[fl.h_pairs[f].r0])
-            return fail(c, VO_ERR_STATE, "voflow_batch_run: an image uploaded after its pyramid was last built (run VO_STAGE_PYRAMID "
-                                         "over it first)");
-    VO_HIP_TRY(c, hipSetDevice(c->device));
-    launch_lk_flow(c->d_imgs, fl.d_pairs, cur_pts(c), cur_npts(c), c->cap, c->max_pts_set, fl.n_pairs, fl.d_next, fl.d_status, fl.d_err,
-                   lk_params(c), c->sel->stream);
-    VO_HIP_TRY(c, hipGetLastError());
-    return VO_OK;
-}
+int voflow_batch_run(vo_ctx *c) { return batch_run(c, "voflow_batch_run", 21); }
 
 int voflow_batch_get(vo_ctx *c, int frame, float *next_pts_xy, uint8_t *status, float *err, int n)
 {

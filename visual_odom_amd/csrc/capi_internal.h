@@ -427,6 +427,21 @@ inline int *cur_npts(vo_ctx *c) { return c->pts_sel < 0 ? c->d_npts : c->d_npts_
 inline int *cur_ages(vo_ctx *c) { return c->pts_sel < 0 ? c->d_ages : c->d_ages_det[c->pts_sel]; }
 // row pitch (pixels) of a bordered level: VO_BX left + w + at least VO_BY right, multiple of 16
 inline int level_stride(int w) { return align_up(VO_BX + w + VO_BY, 16); }
+// the deepest pyramid level index of a w x h image, exactly as buildOpticalFlowPyramid with the 21 x 21 window: stop at
+// lk_max_level, at the table's VO_MAX_LEVELS, or when the next level would not be larger than the window (plan_levels,
+// vowin_max_level)
+inline int plan_depth(int w, int h, int lk_max_level)
+{
+    int l = 0;
+    for (int cw = w, ch = h;; l++) {
+        const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
+        if (l == lk_max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
+            break;
+        cw = nw;
+        ch = nh;
+    }
+    return l;
+}
 // the bytes of a source row of vo_params.input_format that are ever read or copied (ingest_bpp: vo_kernels.h): one plane of a
 // two-byte interleave ends with its last pixel (the right plane of an interleaved frame starts at byte 1: byte 2 w of its last
 // row is outside the frame)

@@ -30,6 +30,8 @@
 // launch hop 0 while the new pair is still crossing PCIe (capi_run.hip); lk_circular_kernel is what every other launch runs.
 // lk_flow_kernel: the same body for ONE hop between an arbitrary (prev, next) pair of the image table, with the err output of
 // cv::calcOpticalFlowPyrLK -- the reference's featureTracking() (feature.cpp:64-74; voflow_*, capi_flow.hip).
+// lk_flow_win_kernel<W>: lk_flow_kernel with a W x W window, W odd in 5 .. 19 (vowin_*, include/vo_flow_win.h): the body with the
+// window as a template parameter, the lane map of LkWin<W> below.
 #include "vo_kernels.h"
 #include "vo_lkmath.h"
 
@@ -37,9 +39,26 @@
 
 namespace vo {
 
-constexpr int LK_WIN = 21;
+constexpr int LK_WIN = 21; // the window of the chain kernels and of lk_flow_kernel; lk_flow_win_kernel<W>: odd W of 5 .. 19
 constexpr int LK_JT_W = 48, LK_JT_H = 40; // search tile (bytes x rows), LDS row stride = LK_JT_W
 constexpr int LK_W_BITS = 14;
+// A W x W window on the wavefront: a row is cut into SEGS 7-pixel segments, lane -> (row = lane / SEGS, segment = lane % SEGS),
+// W * SEGS lanes own pixels (63 for W = 21, at most 57 below).  A lane always reads the 8 columns of its segment, so a row of
+// the window reads COLS = 7 * SEGS + 1 columns -- W + 1 only where 7 divides W -- and the last segment of a row holds
+// LAST = W - 7 * (SEGS - 1) pixels of the window; the rest of it is masked out of every sum (lk_seg_mask).
+template <int W>
+struct LkWin {
+    static_assert(W % 2 == 1 && W >= 5 && W <= LK_WIN, "odd windows of 5 .. 21: the pyramid's borders are laid out for 21");
+    static constexpr int SEGS = (W + 6) / 7, LANES = W * SEGS, COLS = 7 * SEGS + 1, ROWS = W + 1, LAST = W - 7 * (SEGS - 1);
+    // where a new tile starts relative to the corner: the window's reads centred in the tile (12 and 9 for W = 21)
+    static constexpr int OFF_X = ((LK_JT_W - COLS) / 2) & ~3, OFF_Y = (LK_JT_H - ROWS) / 2;
+    static_assert(LANES <= 64 && LK_JT_W >= COLS + OFF_X + 3 && LK_JT_H >= ROWS + OFF_Y, "the lane map and the tile hold the window");
+};
+// the packed int16 pair m (pixels 2 m, 2 m + 1) of a segment that holds `valid` pixels of the window: ones where the pixel counts
+constexpr uint32_t lk_seg_mask(int valid, int m)
+{
+    return (2 * m < valid ? 0x0000ffffu : 0u) | (2 * m + 1 < valid ? 0xffff0000u : 0u);
+}
 
 // 14-bit fixed-point bilinear weights of OpenCV's LKTrackerInvoker from the fractional parts of the
 // window corner: iw00 = cvRound((1-a)*(1-b)*2^14), iw01 = cvRound(a*(1-b)*2^14), iw10 = cvRound((1-a)*b*2^14),
@@ -67,19 +86,22 @@ __device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint3
 struct LkOrigin {
     int x, y;
 };
-// is there no tile yet, or does it miss part of the window of corner (inx, iny): columns inx .. inx + 21, rows iny .. iny + 21
+// is there no tile yet, or does it miss part of what the window of corner (inx, iny) reads: columns inx .. inx + 21, rows
+// iny .. iny + 21 (W = 21; in general LkWin<W>::COLS columns, masked ones included, and W + 1 rows)
+template <int W = LK_WIN>
 __device__ __forceinline__ bool lk_tile_misses(bool have_tile, int jx0, int jy0, int inx, int iny)
 {
-    return !have_tile || inx < jx0 || inx + LK_WIN + 1 > jx0 + LK_JT_W || iny < jy0 || iny + LK_WIN + 1 > jy0 + LK_JT_H;
+    return !have_tile || inx < jx0 || inx + LkWin<W>::COLS > jx0 + LK_JT_W || iny < jy0 || iny + LkWin<W>::ROWS > jy0 + LK_JT_H;
 }
 // a new tile around corner (inx, iny): the origin -- 4-byte aligned, clamped to [-VO_BX, jx_max] x [-VO_BY, jy_max], which keeps
 // the tile inside the level's rectangle -- and the fill, 16-byte chunks c0, c0 + step, ... of the tile's LK_JT_H * LK_JT_W / 16.
 // Returns the origin.  No barrier in here: the caller orders the fill against the LDS reads around it.
+template <int W = LK_WIN>
 __device__ __forceinline__ LkOrigin lk_tile_refill(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
                                                int inx, int iny, int c0, int step)
 {
-    int jx0 = (inx - 12) & ~3;
-    int jy0 = iny - 9;
+    int jx0 = (inx - LkWin<W>::OFF_X) & ~3;
+    int jy0 = iny - LkWin<W>::OFF_Y;
     jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
     jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
     const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
@@ -92,13 +114,14 @@ __device__ __forceinline__ LkOrigin lk_tile_refill(uint8_t *tile, const VO_GLOBA
 }
 // the one-feature kernels: the origin of a tile that covers the window of corner (inx, iny) -- the wave's own if it does, else a
 // new one, fetched between two barriers
+template <int W = LK_WIN>
 __device__ __forceinline__ LkOrigin lk_tile_cover(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
                                               int inx, int iny, int lane, bool have_tile, int jx0, int jy0)
 {
-    if (!lk_tile_misses(have_tile, jx0, jy0, inx, iny))
+    if (!lk_tile_misses<W>(have_tile, jx0, jy0, inx, iny))
         return LkOrigin{jx0, jy0};
     __syncthreads(); // single-wave workgroup: orders the LDS reads before the refill
-    const LkOrigin o = lk_tile_refill(tile, Jimg, jstride, jx_max, jy_max, inx, iny, lane, 64);
+    const LkOrigin o = lk_tile_refill<W>(tile, Jimg, jstride, jx_max, jy_max, inx, iny, lane, 64);
     __syncthreads();
     return o;
 }
@@ -127,7 +150,11 @@ __device__ __forceinline__ void lk_cell_rows(const uint8_t *tile, int off, uint3
 // ERR = true (lk_flow_kernel): ONE hop, frame = (prev, next) = (Quad::l0, Quad::r0); trk / status are [B][cap], nothing retires
 // early, and the level-0 template stays in registers for the err epilogue: err [B][cap] = sum |J(final corner) - I| / (32 * 21 * 21)
 // of a point that ends with status 1, else 0 (err == nullptr: not computed).  Everything ERR adds is behind `if constexpr`.
-template <bool SPLIT, bool ERR>
+// WIN (lk_flow_win_kernel<W>, with ERR): the window, LkWin<WIN> its lane map.  Everything that depends on the window follows it
+// -- halfWin, the +-WIN admissibility tests, the 2 WIN^2 of the min-eigenvalue test, the 32 WIN^2 of err, the tile test and the
+// refill's centring -- and what a window below 21 adds (the masks of a row's last segment) is behind `if constexpr` too: for
+// WIN = 21 every expression is the constant it was.
+template <bool SPLIT, bool ERR, int WIN = LK_WIN>
 __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads,
                                                  const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
                                                  int n_frames, int fpg /* 1, 2, 4 or 8 */, int ppp /* features per part */,
@@ -147,17 +174,19 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
     if (frame >= n_frames || f >= n_pts[frame])
         return;
     const int lane = threadIdx.x;
-    // lane -> (row, 7-pixel segment); lane 63 duplicates lane 62's addresses, contributions zeroed
-    const bool live = lane < 63;
-    const int lr = live ? lane : 62;
-    const int r = lr / 3, c0 = 7 * (lr - 3 * r);
+    // lane -> (row, 7-pixel segment); lane 63 (WIN = 21; every lane from WIN * SEGS on) duplicates the last live lane's
+    // addresses, contributions zeroed
+    using LW = LkWin<WIN>;
+    const bool live = lane < LW::LANES;
+    const int lr = live ? lane : LW::LANES - 1;
+    const int r = lr / LW::SEGS, c0 = 7 * (lr - LW::SEGS * r);
     const int lane_off = r * LK_JT_W + c0; // this lane's row segment inside the search tile
 
     const Quad q = quads[frame];
-    const float halfWin = (LK_WIN - 1) * 0.5f;
+    const float halfWin = (WIN - 1) * 0.5f;
     const float FLT_SCALE = 1.f / (1 << 20);
     const float eps_lo = (float)(prm.epsilon * 0.999999), eps_hi = (float)(prm.epsilon * 1.000001);
-    const float min_eig_n = prm.min_eig * (1.001f * (float)(2 * LK_WIN * LK_WIN)); // see the min-eigenvalue test
+    const float min_eig_n = prm.min_eig * (1.001f * (float)(2 * WIN * WIN)); // see the min-eigenvalue test
 
     const float2 p = pts_in[(size_t)frame * cap + f];
     float prevPtX = unif(p.x), prevPtY = unif(p.y);
@@ -210,7 +239,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // x86's cvFloor(NaN) is INT_MIN (cvttss2si), i.e. "left of the window": OpenCV rejects a NaN coordinate here.
             // v_cvt_i32_f32(NaN) is 0, which would ADMIT it -- so NaN is rejected on the float (one
             // v_cmp_u_f32 into a scalar pair).  +-inf and finite values beyond int32 saturate to the rejected side on both.
-            if (VO_BALLOT(__builtin_isunordered(fpx, fpy)) != 0ull || ipx < -LK_WIN || ipx >= iw || ipy < -LK_WIN || ipy >= ih) {
+            if (VO_BALLOT(__builtin_isunordered(fpx, fpy)) != 0ull || ipx < -WIN || ipx >= iw || ipy < -WIN || ipy >= ih) {
                 if (level == 0)
                     st = 0;
                 continue;
@@ -249,6 +278,17 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                 uint32_t Ip[4];
                 bilinear7_u8(t.a, t.b, u.a, u.b, wt, wb, Ip);
                 bilinear7_deriv(dt, db, wt, wb, Ixp, Iyp);
+                if constexpr (LW::LAST < 7) {
+                    // the last segment of a row reaches beyond the window: its pixels from LAST on get Ix = Iy = 0, once per
+                    // level, so that A11 / A12 / A22, the seeds c1 / c2 and every b1 / b2 of the iteration take nothing from them
+                    const bool part = LW::SEGS == 1 || c0 == 7 * (LW::SEGS - 1);
+#pragma unroll
+                    for (int m = 0; m < 4; m++) {
+                        const uint32_t keep = part ? lk_seg_mask(LW::LAST, m) : 0xffffffffu;
+                        Ixp[m] &= keep;
+                        Iyp[m] &= keep;
+                    }
+                }
                 a11 = sdot2_first(Ixp[0], Ixp[0], 0);
                 a12 = sdot2_first(Ixp[0], Iyp[0], 0);
                 a22 = sdot2_first(Iyp[0], Iyp[0], 0);
@@ -275,7 +315,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             A22 *= FLT_SCALE;
 
             float D = A11 * A22 - A12 * A12;
-            // OpenCV: minEig = (A22 + A11 - sqrt((A11-A22)^2 + 4 A12^2)) / (2 * 21 * 21), rejected when < minEigThreshold.
+            // OpenCV: minEig = (A22 + A11 - sqrt((A11-A22)^2 + 4 A12^2)) / (2 * 21 * 21), rejected when < minEigThreshold
+            // (882 = 2 * 21 * 21 below stands for 2 * WIN * WIN: the argument holds for any positive constant).
             // The correctly rounded sqrt and divide cost ~30 wave-uniform VALU instructions, and the test is almost
             // never close: with t = A22 + A11, s2 = the radicand and u = t - (1.001 * 882 * thr + t * 2^-18),
             // "u > 0 and s2 < 0.9999 u^2" implies sqrt(s2) < u (1 - 4e-5), hence the rounded t - sqrt(s2) exceeds
@@ -289,7 +330,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
 #ifndef VO_HOST_EMUL
                 asm volatile("" ::: "memory"); // keep the sqrt / divide out of the common path
 #endif
-                const float minEig = (t - sqrtf(s2)) / (float)(2 * LK_WIN * LK_WIN);
+                const float minEig = (t - sqrtf(s2)) / (float)(2 * WIN * WIN);
                 eig_ok = !(minEig < prm.min_eig);
             }
             if (!eig_ok || D < FLT_EPSILON) {
@@ -311,9 +352,12 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // tile origins that keep the 40 x 48 tile inside the level's rectangle (vo_dev.h, "reads stay inside their level"):
             // the last tile ends exactly at the row end (column jstride - VO_BX - 1) and at the last border row
             static_assert(LK_JT_W % 16 == 0 && VO_BX % 4 == 0, "16-byte tile chunks at 4-byte aligned origins");
-            static_assert(VO_BY >= LK_WIN && LK_JT_W >= LK_WIN + 1 + 12 + 3 && LK_JT_H >= LK_WIN + 1 + 9,
-                          "a tile clamped to the row end / the last border row still covers the window of every corner the "
-                          "reference admits (up to w - 1, h - 1: the borders are at least a window wide)");
+            // (the right border of a row is stride - VO_BX - w >= VO_BY columns -- level_stride pads the row by VO_BY and rounds up --
+            // so VO_BY is the column border the reads of a corner at w - 1 rely on, as it is the row border below h - 1)
+            static_assert(VO_BY >= WIN && LK_JT_W >= LW::COLS + LW::OFF_X + 3 && LK_JT_H >= LW::ROWS + LW::OFF_Y,
+                          "a tile clamped to the row end / the last border row still covers what the window of every corner the "
+                          "reference admits reads (up to w - 1, h - 1: the borders are at least a window wide)");
+            static_assert(VO_BY >= LW::COLS - 1, "right border (at least VO_BY columns) >= the columns a row reads beyond corner w - 1");
             const int jx_max = jstride - VO_BX - LK_JT_W, jy_max = jh + VO_BY - LK_JT_H;
 
             // The window corner stays in the same pixel cell for two iterations out of three, so the Gauss-Newton
@@ -325,13 +369,13 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             bool run = prm.max_count > 0;
             while (run) {
                 const int inx = uni(vo_f2i(fnx)), iny = uni(vo_f2i(fny));
-                if (VO_BALLOT(__builtin_isunordered(fnx, fny)) != 0ull || inx < -LK_WIN || inx >= jw || iny < -LK_WIN || iny >= jh) {
+                if (VO_BALLOT(__builtin_isunordered(fnx, fny)) != 0ull || inx < -WIN || inx >= jw || iny < -WIN || iny >= jh) {
                     if (level == 0)
                         st = 0;
                     break;
                 }
                 {
-                    const LkOrigin o = lk_tile_cover(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
+                    const LkOrigin o = lk_tile_cover<WIN>(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
                     jx0 = o.x;
                     jy0 = o.y;
                     have_tile = true;
@@ -411,18 +455,19 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // possibly huge -- both conversions then land on a rejected side, x86's INT_MIN and gfx950's saturated INT_MAX)
             if (st && level == 0) {
                 const int fx = vo_f2i(floorf(outX - halfWin)), fy = vo_f2i(floorf(outY - halfWin));
-                if (fx < -LK_WIN || fx >= jw || fy < -LK_WIN || fy >= jh)
+                if (fx < -WIN || fx >= jw || fy < -WIN || fy >= jh)
                     st = 0;
                 if constexpr (ERR) {
                     // err of cv::calcOpticalFlowPyrLK (lkpyramid.cpp, the block behind the iterations): the window at the corner of
                     // the FINAL position (after a possible half step back: another cell, possibly outside the tile) against the
                     // template, sum |Jp - Ip| over the 441 pixels / (32 * 21 * 21).  The integer sum is below 441 * 8160 < 2^24, so
-                    // rounding it once is the reference's running f32 sum bit for bit.
+                    // rounding it once is the reference's running f32 sum bit for bit (WIN * WIN <= 441 pixels; those a row's last
+                    // segment holds beyond the window are masked like their derivatives).
                     if (st && err != nullptr) {
                         const float ex = outX - halfWin, ey = outY - halfWin;
                         const float fex = floorf(ex), fey = floorf(ey);
                         const int inx = uni(fx), iny = uni(fy); // (admitted just above: inside [-21, jw) x [-21, jh))
-                        const LkOrigin o = lk_tile_cover(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
+                        const LkOrigin o = lk_tile_cover<WIN>(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
                         jx0 = o.x;
                         jy0 = o.y;
                         uint32_t Jt[7], Jb[7], Jp[4];
@@ -431,9 +476,16 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                         blend7(Jt, Jb, wt, wb, Jp);
                         uint32_t e = 0; // lane 63 duplicates lane 62's pixels: it contributes nothing
 #pragma unroll
-                        for (int m = 0; m < 4; m++)
-                            e = udot2(pk_absdiff_i16(Jp[m], Ipe[m]), 0x00010001u, e);
-                        errv = wave_sum_exact_f32(live ? (int)e : 0) / (float)(32 * LK_WIN * LK_WIN);
+                        for (int m = 0; m < 4; m++) {
+                            // (the unmasked case keeps the statement it always was: with one shape for both, lk_flow_kernel's
+                            // instruction stream comes out with two scalar moves exchanged)
+                            if constexpr (LW::LAST < 7) {
+                                const bool part = LW::SEGS == 1 || c0 == 7 * (LW::SEGS - 1);
+                                e = udot2(pk_absdiff_i16(Jp[m], Ipe[m]) & (part ? lk_seg_mask(LW::LAST, m) : 0xffffffffu), 0x00010001u, e);
+                            } else
+                                e = udot2(pk_absdiff_i16(Jp[m], Ipe[m]), 0x00010001u, e);
+                        }
+                        errv = wave_sum_exact_f32(live ? (int)e : 0) / (float)(32 * WIN * WIN);
                     }
                 }
             }
@@ -507,6 +559,19 @@ __global__ VO_LK_FLOW_ATTRS void lk_flow_kernel(const PyrImage *__restrict__ img
     lk_circular_body<false, true>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err);
 }
 
+// The same hop with a W x W window, W odd in 5 .. 19 (vowin_*, capi_flow.hip; W = 21 is lk_flow_kernel): the body with
+// WIN = W, one instantiation per window.  Register reports of the eight: profiles/flow.md.
+template <int W>
+__global__ VO_LK_FLOW_ATTRS void lk_flow_win_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ pairs,
+                                                    const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
+                                                    int n_frames, int fpg, int ppp, float2 *__restrict__ next, // [B][cap]
+                                                    uint8_t *__restrict__ status,                               // [B][cap]
+                                                    float *__restrict__ err /* [B][cap] or null */, LkParams prm)
+{
+    static_assert(W < LK_WIN, "21 is lk_flow_kernel");
+    lk_circular_body<false, true, W>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err);
+}
+
 #ifndef VO_HOST_EMUL
 // The launch geometry of the block numbering above: frames per group of 8 XCDs (the largest power of two <= min(8, n_frames)),
 // work items -- features, or the pair kernel's pairs of features (dev/lk_dev.hip) -- per part of a frame's list, and the grid.
@@ -530,6 +595,36 @@ void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d
     const LkGrid g = lk_grid(n_frames, max_pts);
     hipLaunchKernelGGL(lk_flow_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp, d_next,
                        d_status, d_err, prm);
+}
+
+// launch_lk_flow with a window: 21 is lk_flow_kernel itself, every odd W of 5 .. 19 its own instantiation.  Precondition: win is
+// one of these (the entry points of capi_flow.hip refuse every other window); nothing is launched for any other.
+template <int W>
+static void launch_lk_flow_win_w(const LkGrid &g, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
+                                 int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lk_flow_win_kernel<W>, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
+                       d_next, d_status, d_err, prm);
+}
+void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
+                        int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+{
+    if (win == LK_WIN) {
+        launch_lk_flow(d_imgs, d_pairs, d_pts, d_npts, cap, max_pts, n_frames, d_next, d_status, d_err, prm, stream);
+        return;
+    }
+    if (max_pts <= 0 || n_frames <= 0)
+        return;
+    const LkGrid g = lk_grid(n_frames, max_pts);
+    switch (win) {
+#define VO_LK_WIN_CASE(W)                                                                                                       \
+    case W:                                                                                                                     \
+        launch_lk_flow_win_w<W>(g, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, d_next, d_status, d_err, prm, stream);       \
+        break;
+        VO_LK_WIN_CASE(5) VO_LK_WIN_CASE(7) VO_LK_WIN_CASE(9) VO_LK_WIN_CASE(11) VO_LK_WIN_CASE(13) VO_LK_WIN_CASE(15) VO_LK_WIN_CASE(17)
+        VO_LK_WIN_CASE(19)
+#undef VO_LK_WIN_CASE
+    }
 }
 
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,

@@ -24,6 +24,9 @@
 //                     edge items at x4 - 4 .. x4 + 3; rows reflected into 0 .. h - 1                       (pyramid.hip)
 //   lk_circular_*     I-window rows and the 48 x 40 search tile: tile origin clamped to [-VO_BX, stride - VO_BX - 48] x
 //                     [-VO_BY, h + VO_BY - 40], 16-byte chunks; derivative dwords of the 21 x 21 window          (lk.hip)
+//   lk_flow_win_<W>   the same for a W x W window, W odd in 5 .. 19: admitted corners are >= -W >= -21, a lane reads the 8 columns
+//                     of its 7-pixel segment whether the window ends inside it or not, so a row reads 7 ceil(W / 7) + 1 <= 22
+//                     columns and W + 1 <= 20 rows -- never beyond what the 21 x 21 window reads; the same tile clamp  (lk.hip)
 //   fast_tile_*       16-byte chunks of rows y0 - 4 .. (clamped to h + VO_BY - 1), columns x0 - 4 ..; a chunk that would cross
 //                     the row end reads the row's last 16 bytes instead (its bytes are never used)                  (fast.hip)
 // Checked by the sanitizer tier: the CPU emulator (tests/host_check/kernel_emu.cpp) runs these kernel sources with every level

@@ -136,6 +136,10 @@ void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d
 // d_next / d_status / d_err: [B][cap], d_err may be null (the err epilogue is skipped)
 void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
+// the same with a win x win window (lk_flow_win_kernel<win>, odd 5 .. 19; 21 is launch_lk_flow).  Precondition: win is odd and in
+// 5 .. 21 -- there is no kernel for any other window and nothing is launched for one
+void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
+                        int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,
                           int h, int threshold, int nonmax, unsigned long long *d_nmsmask,
                           int *d_rowcnt, int *d_rowoff,
