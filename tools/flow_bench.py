@@ -13,7 +13,20 @@
               the others.  W = 21 there is voflow_batch_run's kernel through the other entry point: the two legs are to agree
               within the spread of `flow`.  With --win the latency part also times vowin_track for each window.
 
-    python tools/flow_bench.py [--pairs 256] [--runs 20] [--repeats 5] [--calls 200] [--win 7 15 21] [--json out.json]
+  --guess      what OPTFLOW_USE_INITIAL_FLOW buys (include/vo_flow_flags.h), at 21 x 21 through the batch calls on the same pairs:
+                (a)   vowin_batch_run(21) at lk_max_level 3;
+                (b)   voflag_batch_run(21, USE_INITIAL_FLOW) at lk_max_level 0 with (a)'s answer as the guess -- a PERFECT
+                      prediction, i.e. an upper bound on the gain;
+                (c)   the same at lk_max_level 3;
+                (a0)  vowin_batch_run(21) at lk_max_level 0, what dropping the levels without a guess gives;
+                (eig) voflag_batch_run(21, GET_MIN_EIGENVALS) at lk_max_level 3 against (a): no epilogue, one sqrt and divide.
+              A run leaves its results where the next run's guesses are read, so every timed run here is ONE run between two
+              synchronisations with the guesses written again before it (untimed); `--runs` x `--repeats` of them per leg.  Each
+              leg also reports how many of the points it tracks end within 0.05 px of (a)'s position.  lk_max_level is part of
+              the pyramid plan, so the level-0 legs run on a table of their own after the level-3 legs, not alternating with them.
+  --skip-base  with --guess: only that section.
+
+    python tools/flow_bench.py [--pairs 256] [--runs 20] [--repeats 5] [--calls 200] [--win 7 15 21] [--guess] [--json out.json]
 """
 import argparse
 import json
@@ -29,6 +42,89 @@ sys.path.insert(0, ROOT)
 W, H = 1241, 376
 
 
+def guess_legs(args, _lib, L, pts, n_max):
+    """the --guess section (see the module's text)"""
+    B, Q = args.pairs, args.frames
+    ctx = _lib.Context(0, W, H, max(4096, n_max), B)
+    counts = [len(pts[f % Q]) for f in range(B)]
+
+    def table(level):
+        ctx.set_params(lk_max_level=level)
+        ctx.batch_configure(2 * B, W, H, B)
+        for f in range(B):
+            k = f % Q
+            ctx.batch_upload_image(2 * f, L[k])
+            ctx.batch_upload_image(2 * f + 1, L[k + 1])
+            ctx.batch_set_points(f, pts[k])
+        ctx.batch_run(_lib.STAGE_PYRAMID)
+        ctx.batch_sync()
+        ctx.flow_batch_set_pairs([(2 * f, 2 * f + 1) for f in range(B)])
+
+    def results():
+        ctx.batch_sync()
+        return [ctx.flow_batch_get(f, n) for f, n in enumerate(counts)]
+
+    def timed(name, run, guesses=None):
+        t = []
+        for i in range(1 + args.runs * args.repeats):   # (run 0 is the warm-up and is not kept)
+            if guesses is not None:
+                for f, g in enumerate(guesses):
+                    ctx.flow_batch_set_guess(f, g)
+            ctx.batch_sync()
+            t0 = time.perf_counter()
+            run()
+            ctx.batch_sync()
+            if i:
+                t.append(1e3 * (time.perf_counter() - t0))
+        t = np.array(t)
+        return dict(median_ms=float(np.median(t)), min_ms=float(t.min()), max_ms=float(t.max()), n_runs=len(t)), results()
+
+    def agreement(res, ref):
+        tracked = within = 0
+        for (nxt, st, _), (rn, _, _) in zip(res, ref):
+            ok = st == 1
+            tracked += int(ok.sum())
+            within += int((np.abs(nxt[ok] - rn[ok]).max(1) <= 0.05).sum()) if ok.any() else 0
+        return dict(tracked=tracked, within_0p05_of_a=within)
+
+    legs = {}
+    table(3)
+    legs["a_win21_level3"], ref = timed("a", lambda: ctx.flow_batch_run(win=21))
+    answer = [np.ascontiguousarray(r[0]) for r in ref]
+    legs["c_guess_level3"], rc = timed("c", lambda: ctx.flow_batch_run(win=21, guess=True), answer)
+    legs["eig_level3"], re = timed("eig", lambda: ctx.flow_batch_run(win=21, min_eigenvals=True))
+    table(0)
+    legs["a0_win21_level0"], r0 = timed("a0", lambda: ctx.flow_batch_run(win=21))
+    legs["b_guess_level0"], rb = timed("b", lambda: ctx.flow_batch_run(win=21, guess=True), answer)
+    for name, res in (("a_win21_level3", ref), ("c_guess_level3", rc), ("eig_level3", re), ("a0_win21_level0", r0), ("b_guess_level0", rb)):
+        legs[name].update(agreement(res, ref))
+        print("guess leg %-16s median %8.3f ms  min %8.3f  max %8.3f  tracked %d  within 0.05 px of (a) %d" %
+              (name, legs[name]["median_ms"], legs[name]["min_ms"], legs[name]["max_ms"], legs[name]["tracked"], legs[name]["within_0p05_of_a"]), flush=True)
+    legs["points"] = int(sum(counts))
+    ctx.close()
+    if args.calls > 0:   # the synchronous call: what the guess's own copy and the flags cost per call (lk_max_level 3)
+        ctx = _lib.Context(0, W, H, max(4096, n_max), 1)
+        g = answer[0]
+        calls = [("vowin_track_21", lambda: ctx.flow_track(L[0], L[1], pts[0], win=21)),
+                 ("voflag_track_21_guess", lambda: ctx.flow_track(L[0], L[1], pts[0], win=21, guess=g)),
+                 ("voflag_track_21_min_eig", lambda: ctx.flow_track(L[0], L[1], pts[0], win=21, min_eigenvals=True))]
+        lat = {}
+        for name, fn in calls:
+            for _ in range(20):
+                fn()
+            t = []
+            for _ in range(args.calls):
+                t0 = time.perf_counter()
+                fn()
+                t.append(1e3 * (time.perf_counter() - t0))
+            t = np.array(t)
+            lat[name] = dict(median_ms=float(np.median(t)), min_ms=float(t.min()), p90_ms=float(np.percentile(t, 90)))
+            print("%-24s median %7.3f ms  min %7.3f  p90 %7.3f  (%d points)" % (name, np.median(t), t.min(), np.percentile(t, 90), len(pts[0])), flush=True)
+        legs["latency"] = lat
+        ctx.close()
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=256)
@@ -37,6 +133,8 @@ def main():
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--frames", type=int, default=4, help="distinct rendered frames the pairs walk over")
     ap.add_argument("--win", type=int, nargs="*", default=[], help="windows to time through vowin_batch_run / vowin_track")
+    ap.add_argument("--guess", action="store_true", help="the USE_INITIAL_FLOW / GET_MIN_EIGENVALS legs")
+    ap.add_argument("--skip-base", action="store_true", help="with --guess: skip the throughput and latency sections")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     from visual_odom_amd import _lib, synth
@@ -46,6 +144,14 @@ def main():
     pts = [np.ascontiguousarray(synth.select_keypoints(L[k], bucket=37, per_bucket=6), np.float32) for k in range(Q)]
     n_max = max(len(p) for p in pts)
     out = dict(pairs=B, width=W, height=H, runs=args.runs, repeats=args.repeats, points_per_frame=float(np.mean([len(p) for p in pts])))
+
+    if args.guess:
+        out["guess"] = guess_legs(args, _lib, L, pts, n_max)
+    if args.guess and args.skip_base:
+        if args.json:
+            with open(args.json, "w") as fh:
+                json.dump(out, fh, indent=1)
+        return
 
     # ---- throughput ----
     ctx = _lib.Context(0, W, H, max(4096, n_max), B)

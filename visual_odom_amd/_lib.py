@@ -44,6 +44,10 @@ EXPORTS = (
 FLOW_EXPORTS = ("voflow_track", "voflow_feature_tracking", "voflow_batch_set_pairs", "voflow_batch_run", "voflow_batch_get")
 # every symbol include/vo_flow_win.h declares: the same tracker with a window of 5 x 5 .. 21 x 21
 WIN_EXPORTS = ("vowin_track", "vowin_feature_tracking", "vowin_batch_run", "vowin_max_level")
+# every symbol include/vo_flow_flags.h declares: the same tracker with cv::calcOpticalFlowPyrLK's flags, and the two flags
+FLAG_EXPORTS = ("voflag_track", "voflag_feature_tracking", "voflag_batch_set_guess", "voflag_batch_run")
+FLAG_USE_INITIAL_FLOW = 4
+FLAG_GET_MIN_EIGENVALS = 8
 
 
 class _VoParamsLayout(C.Structure):
@@ -141,7 +145,11 @@ def load():
     lib.vowin_feature_tracking.argtypes = [vp, vp, vp, i, i, i, vp, i, i, vp, vp, vp, vp, vp]
     lib.vowin_batch_run.argtypes = [vp, i]
     lib.vowin_max_level.argtypes = [vp, i, i, vp]
-    for name in FLOW_EXPORTS + WIN_EXPORTS:
+    lib.voflag_track.argtypes = [vp, vp, vp, i, i, i, vp, i, i, i, vp, vp, vp]
+    lib.voflag_feature_tracking.argtypes = [vp, vp, vp, i, i, i, vp, i, i, i, vp, vp, vp, vp, vp]
+    lib.voflag_batch_set_guess.argtypes = [vp, i, vp, i]
+    lib.voflag_batch_run.argtypes = [vp, i, i]
+    for name in FLOW_EXPORTS + WIN_EXPORTS + FLAG_EXPORTS:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -368,10 +376,16 @@ class Context:
                     keep_idx=keep[:m].copy(), n_out=m)
 
     # ---- two-image tracker (include/vo_flow.h) ------------------------------------------------
-    def flow_track(self, prev, nxt, pts, want_err=True, win=None):
+    @staticmethod
+    def _flow_flags(guess, min_eigenvals):
+        return (FLAG_USE_INITIAL_FLOW if guess is not None else 0) | (FLAG_GET_MIN_EIGENVALS if min_eigenvals else 0)
+
+    def flow_track(self, prev, nxt, pts, want_err=True, win=None, guess=None, min_eigenvals=False):
         """cv::calcOpticalFlowPyrLK(prev, nxt, pts, ...) with the context's LK parameters: (next [n, 2], status [n], err [n] or
         None).  Afterwards the context holds no kept pair.  win: None = voflow_track (21 x 21), a number = vowin_track with that
-        window (include/vo_flow_win.h: odd, 5 .. 21, on the levels flow_max_level gives)."""
+        window (include/vo_flow_win.h: odd, 5 .. 21, on the levels flow_max_level gives).  guess [n, 2] (the search starts there:
+        OPTFLOW_USE_INITIAL_FLOW) and / or min_eigenvals (err = min eigenvalue: OPTFLOW_LK_GET_MIN_EIGENVALS) = voflag_track
+        (include/vo_flow_flags.h), win None = 21 there."""
         imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
         h, w = imgs[0].shape[:2]
         self._kept_shape = (0, 0)
@@ -379,16 +393,25 @@ class Context:
         n = pts.shape[0]
         out, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
         err = np.zeros(max(n, 1), np.float32) if want_err else None
-        if win is None:
+        flags = self._flow_flags(guess, min_eigenvals)
+        if flags:
+            if guess is not None:
+                g = _f32(guess, (-1, 2))
+                if g.shape[0] != n:
+                    raise ValueError("flow_track: one guess per point")
+                out[:n] = g
+            self._chk(self.lib.voflag_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, 21 if win is None else int(win), flags,
+                                            _p(out), _p(st), _pn(err)))
+        elif win is None:
             self._chk(self.lib.voflow_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, _p(out), _p(st), _pn(err)))
         else:
             self._chk(self.lib.vowin_track(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(pts), n, int(win), _p(out), _p(st), _pn(err)))
         return out[:n], st[:n], (err[:n] if want_err else None)
 
-    def feature_tracking(self, prev, nxt, pts, want_err=True, win=None):
+    def feature_tracking(self, prev, nxt, pts, want_err=True, win=None, guess=None, min_eigenvals=False):
         """the reference's featureTracking() (feature.cpp:64-74): calcOpticalFlowPyrLK + deleteUnmatchFeatures.  dict(points0,
         points1: the survivors [n_out, 2]; status [n]: as the reference leaves it; err [n] or None; keep_idx [n_out]; n_out).
-        win: as in flow_track (a number = vowin_feature_tracking)"""
+        win: as in flow_track (a number = vowin_feature_tracking); guess, min_eigenvals: as there (voflag_feature_tracking)"""
         imgs, stride = _imgs(prev, nxt, fmt=self.input_format)
         h, w = imgs[0].shape[:2]
         self._kept_shape = (0, 0)
@@ -399,7 +422,16 @@ class Context:
         p1, st = np.zeros((max(n, 1), 2), np.float32), np.zeros(max(n, 1), np.uint8)
         err = np.zeros(max(n, 1), np.float32) if want_err else None
         keep, n_out = np.zeros(max(n, 1), np.int32), C.c_int(0)
-        if win is None:
+        flags = self._flow_flags(guess, min_eigenvals)
+        if flags:
+            if guess is not None:
+                g = _f32(guess, (-1, 2))
+                if g.shape[0] != n:
+                    raise ValueError("feature_tracking: one guess per point")
+                p1[:n] = g
+            self._chk(self.lib.voflag_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, 21 if win is None else int(win),
+                                                       flags, _p(p1), _p(st), _pn(err), _p(keep), C.addressof(n_out)))
+        elif win is None:
             self._chk(self.lib.voflow_feature_tracking(self.h, _p(imgs[0]), _p(imgs[1]), w, h, stride, _p(p0), n, _p(p1), _p(st), _pn(err),
                                                        _p(keep), C.addressof(n_out)))
         else:
@@ -414,9 +446,20 @@ class Context:
         q = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         self._chk(self.lib.voflow_batch_set_pairs(self.h, _p(q), q.shape[0]))
 
-    def flow_batch_run(self, win=None):
-        """one hop per frame over the pairs, asynchronous on the context's stream (win: a number = vowin_batch_run)"""
-        self._chk(self.lib.voflow_batch_run(self.h) if win is None else self.lib.vowin_batch_run(self.h, int(win)))
+    def flow_batch_run(self, win=None, guess=None, min_eigenvals=False):
+        """one hop per frame over the pairs, asynchronous on the context's stream (win: a number = vowin_batch_run).  guess: True =
+        every frame's search starts at what flow_batch_set_guess or the previous run left in its next positions; min_eigenvals:
+        err = min eigenvalue (voflag_batch_run, win None = 21 there)"""
+        flags = self._flow_flags(guess if guess else None, min_eigenvals)
+        if flags:
+            self._chk(self.lib.voflag_batch_run(self.h, 21 if win is None else int(win), flags))
+        else:
+            self._chk(self.lib.voflow_batch_run(self.h) if win is None else self.lib.vowin_batch_run(self.h, int(win)))
+
+    def flow_batch_set_guess(self, frame, pts):
+        """the guesses of one frame for a flow_batch_run(guess=True): pts [n, 2] into its first n next positions"""
+        g = _f32(pts, (-1, 2))
+        self._chk(self.lib.voflag_batch_set_guess(self.h, int(frame), _p(g), g.shape[0]))
 
     def flow_max_level(self, w, h):
         """the deepest pyramid level the context tracks on for a w x h image under its lk_max_level: the maxLevel of the OpenCV

@@ -50,7 +50,7 @@ def build(force=False, verbose=False, dev=False):
         if os.environ.get("VO_LK_ATTRS"):  # developer A/B of the LK kernel's register caps
             flags.append("-DVO_LK_ATTRS=" + os.environ["VO_LK_ATTRS"])
     headers = [os.path.join(d, f) for d in (CSRC, os.path.join(CSRC, "dev")) for f in os.listdir(d) if f.endswith(".h")]
-    headers += [os.path.join(HERE, "..", "include", f) for f in ("vo_hip.h", "vo_flow.h", "vo_flow_win.h")]
+    headers += [os.path.join(HERE, "..", "include", f) for f in ("vo_hip.h", "vo_flow.h", "vo_flow_win.h", "vo_flow_flags.h")]
     wrapped = {w: s for s, w in DEV_WRAPPERS.items()}
     objs, jobs = [], []
     for s in (DEV_SOURCES if dev else SOURCES):

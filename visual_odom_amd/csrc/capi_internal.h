@@ -328,6 +328,7 @@ struct vo_ctx {
         std::vector<Quad> h_pairs;   // host copy of the pairs (stale-pyramid check)
         int n_pairs = 0;             // 0: no pairs set (or the table has been configured again since)
         int cfg[4] = {0, 0, 0, 0};   // n_images, w, h, n_frames of the table the pairs were set for
+        std::vector<uint8_t> next_set; // [max_frames] the frame's d_next rows hold a guess or a run's results since the pairs were set
     } flow;
     // ---- lock-step sequence loop (vo_seq_*): S sequences x 1 frame per step, state carried on the device ----
     struct Seq {

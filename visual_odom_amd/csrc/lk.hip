@@ -32,6 +32,8 @@
 // cv::calcOpticalFlowPyrLK -- the reference's featureTracking() (feature.cpp:64-74; voflow_*, capi_flow.hip).
 // lk_flow_win_kernel<W>: lk_flow_kernel with a W x W window, W odd in 5 .. 19 (vowin_*, include/vo_flow_win.h): the body with the
 // window as a template parameter, the lane map of LkWin<W> below.
+// lk_flow_flags_kernel<W>: the same hop with the two flags of cv::calcOpticalFlowPyrLK (voflag_*, include/vo_flow_flags.h), every odd
+// W of 5 .. 21: the search starts at the caller's guess, err is the min eigenvalue of the level-0 structure tensor.
 #include "vo_kernels.h"
 #include "vo_lkmath.h"
 
@@ -154,13 +156,24 @@ __device__ __forceinline__ void lk_cell_rows(const uint8_t *tile, int off, uint3
 // -- halfWin, the +-WIN admissibility tests, the 2 WIN^2 of the min-eigenvalue test, the 32 WIN^2 of err, the tile test and the
 // refill's centring -- and what a window below 21 adds (the masks of a row's last segment) is behind `if constexpr` too: for
 // WIN = 21 every expression is the constant it was.
-template <bool SPLIT, bool ERR, int WIN = LK_WIN>
+// FLAGS (lk_flow_flags_kernel<W>, with ERR): `flags`, wave-uniform, holds the bits of cv::calcOpticalFlowPyrLK's flags --
+//   VO_LK_USE_INITIAL_FLOW: at the deepest level the search starts at guess * 2^-level, the guess read from the feature's own
+//     output row (trk is in/out: one wave per feature, read at the top, written at the end).  The template side is untouched; a
+//     start anywhere goes through the ordinary cell entry (NaN rule, +-WIN admissibility, a first tile centred on the START corner).
+//   VO_LK_GET_MIN_EIGENVALS: err = minEig of the level-0 template, the exact expression of the min-eigenvalue test, of every point
+//     whose level-0 template window is admissible -- whatever its status ends as -- and 0 of any other; the L1 epilogue and the
+//     final in-bounds check that belongs to it do not run, with err == nullptr too (OpenCV: the block is skipped on the flag).
+// Everything FLAGS adds is behind `if constexpr`, or -- the test in front of the final check -- a condition that folds to the one it
+// was: written any other way, lk_flow_kernel's scalar moves come out in another order (profiles/flow.md, section 6.2).
+constexpr int VO_LK_USE_INITIAL_FLOW = 4, VO_LK_GET_MIN_EIGENVALS = 8;
+template <bool SPLIT, bool ERR, int WIN = LK_WIN, bool FLAGS = false>
 __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads,
                                                  const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
                                                  int n_frames, int fpg /* 1, 2, 4 or 8 */, int ppp /* features per part */,
                                                  float2 *__restrict__ trk,     // [B][4][cap]
                                                  uint8_t *__restrict__ status, // [B][4][cap]
-                                                 const LkParams prm, int hop_begin, int hop_end, float *__restrict__ err = nullptr)
+                                                 const LkParams prm, int hop_begin, int hop_end, float *__restrict__ err = nullptr,
+                                                 int flags = 0)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_jt[LK_JT_H * LK_JT_W];
 
@@ -219,6 +232,13 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             if (level == prm.max_level) {
                 nextX = prevX;
                 nextY = prevY;
+                if constexpr (FLAGS) {
+                    if (flags & VO_LK_USE_INITIAL_FLOW) { // OpenCV: nextPts[ptidx] * (float)(1. / (1 << level)), one exact multiply
+                        const float2 g = trk[(size_t)frame * cap + f];
+                        nextX = unif(g.x) * scale;
+                        nextY = unif(g.y) * scale;
+                    }
+                }
             } else {
                 nextX = outX * 2.f;
                 nextY = outY * 2.f;
@@ -332,6 +352,11 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
 #endif
                 const float minEig = (t - sqrtf(s2)) / (float)(2 * WIN * WIN);
                 eig_ok = !(minEig < prm.min_eig);
+            }
+            if constexpr (FLAGS) {
+                // (the shortcut above still decides; the value itself is wanted once per feature, admitted or not)
+                if ((flags & VO_LK_GET_MIN_EIGENVALS) && level == 0)
+                    errv = (t - sqrtf(s2)) / (float)(2 * WIN * WIN);
             }
             if (!eig_ok || D < FLT_EPSILON) {
                 if (level == 0)
@@ -453,7 +478,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // final in-bounds check OpenCV performs at level 0 when an err vector is requested
             // (st == 1 here means the last cell entry was admitted and every delta since was finite: outX / outY are finite,
             // possibly huge -- both conversions then land on a rejected side, x86's INT_MIN and gfx950's saturated INT_MAX)
-            if (st && level == 0) {
+            // ((FLAGS) not in the min-eigenvalue mode: OpenCV skips the whole block on that flag)
+            if (st && level == 0 && (!FLAGS || !(flags & VO_LK_GET_MIN_EIGENVALS))) {
                 const int fx = vo_f2i(floorf(outX - halfWin)), fy = vo_f2i(floorf(outY - halfWin));
                 if (fx < -WIN || fx >= jw || fy < -WIN || fy >= jh)
                     st = 0;
@@ -495,8 +521,12 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             if (lane == 0) {
                 trk[(size_t)frame * cap + f] = make_float2(outX, outY);
                 status[(size_t)frame * cap + f] = (uint8_t)st;
-                if (err != nullptr)
-                    err[(size_t)frame * cap + f] = st ? errv : 0.f;
+                if (err != nullptr) {
+                    if constexpr (FLAGS) // (errv of the min-eigenvalue mode is 0 unless the level-0 template was admitted)
+                        err[(size_t)frame * cap + f] = ((flags & VO_LK_GET_MIN_EIGENVALS) || st) ? errv : 0.f;
+                    else
+                        err[(size_t)frame * cap + f] = st ? errv : 0.f;
+                }
             }
             return;
         }
@@ -572,6 +602,19 @@ __global__ VO_LK_FLOW_ATTRS void lk_flow_win_kernel(const PyrImage *__restrict__
     lk_circular_body<false, true, W>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err);
 }
 
+// The same hop with cv::calcOpticalFlowPyrLK's flags (voflag_*, include/vo_flow_flags.h): the body with FLAGS, one instantiation
+// per odd W of 5 .. 21 -- 21 included: lk_flow_kernel stays what it is -- and the two flag bits as a wave-uniform argument, not as
+// template parameters (27 more copies of this body).  `next` is in/out.  Register reports of the nine: profiles/flow.md.
+template <int W>
+__global__ VO_LK_FLOW_ATTRS void lk_flow_flags_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ pairs,
+                                                      const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
+                                                      int n_frames, int fpg, int ppp, float2 *__restrict__ next, // [B][cap], in/out
+                                                      uint8_t *__restrict__ status,                               // [B][cap]
+                                                      float *__restrict__ err /* [B][cap] or null */, LkParams prm, int flags)
+{
+    lk_circular_body<false, true, W, true>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err, flags);
+}
+
 #ifndef VO_HOST_EMUL
 // The launch geometry of the block numbering above: frames per group of 8 XCDs (the largest power of two <= min(8, n_frames)),
 // work items -- features, or the pair kernel's pairs of features (dev/lk_dev.hip) -- per part of a frame's list, and the grid.
@@ -624,6 +667,37 @@ void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, co
         VO_LK_WIN_CASE(5) VO_LK_WIN_CASE(7) VO_LK_WIN_CASE(9) VO_LK_WIN_CASE(11) VO_LK_WIN_CASE(13) VO_LK_WIN_CASE(15) VO_LK_WIN_CASE(17)
         VO_LK_WIN_CASE(19)
 #undef VO_LK_WIN_CASE
+    }
+}
+
+// launch_lk_flow_win with flags (VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS): 0 is launch_lk_flow_win itself, anything else
+// lk_flow_flags_kernel<win>, d_next in/out.  Preconditions: win as there, no other bit in flags.
+template <int W>
+static void launch_lk_flow_flags_w(const LkGrid &g, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts,
+                                   const int *d_npts, int cap, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err,
+                                   const LkParams &prm, hipStream_t stream)
+{
+    hipLaunchKernelGGL(lk_flow_flags_kernel<W>, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
+                       d_next, d_status, d_err, prm, flags);
+}
+void launch_lk_flow_flags(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
+                          int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+{
+    if (flags == 0) {
+        launch_lk_flow_win(win, d_imgs, d_pairs, d_pts, d_npts, cap, max_pts, n_frames, d_next, d_status, d_err, prm, stream);
+        return;
+    }
+    if (max_pts <= 0 || n_frames <= 0 || (flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)))
+        return;
+    const LkGrid g = lk_grid(n_frames, max_pts);
+    switch (win) {
+#define VO_LK_FLAGS_CASE(W)                                                                                                     \
+    case W:                                                                                                                     \
+        launch_lk_flow_flags_w<W>(g, flags, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, d_next, d_status, d_err, prm, stream); \
+        break;
+        VO_LK_FLAGS_CASE(5) VO_LK_FLAGS_CASE(7) VO_LK_FLAGS_CASE(9) VO_LK_FLAGS_CASE(11) VO_LK_FLAGS_CASE(13) VO_LK_FLAGS_CASE(15)
+        VO_LK_FLAGS_CASE(17) VO_LK_FLAGS_CASE(19) VO_LK_FLAGS_CASE(21)
+#undef VO_LK_FLAGS_CASE
     }
 }
 

@@ -140,6 +140,11 @@ void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d
 // 5 .. 21 -- there is no kernel for any other window and nothing is launched for one
 void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                         int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
+// the same with cv::calcOpticalFlowPyrLK's flags (4: the search starts at the guess d_next holds, in/out; 8: err = min eigenvalue,
+// no final in-bounds check): lk_flow_flags_kernel<win>, every odd win of 5 .. 21; flags == 0 is launch_lk_flow_win.  Preconditions:
+// win as above and no other bit in flags -- nothing is launched otherwise
+void launch_lk_flow_flags(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
+                          int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,
                           int h, int threshold, int nonmax, unsigned long long *d_nmsmask,
                           int *d_rowcnt, int *d_rowoff,
