@@ -52,31 +52,45 @@ CASES = {
 }
 
 
+def freeze(want):
+    for arr in want:
+        if arr is not None:
+            arr.setflags(write=False)
+    return want
+
+
 def case(name, small_seq, orc):
     """dict(prev, next, pts, max_level, want=(next, status, err)) of a named case; the checker runs once per session"""
     if name not in _CACHE:
         a, b, p, ml = CASES[name]
         im, ps = images(small_seq), point_sets(small_seq)
-        want = orc.calc_optical_flow_pyr_lk(im[a], im[b], ps[p], max_level=ml)
-        for arr in want:
-            arr.setflags(write=False)
+        want = freeze(orc.calc_optical_flow_pyr_lk(im[a], im[b], ps[p], max_level=ml))
         _CACHE[name] = dict(prev=im[a], next=im[b], pts=ps[p], max_level=ml, want=want)
     return _CACHE[name]
 
 
+def random_draw(rng, seed, small_seq):
+    """(prev, next, pts, max_level): a crop of 64 .. 200 x 48 .. 160 of L0 -> L1, n of 0 .. 128 points (seed 0: none, seed 1: one)
+    uniform in [-25, w + 25] x [-25, h + 25], and a max_level of 0 .. 4"""
+    w, h = int(rng.integers(64, 201)), int(rng.integers(48, 161))
+    x0, y0 = int(rng.integers(0, 480 - w + 1)), int(rng.integers(0, 160 - h + 1))
+    n = 0 if seed == 0 else 1 if seed == 1 else int(rng.integers(0, 129))
+    prev = np.ascontiguousarray(small_seq["L"][0][y0:y0 + h, x0:x0 + w])
+    nxt = np.ascontiguousarray(small_seq["L"][1][y0:y0 + h, x0:x0 + w])
+    pts = np.stack([rng.uniform(-25, w + 25, n), rng.uniform(-25, h + 25, n)], -1).astype(np.float32).reshape(-1, 2)
+    return prev, nxt, pts, int(rng.integers(0, 5))
+
+
+def no_points():
+    return np.zeros((0, 2), np.float32), np.zeros(0, np.uint8), np.zeros(0, np.float32)
+
+
 def random_case(seed, small_seq, orc):
-    """crops of 64 .. 200 x 48 .. 160 of L0 -> L1, n of 0 .. 128 points uniform in [-25, w + 25] x [-25, h + 25]"""
+    """random_draw of generator 1000 + seed, tracked at its max_level"""
     key = ("random", seed)
     if key not in _CACHE:
-        rng = np.random.default_rng(1000 + seed)
-        w, h = int(rng.integers(64, 201)), int(rng.integers(48, 161))
-        x0, y0 = int(rng.integers(0, 480 - w + 1)), int(rng.integers(0, 160 - h + 1))
-        n = 0 if seed == 0 else 1 if seed == 1 else int(rng.integers(0, 129))
-        prev = np.ascontiguousarray(small_seq["L"][0][y0:y0 + h, x0:x0 + w])
-        nxt = np.ascontiguousarray(small_seq["L"][1][y0:y0 + h, x0:x0 + w])
-        pts = np.stack([rng.uniform(-25, w + 25, n), rng.uniform(-25, h + 25, n)], -1).astype(np.float32).reshape(-1, 2)
-        ml = int(rng.integers(0, 5))
-        want = orc.calc_optical_flow_pyr_lk(prev, nxt, pts, max_level=ml) if n else (np.zeros((0, 2), np.float32), np.zeros(0, np.uint8), np.zeros(0, np.float32))
+        prev, nxt, pts, ml = random_draw(np.random.default_rng(1000 + seed), seed, small_seq)
+        want = orc.calc_optical_flow_pyr_lk(prev, nxt, pts, max_level=ml) if len(pts) else no_points()
         _CACHE[key] = dict(prev=prev, next=nxt, pts=pts, max_level=ml, want=want)
     return _CACHE[key]
 

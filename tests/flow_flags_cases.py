@@ -43,13 +43,6 @@ def ref_lib():
     return _lib
 
 
-def _freeze(t):
-    for a in t:
-        if a is not None:
-            a.setflags(write=False)
-    return t
-
-
 def driver(prev, nxt, pts, guess, win=21, max_level=3, max_count=30, eps=0.01, min_eig=1e-3, want_err=True):
     """the checker started at `guess`: (next [n, 2], status [n], err [n] or None)"""
     prev, nxt = np.ascontiguousarray(prev, np.uint8), np.ascontiguousarray(nxt, np.uint8)
@@ -94,9 +87,9 @@ def guess_case(kind, win, lk_max_level, small_seq, orc):
             guess = (pts + np.random.default_rng(7).uniform(-6, 6, pts.shape)).astype(np.float32)
         e = wc.depth(480, 160, lk_max_level)
         _CACHE[key] = dict(prev=prev, next=nxt, pts=pts, guess=guess, win=win, lk_max_level=lk_max_level, max_level=e,
-                           want=_freeze(driver(prev, nxt, pts, guess, win=win, max_level=e)),
-                           want_no_err=_freeze(driver(prev, nxt, pts, guess, win=win, max_level=e, want_err=False)),
-                           plain=_freeze(orc.calc_optical_flow_pyr_lk(prev, nxt, pts, win=win, max_level=e)))
+                           want=fc.freeze(driver(prev, nxt, pts, guess, win=win, max_level=e)),
+                           want_no_err=fc.freeze(driver(prev, nxt, pts, guess, win=win, max_level=e, want_err=False)),
+                           plain=fc.freeze(orc.calc_optical_flow_pyr_lk(prev, nxt, pts, win=win, max_level=e)))
     return _CACHE[key]
 
 
@@ -122,7 +115,7 @@ def adversarial_case(win, small_seq, orc):
         with np.errstate(over="ignore"):
             for i, v in enumerate(ADVERSARIAL):
                 guess[i, i & 1] = np.float32(v)
-        _CACHE[key] = dict(c, guess=guess, want=_freeze(driver(c["prev"], c["next"], c["pts"], guess, win=win, max_level=c["max_level"])),
+        _CACHE[key] = dict(c, guess=guess, want=fc.freeze(driver(c["prev"], c["next"], c["pts"], guess, win=win, max_level=c["max_level"])),
                            plain=c["want"])
     return _CACHE[key]
 
@@ -172,7 +165,7 @@ def eig_set(name, win, small_seq, orc):
         if (name, win) in EIG_BELOW_THRESHOLD:
             assert int(below.sum()) == EIG_BELOW_THRESHOLD[(name, win)]
         _CACHE[key] = dict(img=img, pts=pts, win=win, adm=adm, verifiable=ver, below=below,
-                           want_no_err=_freeze(plain_no_err(orc, img, img, pts, win=win, max_level=0)))
+                           want_no_err=fc.freeze(plain_no_err(orc, img, img, pts, win=win, max_level=0)))
     return _CACHE[key]
 
 
@@ -215,6 +208,6 @@ def final_check_case(small_seq, orc):
         flips = (no_err[1] == 1) & (with_err[1] == 0)
         assert len(pts) == 3618 and flips.sum() >= 10 and np.array_equal(fc.bits(no_err[0]), fc.bits(with_err[0]))
         assert not ((no_err[1] == 0) & (with_err[1] == 1)).any()
-        _CACHE[key] = dict(prev=im["cL0"], next=im["cL1"], pts=pts, win=21, lk_max_level=3, max_level=1, max_count=2, want_no_err=_freeze(no_err),
-                           with_err=_freeze(with_err), flips=flips)
+        _CACHE[key] = dict(prev=im["cL0"], next=im["cL1"], pts=pts, win=21, lk_max_level=3, max_level=1, max_count=2, want_no_err=fc.freeze(no_err),
+                           with_err=fc.freeze(with_err), flips=flips)
     return _CACHE[key]

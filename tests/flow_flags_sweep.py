@@ -4,59 +4,23 @@ Every such call must come back with the documented code -- never a fault, never 
 a refused call writes nothing.  Run as a SCRIPT in a child process by tests/test_gpu_flow_flags.py (a fault would otherwise take the
 test session down with it); prints one JSON object {"checked": n, "covered": [...], "failures": [...]} and exits 0 iff there is no
 failure.  Needs a GPU (vo_create)."""
-import ctypes as C
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from visual_odom_amd import _lib  # noqa: E402
+from flow_sweep_common import ARG, CAP, FRAMES, OK, SENT, STATE, H, W, Sweep, _lib, vp
 
-OK, ARG, STATE = 0, -1, -3
-W, H, CAP, FRAMES = 320, 96, 256, 2
 BAD_FLAGS = (1, 2, 3, 5, 16, 20, 0x100, -1, -4)
 BAD_WINDOWS = (-1, 0, 4, 6, 22, 23)
 GUESS, EIG = _lib.FLAG_USE_INITIAL_FLOW, _lib.FLAG_GET_MIN_EIGENVALS
 
 
 def main():
-    lib = _lib.load()
-    fails, covered, checked = [], set(), [0]
-    ctx = _lib.Context(0, W, H, CAP, FRAMES)
-    h = ctx.h
-
-    def vp(a):
-        return a.ctypes.data_as(C.c_void_p)
-
-    def expect(name, want, *args):
-        covered.add(name)
-        checked[0] += 1
-        rc = getattr(lib, name)(*args)
-        if rc != want:
-            fails.append("%s%r -> %d, expected %d" % (name, tuple(str(a)[:20] for a in args[1:]), rc, want))
-        elif rc < 0 and args[0] is not None and not lib.vo_last_error(args[0]):
-            fails.append("%s: vo_last_error is empty after %d" % (name, rc))
-        return rc
-
-    rng = np.random.default_rng(3)
-    img = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    pts = np.full((CAP + 8, 2), 40.0, np.float32)
-    SENT = 77.25
-    out = np.full((CAP + 8, 2), SENT, np.float32)   # (in/out: a refused call leaves the guesses as they were)
-    st = np.full(CAP + 8, 9, np.uint8)
-    err = np.full(CAP + 8, SENT, np.float32)
-    idx = np.full(CAP + 8, -5, np.int32)
-    n_out = C.c_int(-5)
-    pn = C.addressof(n_out)
-    I, P, O, S, E, K = vp(img), vp(pts), vp(out), vp(st), vp(err), vp(idx)
+    s = Sweep()
+    lib, ctx, h, fails, expect, untouched = s.lib, s.ctx, s.h, s.fails, s.expect, s.untouched
+    img, pts, out, st, err, pn = s.img, s.pts, s.out, s.st, s.err, s.pn
+    I, P, O, S, E, K = s.pointers
     T, F, RUN, SET = "voflag_track", "voflag_feature_tracking", "voflag_batch_run", "voflag_batch_set_guess"
-
-    def untouched(what):
-        if (out != SENT).any() or (st != 9).any() or (err != SENT).any() or (idx != -5).any() or n_out.value != -5:
-            fails.append(what + " wrote to its outputs")
 
     # ---- flags and windows without a kernel: refused before anything else happens ----
     for fl in BAD_FLAGS:
@@ -165,9 +129,7 @@ def main():
     expect(SET, STATE, h, 0, P, 4)
     ctx.batch_configure(4, W, H, 1)                        # leaves the loop
     expect(T, OK, h, I, I, W, H, W, P, 4, 15, GUESS, O, S, E)
-    ctx.close()
-    print(json.dumps({"checked": checked[0], "covered": sorted(covered), "failures": fails}))
-    return 1 if fails else 0
+    return s.report()
 
 
 if __name__ == "__main__":

@@ -3,51 +3,18 @@ strides, pair indices outside the table, frames beyond the table, calls in the w
 the documented code -- never a fault, never a silent success -- and leave vo_last_error filled.  Run as a SCRIPT in a child
 process by tests/test_gpu_flow.py (a fault would otherwise take the test session down with it); prints one JSON object
 {"checked": n, "covered": [...], "failures": [...]} and exits 0 iff there is no failure.  Needs a GPU (vo_create)."""
-import ctypes as C
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from visual_odom_amd import _lib  # noqa: E402
-
-OK, ARG, STATE = 0, -1, -3
-W, H, CAP, FRAMES = 320, 96, 256, 2
+from flow_sweep_common import ARG, CAP, FRAMES, OK, SENT, STATE, H, W, Sweep, _lib, vp
 
 
 def main():
-    lib = _lib.load()
-    fails, covered, checked = [], set(), [0]
-    ctx = _lib.Context(0, W, H, CAP, FRAMES)
-    h = ctx.h
-
-    def vp(a):
-        return a.ctypes.data_as(C.c_void_p)
-
-    def expect(name, want, *args):
-        covered.add(name)
-        checked[0] += 1
-        rc = getattr(lib, name)(*args)
-        if rc != want:
-            fails.append("%s%r -> %d, expected %d" % (name, tuple(str(a)[:20] for a in args[1:]), rc, want))
-        elif rc < 0 and args[0] is not None and not lib.vo_last_error(args[0]):
-            fails.append("%s: vo_last_error is empty after %d" % (name, rc))
-        return rc
-
-    rng = np.random.default_rng(3)
-    img = rng.integers(0, 256, (H, W), dtype=np.uint8)
-    pts = np.full((CAP + 8, 2), 40.0, np.float32)
-    SENT = 77.25
-    out = np.full((CAP + 8, 2), SENT, np.float32)
-    st = np.full(CAP + 8, 9, np.uint8)
-    err = np.full(CAP + 8, SENT, np.float32)
-    idx = np.full(CAP + 8, -5, np.int32)
-    n_out = C.c_int(-5)
-    pn = C.addressof(n_out)
-    I, P, O, S, E, K = vp(img), vp(pts), vp(out), vp(st), vp(err), vp(idx)
+    s = Sweep()
+    ctx, h, fails, expect = s.ctx, s.h, s.fails, s.expect
+    img, pts, out, st, err, idx, n_out, pn = s.img, s.pts, s.out, s.st, s.err, s.idx, s.n_out, s.pn
+    I, P, O, S, E, K = s.pointers
 
     # ---- voflow_track ----
     T = "voflow_track"
@@ -141,9 +108,7 @@ def main():
     expect(GET, STATE, h, 0, O, S, E, 4)
     ctx.batch_configure(4, W, H, 1)                        # leaves the loop
     expect(T, OK, h, I, I, W, H, W, P, 4, O, S, E)
-    ctx.close()
-    print(json.dumps({"checked": checked[0], "covered": sorted(covered), "failures": fails}))
-    return 1 if fails else 0
+    return s.report()
 
 
 if __name__ == "__main__":

@@ -41,12 +41,6 @@ CASES = {
 }
 
 
-def _freeze(want):
-    for arr in want:
-        arr.setflags(write=False)
-    return want
-
-
 def case(name, win, small_seq, orc):
     """dict(prev, next, pts, win, lk_max_level, max_level = E, want = (next, status, err))"""
     key = (name, win)
@@ -56,7 +50,7 @@ def case(name, win, small_seq, orc):
         pts = lattice(96, 64, win) if p == "lattice" else fc.point_sets(small_seq)[p]
         h, w = im[a].shape
         e = depth(w, h, ml)
-        want = _freeze(orc.calc_optical_flow_pyr_lk(im[a], im[b], pts, win=win, max_level=e))
+        want = fc.freeze(orc.calc_optical_flow_pyr_lk(im[a], im[b], pts, win=win, max_level=e))
         _CACHE[key] = dict(prev=im[a], next=im[b], pts=pts, win=win, lk_max_level=ml, max_level=e, want=want)
     return _CACHE[key]
 
@@ -118,16 +112,8 @@ def random_case(seed, small_seq, orc):
         order = np.random.default_rng(77).permutation(np.repeat(WINDOWS, 2))
         assert 0 <= seed < N_RANDOM == len(order)
         win = int(order[seed])
-        rng = np.random.default_rng(2000 + seed)
-        w, h = int(rng.integers(64, 201)), int(rng.integers(48, 161))
-        x0, y0 = int(rng.integers(0, 480 - w + 1)), int(rng.integers(0, 160 - h + 1))
-        n = 0 if seed == 0 else 1 if seed == 1 else int(rng.integers(0, 129))
-        prev = np.ascontiguousarray(small_seq["L"][0][y0:y0 + h, x0:x0 + w])
-        nxt = np.ascontiguousarray(small_seq["L"][1][y0:y0 + h, x0:x0 + w])
-        pts = np.stack([rng.uniform(-25, w + 25, n), rng.uniform(-25, h + 25, n)], -1).astype(np.float32).reshape(-1, 2)
-        ml = int(rng.integers(0, 5))
-        e = depth(w, h, ml)
-        want = orc.calc_optical_flow_pyr_lk(prev, nxt, pts, win=win, max_level=e) if n else \
-            (np.zeros((0, 2), np.float32), np.zeros(0, np.uint8), np.zeros(0, np.float32))
-        _CACHE[key] = dict(prev=prev, next=nxt, pts=pts, win=win, lk_max_level=ml, max_level=e, want=_freeze(want))
+        prev, nxt, pts, ml = fc.random_draw(np.random.default_rng(2000 + seed), seed, small_seq)
+        e = depth(prev.shape[1], prev.shape[0], ml)
+        want = orc.calc_optical_flow_pyr_lk(prev, nxt, pts, win=win, max_level=e) if len(pts) else fc.no_points()
+        _CACHE[key] = dict(prev=prev, next=nxt, pts=pts, win=win, lk_max_level=ml, max_level=e, want=fc.freeze(want))
     return _CACHE[key]

@@ -1,8 +1,10 @@
 // flow_emu.cpp -- TEST ONLY.  Executes the product's two-image tracker on the CPU through the coroutine SIMT emulator of hip_emu.h:
-// pyr_pass_kernel (pyramid.hip) over the two images, lk_flow_kernel (lk.hip) over the points, flow_compact_kernel (post.hip) over
-// the result.  Every level of both pyramids is a heap block of its own of exactly stride x (h + 2 VO_BY) bytes / dwords, so that
-// under AddressSanitizer a load outside a level aborts (the err epilogue's tile refill included).  Two forms: a shared library
-// for tests/test_flow_emulation.py, and -- with -DFLOW_EMU_MAIN -- a stand-alone program (the sanitizer tier: built with
+// pyr_pass_kernel (pyramid.hip) over the two images, the LK kernel of a window and flags (lk.hip: lk_flow_kernel,
+// lk_flow_win_kernel<W>, lk_flow_flags_kernel<W>, picked by the product's own lk_for_window / lk_flow_route and launched over the
+// product's lk_grid) over the points, flow_compact_kernel (post.hip) over the result.  Every level of both pyramids is a heap block
+// of its own of exactly stride x (h + 2 VO_BY) bytes / dwords (emu_pyramid.h), so that under AddressSanitizer a load outside a
+// level aborts -- the masked lanes', the err epilogue's tile refill and a far-off start's tile included.  Two forms: a shared
+// library for tests/flow_emu.py, and -- with -DFLOW_EMU_MAIN -- a stand-alone program (the sanitizer tier: built with
 // -fsanitize=address,undefined and run as a child, nothing instrumented is loaded into python) that reads one case from a file
 // and writes the results to another.  Not a product path.
 #include "hip_emu.h"
@@ -11,72 +13,21 @@
 #include "../../visual_odom_amd/csrc/pyramid.hip"
 #include "../../visual_odom_amd/csrc/post.hip"
 
-#include <memory>
-#include <vector>
-
-namespace {
-
-// the geometry libvo_hip plans (capi.hip: plan_levels / level_stride)
-struct Plan {
-    int levels = 0;
-    int lw[VO_MAX_LEVELS], lh[VO_MAX_LEVELS], ls[VO_MAX_LEVELS];
-};
-
-Plan plan(int w, int h, int max_level)
-{
-    Plan p;
-    int cw = w, ch = h, l = 0;
-    for (;; l++) {
-        p.lw[l] = cw;
-        p.lh[l] = ch;
-        p.ls[l] = (VO_BX + cw + VO_BY + 15) / 16 * 16;
-        const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-        if (l == max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
-            break;
-        cw = nw;
-        ch = nh;
-    }
-    p.levels = l + 1;
-    return p;
-}
-
-struct Heap {
-    std::vector<std::unique_ptr<uint8_t[]>> pix;
-    std::vector<std::unique_ptr<uint32_t[]>> der;
-    std::vector<vo::PyrImage> tab;
-    Heap(const Plan &p, const uint8_t *const *imgs, int n_img, int w, int h) : tab((size_t)n_img)
-    {
-        for (int i = 0; i < n_img; i++) {
-            memset(&tab[i], 0, sizeof(vo::PyrImage));
-            for (int l = 0; l < p.levels; l++) {
-                const size_t n = (size_t)p.ls[l] * (p.lh[l] + 2 * VO_BY), org = (size_t)VO_BY * p.ls[l] + VO_BX;
-                pix.emplace_back(new uint8_t[n]);
-                der.emplace_back(new uint32_t[n]);
-                memset(pix.back().get(), 0xA5, n); // (a read of border the build did not write shows up)
-                memset(der.back().get(), 0, 4 * n);
-                tab[i].lvl[l] = pix.back().get() + org;
-                tab[i].der[l] = der.back().get() + org;
-                tab[i].w[l] = p.lw[l];
-                tab[i].h[l] = p.lh[l];
-                tab[i].stride[l] = p.ls[l];
-            }
-            for (int y = 0; y < h; y++)
-                memcpy(tab[i].lvl[0] + (ptrdiff_t)y * p.ls[0], imgs[i] + (size_t)y * w, (size_t)w);
-        }
-    }
-};
-
-} // namespace
+#include "emu_pyramid.h"
 
 extern "C" {
 
-// prev, next: tight w x h gray images; pts [n][2].  next_out [n][2], status [n], err [n] or null (the kernel's "not requested").
-// n_frames copies of the pair are tracked as frames of one launch (every frame must give the same bits: frame -> XCD numbering);
-// the outputs are those of frame `frame`.  Returns the number of pyramid levels built.
-int fe_track(const uint8_t *prev, const uint8_t *next, int w, int h, int max_level, const float *pts, int n, int max_count, double eps,
-             float min_eig, float *next_out, uint8_t *status, float *err, int n_frames, int frame)
+// prev, next: tight w x h gray images; pts [n][2].  n_frames frames of the pair in one launch (the frame -> XCD numbering); frame
+// f tracks the first counts[f] of the n points (counts == null: n in every frame).  next_io [n_frames][n][2]: the guesses in (read
+// with flags & 4 only), the results out; status [n_frames][n]; err [n_frames][n] or null (the kernel's "not requested").  Rows
+// from counts[f] on come back as the kernel left them: untouched (guesses / 0xA5 / -1).  Returns the number of pyramid levels
+// built, -1 for a window or flags without a kernel.
+int fe_track(const uint8_t *prev, const uint8_t *next, int w, int h, int max_level, const float *pts, int n, int win, int flags, int max_count,
+             double eps, float min_eig, float *next_io, uint8_t *status, float *err, int n_frames, const int *counts)
 {
     using namespace vo;
+    if (!lk_for_window(win, [](auto) {}) || (flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)) || n_frames < 1)
+        return -1;
     const Plan p = plan(w, h, max_level);
     const uint8_t *imgs[2] = {prev, next};
     Heap heap(p, imgs, 2, w, h);
@@ -98,23 +49,37 @@ int fe_track(const uint8_t *prev, const uint8_t *next, int w, int h, int max_lev
     const int cap = n + 3; // (cap != n: the frame stride of the outputs is the capacity)
     std::vector<Quad> pairs((size_t)n_frames, Quad{0, 1, 1, 0});
     std::vector<int> npts((size_t)n_frames, n);
+    int most = counts ? 0 : n;
+    for (int f = 0; counts && f < n_frames; f++) {
+        npts[(size_t)f] = counts[f] < 0 ? 0 : counts[f] > n ? n : counts[f];
+        most = npts[(size_t)f] > most ? npts[(size_t)f] : most;
+    }
     std::vector<float2> in((size_t)n_frames * cap), out((size_t)n_frames * cap, make_float2(123456.f, -7.f));
     std::vector<uint8_t> st((size_t)n_frames * cap, (uint8_t)0xA5);
     std::vector<float> er((size_t)n_frames * cap, -1.f);
-    for (int f = 0; f < n_frames; f++)
+    for (int f = 0; f < n_frames; f++) {
         memcpy(&in[(size_t)f * cap], pts, sizeof(float2) * (size_t)n);
-    // launch_lk_flow's grid
-    const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
-    const int parts = 8 / fpg, ppp = (n + parts - 1) / parts, groups = (n_frames + fpg - 1) / fpg;
-    for (unsigned b = 0; b < (unsigned)(8 * groups * ppp); b++)
-        emu::run_block(64, b, 0, 0, [&] {
-            lk_flow_kernel(d_imgs, pairs.data(), in.data(), npts.data(), cap, n_frames, fpg, ppp, out.data(), st.data(),
-                           err ? er.data() : nullptr, prm);
+        if (flags & VO_LK_USE_INITIAL_FLOW)
+            memcpy(&out[(size_t)f * cap], next_io + (size_t)f * 2 * n, sizeof(float2) * (size_t)n);
+    }
+    if (most > 0) { // launch_lk_flow of lk.hip over the largest count (the library's max_pts), a loop over the blocks as the launch
+        const LkGrid g = lk_grid(n_frames, most);
+        lk_for_window(win, [&](auto wc) {
+            lk_flow_route<decltype(wc)::value>(flags, [&](auto kernel, auto... tail) {
+                for (int b = 0; b < g.blocks; b++)
+                    emu::run_block(64, (unsigned)b, 0, 0, [&] {
+                        kernel(d_imgs, pairs.data(), in.data(), npts.data(), cap, n_frames, g.fpg, g.ppp, out.data(), st.data(),
+                               err ? er.data() : nullptr, prm, tail...);
+                    });
+            });
         });
-    memcpy(next_out, &out[(size_t)frame * cap], sizeof(float2) * (size_t)n);
-    memcpy(status, &st[(size_t)frame * cap], (size_t)n);
-    if (err)
-        memcpy(err, &er[(size_t)frame * cap], sizeof(float) * (size_t)n);
+    }
+    for (int f = 0; f < n_frames; f++) {
+        memcpy(next_io + (size_t)f * 2 * n, &out[(size_t)f * cap], sizeof(float2) * (size_t)n);
+        memcpy(status + (size_t)f * n, &st[(size_t)f * cap], (size_t)n);
+        if (err)
+            memcpy(err + (size_t)f * n, &er[(size_t)f * cap], sizeof(float) * (size_t)n);
+    }
     return p.levels;
 }
 
@@ -132,31 +97,34 @@ int fe_compact(const float *pts0, const float *next, uint8_t *status, int n, flo
 
 #ifdef FLOW_EMU_MAIN
 #include <stdio.h>
-// in:  int32 w, h, max_level, n, max_count; float64 eps; float32 min_eig; uint8 prev [h][w], next [h][w]; float32 pts [n][2]
+// in:  int32 w, h, max_level, n, max_count, win, flags; float64 eps; float32 min_eig; uint8 prev [h][w], next [h][w];
+//      float32 pts [n][2], guess [n][2]
 // out: float32 next [n][2]; float32 err [n]; uint8 status [n]; then the compaction: int32 n_out; uint8 status [n]; int32 idx [n]
 int main(int argc, char **argv)
 {
     if (argc != 3)
         return 2;
     FILE *f = fopen(argv[1], "rb");
-    int32_t hd[5];
+    int32_t hd[7];
     double eps;
     float min_eig;
     if (!f || fread(hd, sizeof(hd), 1, f) != 1 || fread(&eps, 8, 1, f) != 1 || fread(&min_eig, 4, 1, f) != 1)
         return 3;
     const int w = hd[0], h = hd[1], n = hd[3];
     std::vector<uint8_t> prev((size_t)w * h), next((size_t)w * h), st((size_t)n + 1), st2;
-    std::vector<float> pts((size_t)2 * n + 2), out((size_t)2 * n + 2), err((size_t)n + 1), o0((size_t)2 * n + 2), o1((size_t)2 * n + 2);
+    std::vector<float> pts((size_t)2 * n + 2), io((size_t)2 * n + 2), err((size_t)n + 1), o0((size_t)2 * n + 2), o1((size_t)2 * n + 2);
     std::vector<int32_t> idx((size_t)n + 1, -1);
     if (fread(prev.data(), 1, prev.size(), f) != prev.size() || fread(next.data(), 1, next.size(), f) != next.size() ||
-        fread(pts.data(), 8, (size_t)n, f) != (size_t)n)
+        fread(pts.data(), 8, (size_t)n, f) != (size_t)n || fread(io.data(), 8, (size_t)n, f) != (size_t)n)
         return 3;
     fclose(f);
-    fe_track(prev.data(), next.data(), w, h, hd[2], pts.data(), n, hd[4], eps, min_eig, out.data(), st.data(), err.data(), 1, 0);
+    if (fe_track(prev.data(), next.data(), w, h, hd[2], pts.data(), n, hd[5], hd[6], hd[4], eps, min_eig, io.data(), st.data(), err.data(), 1,
+                 nullptr) < 0)
+        return 4;
     st2 = st;
-    const int32_t n_out = fe_compact(pts.data(), out.data(), st2.data(), n, o0.data(), o1.data(), idx.data(), 256);
+    const int32_t n_out = fe_compact(pts.data(), io.data(), st2.data(), n, o0.data(), o1.data(), idx.data(), 256);
     f = fopen(argv[2], "wb");
-    if (!f || fwrite(out.data(), 8, (size_t)n, f) != (size_t)n || fwrite(err.data(), 4, (size_t)n, f) != (size_t)n ||
+    if (!f || fwrite(io.data(), 8, (size_t)n, f) != (size_t)n || fwrite(err.data(), 4, (size_t)n, f) != (size_t)n ||
         fwrite(st.data(), 1, (size_t)n, f) != (size_t)n || fwrite(&n_out, 4, 1, f) != 1 || fwrite(st2.data(), 1, (size_t)n, f) != (size_t)n ||
         fwrite(idx.data(), 4, (size_t)n, f) != (size_t)n)
         return 6;

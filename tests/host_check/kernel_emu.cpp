@@ -12,75 +12,9 @@
 #include "../../visual_odom_amd/csrc/essential.hip"
 #include "../../visual_odom_amd/csrc/seq.hip"
 
-#include <memory>
-#include <vector>
+#include "emu_pyramid.h"
 
 namespace {
-
-struct Plan {
-    int levels = 0;
-    int lw[VO_MAX_LEVELS], lh[VO_MAX_LEVELS], ls[VO_MAX_LEVELS];
-    size_t off[VO_MAX_LEVELS], total = 0;
-};
-
-// the geometry libvo_hip plans in capi.hip (plan_levels / level_stride)
-Plan plan(int w, int h, int max_level)
-{
-    Plan p;
-    int cw = w, ch = h, l = 0;
-    size_t off = 0;
-    for (;; l++) {
-        p.lw[l] = cw;
-        p.lh[l] = ch;
-        p.ls[l] = (VO_BX + cw + VO_BY + 15) / 16 * 16;
-        p.off[l] = off;
-        off += (size_t)p.ls[l] * (ch + 2 * VO_BY);
-        off = (off + 255) / 256 * 256;
-        int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-        if (l == max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
-            break;
-        cw = nw;
-        ch = nh;
-    }
-    p.levels = l + 1;
-    p.total = off;
-    return p;
-}
-
-// The image table of the emulated runs: every level of every image in its OWN heap block of exactly ls * (lh + 2 VO_BY)
-// bytes / dwords.  That is tighter than the product's table (capi.hip: levels one after the other at 256-byte boundaries, the
-// images one after the other, vo_create's worst-case slack behind the last): under AddressSanitizer (VO_SANITIZE=1,
-// tests/test_sanitize.py) any kernel access outside a level's bordered allocation aborts, whichever level, image or pyramid
-// depth it belongs to.  Pixels are poisoned with 0xA5 (a read of border the build did not write shows up), derivatives zero.
-struct Heap {
-    Plan p;
-    std::vector<std::unique_ptr<uint8_t[]>> pix;
-    std::vector<std::unique_ptr<uint32_t[]>> der;
-    std::vector<vo::PyrImage> tab;
-    size_t level_elems(int l) const { return (size_t)p.ls[l] * (p.lh[l] + 2 * VO_BY); }
-    uint8_t *pix_block(int i, int l) { return pix[(size_t)i * p.levels + l].get(); }
-    uint32_t *der_block(int i, int l) { return der[(size_t)i * p.levels + l].get(); }
-    Heap(const Plan &plan_, int n_img, const uint8_t *imgs, int w, int h) : p(plan_), tab(n_img)
-    {
-        for (int i = 0; i < n_img; i++) {
-            memset(&tab[i], 0, sizeof(vo::PyrImage));
-            for (int l = 0; l < p.levels; l++) {
-                const size_t n = level_elems(l), org = (size_t)VO_BY * p.ls[l] + VO_BX;
-                pix.emplace_back(new uint8_t[n]);
-                der.emplace_back(new uint32_t[n]);
-                memset(pix.back().get(), 0xA5, n);
-                memset(der.back().get(), 0, 4 * n);
-                tab[i].lvl[l] = pix.back().get() + org;
-                tab[i].der[l] = der.back().get() + org;
-                tab[i].w[l] = p.lw[l];
-                tab[i].h[l] = p.lh[l];
-                tab[i].stride[l] = p.ls[l];
-            }
-            for (int y = 0; y < h; y++)
-                memcpy(tab[i].lvl[0] + (ptrdiff_t)y * p.ls[0], imgs + ((size_t)i * h + y) * w, w);
-        }
-    }
-};
 
 int g_bucket_threads = 256; // ke_set_bucket_threads: width of bucket_kernel's workgroup (256, or 1024 as in launches of <= 4 frames)
 int g_fast_big = 0; // ke_set_fast_big: tile form of the FAST kernel (0: 64 x 16, 1: 64 x 32, 2: 128 x 32)
@@ -140,15 +74,9 @@ void ke_set_pyr_lds(int on) { g_pyr_lds = on; }
 int ke_pass_decode_check(int w, int h, int max_level, int n)
 {
     using namespace vo;
-    int lw[VO_MAX_LEVELS], lh[VO_MAX_LEVELS], ls[VO_MAX_LEVELS], L = 0;
-    for (int cw = w, ch = h;; L++) {
-        lw[L] = cw; lh[L] = ch; ls[L] = (VO_BX + cw + VO_BY + 15) / 16 * 16;
-        const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-        if (L == max_level || L + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21) break;
-        cw = nw; ch = nh;
-    }
-    L++;
-    const PassPlan pp = pass_plan(L, lw, lh, ls);
+    const Plan p = plan(w, h, max_level);
+    const int L = p.levels;
+    const PassPlan pp = pass_plan(L, p.lw, p.lh, p.ls);
     for (int l = 0; l < L; l++) {
         const uint32_t nci = (uint32_t)pp.nci[l], wpi = nci * (uint32_t)pp.gy[l];
         const uint32_t per = (uint32_t)pass_images_per_launch(pp, l), ni = n > 0 && (uint32_t)n < per ? (uint32_t)n : per; // (more images: a second launch)
@@ -451,7 +379,7 @@ int ke_bordered_level(const uint8_t *img, int w, int h, int max_level, int level
     Plan p = plan(w, h, max_level);
     if (level < 0 || level >= p.levels)
         return -1;
-    Heap heap(p, 1, img, w, h);
+    Heap heap(p, &img, 1, w, h);
     build_pyramids(p, heap.tab.data(), 1);
     const int n = (int)heap.level_elems(level);
     if (n > cap)
@@ -554,7 +482,10 @@ int ke_run(const uint8_t *imgs, int n_img, int w, int h, int max_level, int want
 {
     using namespace vo;
     Plan p = plan(w, h, max_level);
-    Heap heap(p, n_img, imgs, w, h);
+    std::vector<const uint8_t *> img_ptr;
+    for (int i = 0; i < n_img; i++)
+        img_ptr.push_back(imgs + (size_t)i * w * h);
+    Heap heap(p, img_ptr.data(), n_img, w, h);
     std::vector<PyrImage> &tab = heap.tab;
     const PyrImage *d_imgs = tab.data();
     build_pyramids(p, d_imgs, n_img);
@@ -643,7 +574,7 @@ int ke_detect(const uint8_t *img, int w, int h, int threshold, int nonmax, int d
 {
     using namespace vo;
     Plan p = plan(w, h, 0);
-    Heap heap(p, 1, img, w, h); // (a one-level pyramid: nothing follows level 0)
+    Heap heap(p, &img, 1, w, h); // (a one-level pyramid: nothing follows level 0)
     PyrImage &im = heap.tab[0];
     Quad quad{0, 0, 0, 0};
     const int fcap = 1 << 17;

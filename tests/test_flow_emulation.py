@@ -1,65 +1,29 @@
 """The two-image tracker's kernels executed on the CPU through the coroutine SIMT emulator (tests/host_check/hip_emu.h +
-flow_emu.cpp): pyr_pass_kernel over the two images, lk_flow_kernel (visual_odom_amd/csrc/lk.hip: one hop + the err epilogue) and
-flow_compact_kernel (post.hip: deleteUnmatchFeatures), from the product sources.  Positions, status and err are compared BIT FOR
-BIT with the checker's calcOpticalFlowPyrLK (accum_mode 0), every point; the compaction with the python restatement of
-feature.cpp:20-37 applied to the checker's outputs.  tests/flow_cases.py holds the cases and asserts, on the checker's side,
-that each comparison sees both statuses, tracked points that left the image, and the zero-err rule.
+flow_emu.cpp, run through tests/flow_emu.py): pyr_pass_kernel over the two images, lk_flow_kernel (visual_odom_amd/csrc/lk.hip: one
+hop + the err epilogue) and flow_compact_kernel (post.hip: deleteUnmatchFeatures), from the product sources.  Positions, status
+and err are compared BIT FOR BIT with the checker's calcOpticalFlowPyrLK (accum_mode 0), every point; the compaction with the
+python restatement of feature.cpp:20-37 applied to the checker's outputs.  tests/flow_cases.py holds the cases and asserts, on the
+checker's side, that each comparison sees both statuses, tracked points that left the image, and the zero-err rule.
 
-The sanitizer tier is a STAND-ALONE program: the same harness with a main() of its own, every pyramid level in an exactly sized
-heap block, built with -fsanitize=address,undefined (runtimes linked statically) and run as a child.  Nothing instrumented is
-loaded into python.  Unit test of device code, not a product path."""
-import ctypes as C
-import os
-import subprocess
-
+The sanitizer tier is the same harness as a STAND-ALONE program (flow_emu.run_standalone).  Unit test of device code, not a
+product path."""
 import numpy as np
 import pytest
 
 import flow_cases as fc
-from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
-
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("flow_emu.cpp", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_tri.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
+import flow_emu as fe
+from flow_emu import compact as fe_compact
 
 
 @pytest.fixture(scope="module")
 def femu():
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    so = os.path.join(BUILD_DIR, "libflow_emu.so")
-    if _stale(so):
-        subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared"] + SAN_FLAGS + ["-o", so, os.path.join(SRC_DIR, "flow_emu.cpp")])
-    lib = C.CDLL(so)
-    lib.fe_track.restype = C.c_int
-    lib.fe_compact.restype = C.c_int
-    return lib
+    return fe.load()
 
 
-def fe_track(lib, prev, nxt, pts, max_level=3, max_count=30, eps=0.01, min_eig=1e-3, want_err=True, n_frames=1, frame=0):
-    h, w = prev.shape
-    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
-    n = len(pts)
-    out = np.zeros((max(n, 1), 2), np.float32)
-    st = np.zeros(max(n, 1), np.uint8)
-    err = np.zeros(max(n, 1), np.float32)
-    lib.fe_track(vp(np.ascontiguousarray(prev)), vp(np.ascontiguousarray(nxt)), w, h, max_level, vp(pts), n, max_count, C.c_double(eps),
-                 C.c_float(min_eig), vp(out), vp(st), vp(err) if want_err else None, n_frames, frame)
-    return out[:n], st[:n], (err[:n] if want_err else None)
-
-
-def fe_compact(lib, pts0, nxt, status, threads):
-    n = len(status)
-    st = status.copy()
-    o0, o1 = np.zeros((max(n, 1), 2), np.float32), np.zeros((max(n, 1), 2), np.float32)
-    idx = np.full(max(n, 1), -1, np.int32)
-    k = lib.fe_compact(vp(np.ascontiguousarray(pts0, np.float32)), vp(np.ascontiguousarray(nxt, np.float32)), vp(st), n, vp(o0), vp(o1), vp(idx), threads)
-    return o0[:k], o1[:k], st, idx[:k], k
+def fe_track(lib, prev, nxt, pts, max_level=3, want_err=True, n_frames=1, frame=0):
+    """the 21 x 21 window, no flags: lk_flow_kernel; the outputs of frame `frame` of the n_frames copies of the pair"""
+    c = dict(prev=prev, next=nxt, pts=pts, win=21, lk_max_level=max_level)
+    return fe.track(lib, c, want_err=want_err, n_frames=n_frames, frame=frame)[0]
 
 
 @pytest.mark.parametrize("name", list(fc.CASES))
@@ -128,32 +92,9 @@ def test_compaction_of_nothing_and_of_nan(femu):
 @pytest.mark.sanitize
 def test_flow_kernels_standalone_under_sanitizers(tmp_path, orc, small_seq):
     """ASan + UBSan over the kernel sources in a program of its own: exactly sized pyramid levels, no report, the same bits"""
-    out_dir = os.path.join(ROOT, "tests", "_build", "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "flow_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DFLOW_EMU_MAIN", "-o", exe, os.path.join(SRC_DIR, "flow_emu.cpp")])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     for name in ("crop", "lattice"):
         c = fc.case(name, small_seq, orc)
-        h, w = c["prev"].shape
-        n = len(c["pts"])
-        fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.array([w, h, c["max_level"], n, 30], np.int32).tobytes())
-            f.write(np.array([0.01], np.float64).tobytes() + np.array([1e-3], np.float32).tobytes())
-            f.write(c["prev"].tobytes() + c["next"].tobytes() + c["pts"].tobytes())
-        p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-        assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, text[-4000:]
-        raw = np.fromfile(fout, np.uint8)
-        nxt = raw[:8 * n].view(np.float32).reshape(n, 2)
-        err = raw[8 * n:12 * n].view(np.float32)
-        st = raw[12 * n:13 * n]
-        fc.assert_same((nxt, st, err), c["want"], name)
-        k = int(raw[13 * n:13 * n + 4].view(np.int32)[0])
-        st2 = raw[13 * n + 4:14 * n + 4]
-        idx = raw[14 * n + 4:14 * n + 4 + 4 * n].view(np.int32)[:k]
+        got, (k, st2, idx) = fe.run_standalone(tmp_path, dict(c, win=21, lk_max_level=c["max_level"]), what=name)
+        fc.assert_same(got, c["want"], name)
         _, _, wst, wkeep = fc.delete_unmatch_features(c["pts"], *c["want"][:2])
         assert k == len(wkeep) and np.array_equal(idx, wkeep) and np.array_equal(st2, wst)

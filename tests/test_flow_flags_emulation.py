@@ -1,69 +1,38 @@
 """The two-image tracker's kernels with flags (visual_odom_amd/csrc/lk.hip: lk_flow_flags_kernel<W>, every odd W of 5 .. 21)
-executed on the CPU through the coroutine SIMT emulator (tests/host_check/hip_emu.h + flow_flags_emu.cpp, over flow_emu.cpp's
-harness), from the product source.  The expected side is the checker's (tests/flow_flags_cases.py): for USE_INITIAL_FLOW the
+executed on the CPU through the coroutine SIMT emulator (tests/host_check/hip_emu.h + flow_emu.cpp, run through
+tests/flow_emu.py), from the product source.  The expected side is the checker's (tests/flow_flags_cases.py): for USE_INITIAL_FLOW the
 checker's own level loop started at the guess (tests/host_check/lk_flags_ref.c; its pin is the first test here), for
 GET_MIN_EIGENVALS the checker without an err vector and its threshold as a bracket around every value.  Positions, status and err
 are compared BIT FOR BIT, every point (NaN included), after the premises that make a guess-ignoring or epilogue-keeping kernel fail.
 
-The library loaded into python is built WITHOUT sanitizer flags whatever the environment says.  The sanitizer tier is the same
-harness as a STAND-ALONE program with its own main(), built with -fsanitize=address,undefined (runtimes linked statically) and run
-as a child.  Unit test of device code, not a product path."""
+The sanitizer tier is the same harness as a STAND-ALONE program (flow_emu.run_standalone).  Unit test of device code, not a
+product path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import flow_cases as fc
+import flow_emu as fe
 import flow_flags_cases as gc
 import flow_win_cases as wc
-from conftest import ROOT, vp
+from conftest import vp
 
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("flow_flags_emu.cpp", "flow_emu.cpp", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_tri.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
 ALL_WINDOWS = wc.WINDOWS + (21,)
 GUESS, EIG = gc.FLAG_GUESS, gc.FLAG_EIG
 
 
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
-
-
 @pytest.fixture(scope="module")
 def femu():
-    os.makedirs(OUT_DIR, exist_ok=True)
-    so = os.path.join(OUT_DIR, "libflow_flags_emu.so")
-    if _stale(so):
-        subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, os.path.join(SRC_DIR, "flow_flags_emu.cpp")])
-    lib = C.CDLL(so)
-    lib.ff_track.restype = C.c_int
-    return lib
+    return fe.load()
 
 
 def ff_track(lib, c, flags, guess=None, want_err=True, counts=None, max_count=30):
     """the case's pair through the emulated kernel of its window and flags, with the context's lk_max_level; one frame, or
     len(counts) frames of one launch: (next [F, n, 2], status [F, n], err [F, n] or None), F squeezed away for one frame"""
-    prev, nxt = np.ascontiguousarray(c["prev"]), np.ascontiguousarray(c["next"])
-    h, w = prev.shape
-    pts = np.ascontiguousarray(c["pts"], np.float32).reshape(-1, 2)
-    n, nf = len(pts), 1 if counts is None else len(counts)
-    io = np.zeros((nf, n, 2), np.float32)
-    if guess is not None:
-        io[:] = np.asarray(guess, np.float32).reshape(-1, n, 2)
-    st = np.zeros((nf, n), np.uint8)
-    err = np.zeros((nf, n), np.float32)
-    cnt = None if counts is None else np.asarray(counts, np.int32)
-    levels = lib.ff_track(vp(prev), vp(nxt), w, h, c["lk_max_level"], vp(pts), n, c["win"], flags, max_count, C.c_double(0.01), C.c_float(1e-3),
-                          vp(io), vp(st), vp(err) if want_err else None, nf, None if cnt is None else vp(cnt))
+    got, levels = fe.track(lib, c, flags, guess=guess, want_err=want_err, counts=counts, frame=0 if counts is None else None, max_count=max_count)
     assert levels == c["max_level"] + 1, "the harness plans the levels the depth rule says"
-    if counts is None:
-        return io[0], st[0], (err[0] if want_err else None)
-    return io, st, (err if want_err else None)
+    return got
 
 
 # ---- the expected side's own pin ----------------------------------------------------------------------------------------------
@@ -166,38 +135,18 @@ def test_flags_without_a_kernel_are_refused(femu):
     pts = np.zeros((1, 2), np.float32)
     io, st = np.zeros((1, 2), np.float32), np.zeros(1, np.uint8)
     for win, flags in ((21, 1), (21, 2), (21, 16), (21, -1), (20, 4), (23, 8)):
-        assert femu.ff_track(vp(img), vp(img), 96, 64, 3, vp(pts), 1, win, flags, 30, C.c_double(0.01), C.c_float(1e-3), vp(io), vp(st), None, 1, None) == -1
+        assert femu.fe_track(vp(img), vp(img), 96, 64, 3, vp(pts), 1, win, flags, 30, C.c_double(0.01), C.c_float(1e-3), vp(io), vp(st), None, 1, None) == -1
 
 
 @pytest.mark.sanitize
 def test_flags_kernels_standalone_under_sanitizers(tmp_path, orc, small_seq):
     """ASan + UBSan over the kernel source in a program of its own: exactly sized pyramid levels, far-off starts, no report, the
     same bits"""
-    out_dir = os.path.join(OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "flow_flags_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DFLOW_FLAGS_EMU_MAIN", "-o", exe, os.path.join(SRC_DIR, "flow_flags_emu.cpp")])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     runs = [(gc.adversarial_case(win, small_seq, orc), GUESS) for win in (21, 7, 13)]
     c = gc.final_check_case(small_seq, orc)
     k = np.flatnonzero(c["flips"])[:40]
     runs.append((dict(c, pts=np.ascontiguousarray(c["pts"][k]), guess=np.ascontiguousarray(c["pts"][k]), want=tuple(a[k] for a in c["want_no_err"][:2]) + (None,)),
                  GUESS | EIG))
     for c, flags in runs:
-        h, w = c["prev"].shape
-        n = len(c["pts"])
-        fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-        with open(fin, "wb") as f:
-            f.write(np.array([w, h, c["lk_max_level"], n, c.get("max_count", 30), c["win"], flags], np.int32).tobytes())
-            f.write(np.array([0.01], np.float64).tobytes() + np.array([1e-3], np.float32).tobytes())
-            f.write(c["prev"].tobytes() + c["next"].tobytes() + c["pts"].tobytes() + np.ascontiguousarray(c["guess"], np.float32).tobytes())
-        p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-        assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, ((c["win"], flags), text[-4000:])
-        raw = np.fromfile(fout, np.uint8)
-        nxt = raw[:8 * n].view(np.float32).reshape(n, 2)
-        err = raw[8 * n:12 * n].view(np.float32)
-        st = raw[12 * n:13 * n]
+        (nxt, st, err), _ = fe.run_standalone(tmp_path, c, flags, guess=c["guess"], what=(c["win"], flags))
         fc.assert_same((nxt, st, err if c["want"][2] is not None else None), c["want"], (c["win"], flags))

@@ -1,59 +1,32 @@
 """The windowed two-image tracker's kernels (visual_odom_amd/csrc/lk.hip: lk_flow_win_kernel<W>, W odd in 5 .. 19) executed on the
-CPU through the coroutine SIMT emulator (tests/host_check/hip_emu.h + flow_win_emu.cpp, over flow_emu.cpp's harness), from the
+CPU through the coroutine SIMT emulator (tests/host_check/hip_emu.h + flow_emu.cpp, run through tests/flow_emu.py), from the
 product source.  Positions, status and err are compared BIT FOR BIT, every point, with the checker's
 calcOpticalFlowPyrLK(win=W, max_level=E) (accum_mode 0), E being the depth the library plans (tests/flow_win_cases.py, which also
 holds the premises every comparison asserts first).
 
-The library loaded into python is built WITHOUT sanitizer flags whatever the environment says.  The sanitizer tier is the same
-harness as a STAND-ALONE program with its own main(): every pyramid level in an exactly sized heap block, built with
--fsanitize=address,undefined (runtimes linked statically) and run as a child.  Unit test of device code, not a product path."""
+The sanitizer tier is the same harness as a STAND-ALONE program (flow_emu.run_standalone).  Unit test of device code, not a
+product path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import flow_cases as fc
+import flow_emu as fe
 import flow_win_cases as wc
-from conftest import ROOT, vp
-
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("flow_win_emu.cpp", "flow_emu.cpp", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_tri.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
+from conftest import vp
 
 
 @pytest.fixture(scope="module")
 def wemu():
-    os.makedirs(OUT_DIR, exist_ok=True)
-    so = os.path.join(OUT_DIR, "libflow_win_emu.so")
-    if _stale(so):
-        subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, os.path.join(SRC_DIR, "flow_win_emu.cpp")])
-    lib = C.CDLL(so)
-    lib.fw_track.restype = C.c_int
-    return lib
+    return fe.load()
 
 
 def fw_track(lib, c, want_err=True, n_frames=1, frame=0, n=None):
     """the case's pair through the emulated kernel of its window, with the context's lk_max_level (the harness plans the levels)"""
-    prev, nxt = c["prev"], c["next"]
-    h, w = prev.shape
-    pts = np.ascontiguousarray(c["pts"] if n is None else c["pts"][:n], np.float32).reshape(-1, 2)
-    n = len(pts)
-    out = np.zeros((max(n, 1), 2), np.float32)
-    st = np.zeros(max(n, 1), np.uint8)
-    err = np.zeros(max(n, 1), np.float32)
-    levels = lib.fw_track(vp(np.ascontiguousarray(prev)), vp(np.ascontiguousarray(nxt)), w, h, c["lk_max_level"], vp(pts), n, c["win"], 30,
-                          C.c_double(0.01), C.c_float(1e-3), vp(out), vp(st), vp(err) if want_err else None, n_frames, frame)
+    got, levels = fe.track(lib, c, want_err=want_err, n_frames=n_frames, frame=frame, n=n)
     assert levels == c["max_level"] + 1, "the harness plans the levels the depth rule says"
-    return out[:n], st[:n], (err[:n] if want_err else None)
+    return got
 
 
 @pytest.mark.parametrize("name", ["crop", "lattice", "flat"])
@@ -105,7 +78,7 @@ def test_windows_without_a_kernel_are_refused(wemu):
     pts = np.zeros((1, 2), np.float32)
     out, st = np.zeros((1, 2), np.float32), np.zeros(1, np.uint8)
     for win in (-1, 0, 3, 4, 6, 20, 22, 23, 31):
-        assert wemu.fw_track(vp(img), vp(img), 96, 64, 3, vp(pts), 1, win, 30, C.c_double(0.01), C.c_float(1e-3), vp(out), vp(st), None, 1, 0) == -1
+        assert wemu.fe_track(vp(img), vp(img), 96, 64, 3, vp(pts), 1, win, 0, 30, C.c_double(0.01), C.c_float(1e-3), vp(out), vp(st), None, 1, None) == -1
 
 
 @pytest.mark.parametrize("seed", range(wc.N_RANDOM))
@@ -144,28 +117,8 @@ def test_depth_premise_at_21(orc, small_seq):
 @pytest.mark.sanitize
 def test_win_kernels_standalone_under_sanitizers(tmp_path, orc, small_seq):
     """ASan + UBSan over the kernel source in a program of its own: exactly sized pyramid levels, no report, the same bits"""
-    out_dir = os.path.join(OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "flow_win_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DFLOW_WIN_EMU_MAIN", "-o", exe, os.path.join(SRC_DIR, "flow_win_emu.cpp")])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     for win in (5, 13, 15, 19):
         for name in ("crop", "lattice"):
             c = wc.case(name, win, small_seq, orc)
-            h, w = c["prev"].shape
-            n = len(c["pts"])
-            fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-            with open(fin, "wb") as f:
-                f.write(np.array([w, h, c["lk_max_level"], n, 30, win], np.int32).tobytes())
-                f.write(np.array([0.01], np.float64).tobytes() + np.array([1e-3], np.float32).tobytes())
-                f.write(c["prev"].tobytes() + c["next"].tobytes() + c["pts"].tobytes())
-            p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-            text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-            assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, ((name, win), text[-4000:])
-            raw = np.fromfile(fout, np.uint8)
-            nxt = raw[:8 * n].view(np.float32).reshape(n, 2)
-            err = raw[8 * n:12 * n].view(np.float32)
-            st = raw[12 * n:13 * n]
-            fc.assert_same((nxt, st, err), c["want"], (name, win))
+            got, _ = fe.run_standalone(tmp_path, c, what=(name, win))
+            fc.assert_same(got, c["want"], (name, win))

@@ -22,7 +22,7 @@ def kemu():
     os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "libkernel_emu.so")
     csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
-    deps = [os.path.join(src_dir, f) for f in ("kernel_emu.cpp", "hip_emu.h")]
+    deps = [os.path.join(src_dir, f) for f in ("kernel_emu.cpp", "emu_pyramid.h", "hip_emu.h")]
     deps += [os.path.join(csrc, f) for f in ("lk.hip", "pyramid.hip", "fast.hip", "dev/lk_dev.hip", "dev/pyramid_dev.hip", "dev/fast_dev.hip",
                                                "vo_dev_hooks.h", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_svd_wide.h",
                                                "vo_linalg.h", "vo_epnp.h", "pnp.hip", "vo_p3p.h", "vo_math.h",

@@ -6,7 +6,7 @@
 // The calls of include/vo_flow_win.h (vowin_*) are the same host code with a window: every call below takes `win`, voflow_* pass
 // 21 (lk_flow_kernel), vowin_* the caller's (lk_flow_win_kernel<win>, refused before anything is launched if there is none).
 // The calls of include/vo_flow_flags.h (voflag_*) are the same host code again with cv::calcOpticalFlowPyrLK's flags: voflow_* and
-// vowin_* pass 0 and reach the launchers they always reached, anything else is lk_flow_flags_kernel<win> (launch_lk_flow_flags).
+// vowin_* pass 0 and reach the kernels they always reached, anything else is lk_flow_flags_kernel<win> (launch_lk_flow's route).
 #include "capi_internal.h"
 #include "../../include/vo_flow_flags.h"
 
@@ -90,8 +90,8 @@ int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_
     std::fill(c->img_stale.begin(), c->img_stale.begin() + slot1 + 1, (uint8_t)0);
     if (flags & VOFLAG_USE_INITIAL_FLOW)
         VO_HIP_TRY(c, hipMemcpyAsync(fl.d_next, guess, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, st));
-    launch_lk_flow_flags(win, flags, c->d_imgs, fl.d_pairs + c->max_frames + k, c->d_pts, c->d_npts, c->cap, n, 1, fl.d_next, fl.d_status,
-                         want_err ? fl.d_err : nullptr, lk_params(c), st);
+    launch_lk_flow(win, flags, c->d_imgs, fl.d_pairs + c->max_frames + k, c->d_pts, c->d_npts, c->cap, n, 1, fl.d_next, fl.d_status,
+                   want_err ? fl.d_err : nullptr, lk_params(c), st);
     if (compact)
         launch_flow_compact(c->d_pts, fl.d_next, fl.d_status, c->d_npts, c->cap, fl.d_out0, fl.d_out1, fl.d_idx, fl.d_nout, 1, st);
     FlowGather g;
@@ -111,7 +111,7 @@ int flow_sync_call(vo_ctx *c, const char *who, const uint8_t *prev, const uint8_
     return VO_OK;
 }
 
-// the windows with a kernel: odd, 5 .. 21 (vo_flow_win.h says why 23 and above are out) -- launch_lk_flow_win's precondition,
+// the windows with a kernel: odd, 5 .. 21 (vo_flow_win.h says why 23 and above are out) -- launch_lk_flow's precondition,
 // checked by every entry point before anything else happens
 bool win_ok(int win) { return win >= 5 && win <= 21 && (win & 1); }
 int bad_win(vo_ctx *c, const char *who) { return fail(c, VO_ERR_ARG, (std::string(who) + ": win is not an odd number of 5 .. 21").c_str()); }
@@ -206,8 +206,8 @@ int batch_run(vo_ctx *c, const char *who, int win, int flags)
                 return fail(c, VO_ERR_STATE, (me + ": VOFLAG_USE_INITIAL_FLOW, and a frame's next positions hold neither a guess "
                                                    "(voflag_batch_set_guess) nor a run's results since voflow_batch_set_pairs").c_str());
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    launch_lk_flow_flags(win, flags, c->d_imgs, fl.d_pairs, cur_pts(c), cur_npts(c), c->cap, c->max_pts_set, fl.n_pairs, fl.d_next,
-                         fl.d_status, fl.d_err, lk_params(c), c->sel->stream);
+    launch_lk_flow(win, flags, c->d_imgs, fl.d_pairs, cur_pts(c), cur_npts(c), c->cap, c->max_pts_set, fl.n_pairs, fl.d_next, fl.d_status,
+                   fl.d_err, lk_params(c), c->sel->stream);
     VO_HIP_TRY(c, hipGetLastError());
     std::fill(fl.next_set.begin(), fl.next_set.begin() + fl.n_pairs, (uint8_t)1); // (every frame's rows are a run's results now)
     return VO_OK;

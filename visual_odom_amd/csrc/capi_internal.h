@@ -412,7 +412,6 @@ inline int fail_hip(vo_ctx *ctx, const char *what, hipError_t e)
 
 // the detection grid's bucket edge in pixels (vo_detect_params.bucket_size, 0 = a tenth of the image height)
 inline int bucket_size(const vo_ctx *c) { return c->dprm.bucket_size > 0 ? c->dprm.bucket_size : c->h / 10; }
-inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 // register budget of the pose kernels for the stand-alone calls (vo_pnp_ransac, vo_essential_pose): nothing runs beside
 // them, so the full 512 registers unless the caller pinned the other variant
 inline int standalone_waves(const vo_ctx *c) { return c->pin.pose_waves ? c->pin.pose_waves : 1; }
@@ -426,23 +425,6 @@ inline void use_const_quad(vo_ctx *c, int k) // frame 0 of a one-frame configura
 inline float2 *cur_pts(vo_ctx *c) { return c->pts_sel < 0 ? c->d_pts : c->d_pts_det[c->pts_sel]; }
 inline int *cur_npts(vo_ctx *c) { return c->pts_sel < 0 ? c->d_npts : c->d_npts_det[c->pts_sel]; }
 inline int *cur_ages(vo_ctx *c) { return c->pts_sel < 0 ? c->d_ages : c->d_ages_det[c->pts_sel]; }
-// row pitch (pixels) of a bordered level: VO_BX left + w + at least VO_BY right, multiple of 16
-inline int level_stride(int w) { return align_up(VO_BX + w + VO_BY, 16); }
-// the deepest pyramid level index of a w x h image, exactly as buildOpticalFlowPyramid with the 21 x 21 window: stop at
-// lk_max_level, at the table's VO_MAX_LEVELS, or when the next level would not be larger than the window (plan_levels,
-// vowin_max_level)
-inline int plan_depth(int w, int h, int lk_max_level)
-{
-    int l = 0;
-    for (int cw = w, ch = h;; l++) {
-        const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
-        if (l == lk_max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
-            break;
-        cw = nw;
-        ch = nh;
-    }
-    return l;
-}
 // the bytes of a source row of vo_params.input_format that are ever read or copied (ingest_bpp: vo_kernels.h): one plane of a
 // two-byte interleave ends with its last pixel (the right plane of an interleaved frame starts at byte 1: byte 2 w of its last
 // row is outside the frame)

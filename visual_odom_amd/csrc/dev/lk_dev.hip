@@ -340,7 +340,7 @@ static void launch_lk_circular_pair(const PyrImage *d_imgs, const Quad *d_quads,
     if (max_pts <= 0 || n_frames <= 0)
         return;
     const LkGrid g = lk_grid(n_frames, (max_pts + 1) / 2); // PAIRS per part
-    hipLaunchKernelGGL(lk_circular_pair_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
+    hipLaunchKernelGGL(lk_circular_pair_kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
                        g.fpg, g.ppp, d_trk, d_status, prm);
 }
 

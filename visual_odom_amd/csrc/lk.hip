@@ -38,6 +38,7 @@
 #include "vo_lkmath.h"
 
 #include <float.h>
+#include <type_traits>
 
 namespace vo {
 
@@ -615,90 +616,60 @@ __global__ VO_LK_FLOW_ATTRS void lk_flow_flags_kernel(const PyrImage *__restrict
     lk_circular_body<false, true, W, true>(imgs, pairs, pts_in, n_pts, cap, n_frames, fpg, ppp, next, status, prm, 0, 1, err, flags);
 }
 
-#ifndef VO_HOST_EMUL
 // The launch geometry of the block numbering above: frames per group of 8 XCDs (the largest power of two <= min(8, n_frames)),
-// work items -- features, or the pair kernel's pairs of features (dev/lk_dev.hip) -- per part of a frame's list, and the grid.
+// work items -- features, or the pair kernel's pairs of features (dev/lk_dev.hip) -- per part of a frame's list, and the number
+// of workgroups.  Host code; the CPU emulator of the tests launches by it too.
 struct LkGrid {
-    int fpg, ppp;
-    dim3 grid;
+    int fpg, ppp, blocks;
 };
-static LkGrid lk_grid(int n_frames, int n_items)
+inline LkGrid lk_grid(int n_frames, int n_items)
 {
     const int fpg = n_frames >= 8 ? 8 : n_frames >= 4 ? 4 : n_frames >= 2 ? 2 : 1;
     const int parts = 8 / fpg, ppp = (n_items + parts - 1) / parts;
     const int groups = (n_frames + fpg - 1) / fpg;
-    return {fpg, ppp, dim3((unsigned)(8 * groups * ppp))};
+    return {fpg, ppp, 8 * groups * ppp};
 }
 
-void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
-                    int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+// The windows of the two-image kernels, listed once: f(std::integral_constant<int, W>) for the odd W of 5 .. 21 that `win` is;
+// false, and f not called, for any other window.
+template <int... W, typename F>
+inline bool lk_visit_window(int win, F &&f)
 {
-    if (max_pts <= 0 || n_frames <= 0)
-        return;
-    const LkGrid g = lk_grid(n_frames, max_pts);
-    hipLaunchKernelGGL(lk_flow_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp, d_next,
-                       d_status, d_err, prm);
+    return ((win == W && (f(std::integral_constant<int, W>{}), true)) || ...);
+}
+template <typename F>
+inline bool lk_for_window(int win, F &&f)
+{
+    return lk_visit_window<5, 7, 9, 11, 13, 15, 17, 19, LK_WIN>(win, f);
 }
 
-// launch_lk_flow with a window: 21 is lk_flow_kernel itself, every odd W of 5 .. 19 its own instantiation.  Precondition: win is
-// one of these (the entry points of capi_flow.hip refuse every other window); nothing is launched for any other.
-template <int W>
-static void launch_lk_flow_win_w(const LkGrid &g, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
-                                 int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
+// The route from (W, flags) to a two-image kernel, written once: run(kernel, arguments behind prm...).  Flags are
+// lk_flow_flags_kernel<W>, which takes them as its last argument; without, 21 is lk_flow_kernel and any other W its own kernel.
+template <int W, typename R>
+inline void lk_flow_route(int flags, R &&run)
 {
-    hipLaunchKernelGGL(lk_flow_win_kernel<W>, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
-                       d_next, d_status, d_err, prm);
-}
-void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
-                        int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
-{
-    if (win == LK_WIN) {
-        launch_lk_flow(d_imgs, d_pairs, d_pts, d_npts, cap, max_pts, n_frames, d_next, d_status, d_err, prm, stream);
-        return;
-    }
-    if (max_pts <= 0 || n_frames <= 0)
-        return;
-    const LkGrid g = lk_grid(n_frames, max_pts);
-    switch (win) {
-#define VO_LK_WIN_CASE(W)                                                                                                       \
-    case W:                                                                                                                     \
-        launch_lk_flow_win_w<W>(g, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, d_next, d_status, d_err, prm, stream);       \
-        break;
-        VO_LK_WIN_CASE(5) VO_LK_WIN_CASE(7) VO_LK_WIN_CASE(9) VO_LK_WIN_CASE(11) VO_LK_WIN_CASE(13) VO_LK_WIN_CASE(15) VO_LK_WIN_CASE(17)
-        VO_LK_WIN_CASE(19)
-#undef VO_LK_WIN_CASE
-    }
+    if (flags != 0)
+        run(lk_flow_flags_kernel<W>, flags);
+    else if constexpr (W == LK_WIN)
+        run(lk_flow_kernel);
+    else
+        run(lk_flow_win_kernel<W>);
 }
 
-// launch_lk_flow_win with flags (VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS): 0 is launch_lk_flow_win itself, anything else
-// lk_flow_flags_kernel<win>, d_next in/out.  Preconditions: win as there, no other bit in flags.
-template <int W>
-static void launch_lk_flow_flags_w(const LkGrid &g, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts,
-                                   const int *d_npts, int cap, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err,
-                                   const LkParams &prm, hipStream_t stream)
+#ifndef VO_HOST_EMUL
+// (vo_kernels.h has the preconditions; the entry points of capi_flow.hip refuse what breaks them before anything else happens)
+void launch_lk_flow(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
+                    int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
 {
-    hipLaunchKernelGGL(lk_flow_flags_kernel<W>, g.grid, dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
-                       d_next, d_status, d_err, prm, flags);
-}
-void launch_lk_flow_flags(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
-                          int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream)
-{
-    if (flags == 0) {
-        launch_lk_flow_win(win, d_imgs, d_pairs, d_pts, d_npts, cap, max_pts, n_frames, d_next, d_status, d_err, prm, stream);
-        return;
-    }
     if (max_pts <= 0 || n_frames <= 0 || (flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)))
         return;
     const LkGrid g = lk_grid(n_frames, max_pts);
-    switch (win) {
-#define VO_LK_FLAGS_CASE(W)                                                                                                     \
-    case W:                                                                                                                     \
-        launch_lk_flow_flags_w<W>(g, flags, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, d_next, d_status, d_err, prm, stream); \
-        break;
-        VO_LK_FLAGS_CASE(5) VO_LK_FLAGS_CASE(7) VO_LK_FLAGS_CASE(9) VO_LK_FLAGS_CASE(11) VO_LK_FLAGS_CASE(13) VO_LK_FLAGS_CASE(15)
-        VO_LK_FLAGS_CASE(17) VO_LK_FLAGS_CASE(19) VO_LK_FLAGS_CASE(21)
-#undef VO_LK_FLAGS_CASE
-    }
+    lk_for_window(win, [&](auto w) {
+        lk_flow_route<decltype(w)::value>(flags, [&](auto kernel, auto... tail) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_pairs, d_pts, d_npts, cap, n_frames, g.fpg,
+                               g.ppp, d_next, d_status, d_err, prm, tail...);
+        });
+    });
 }
 
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
@@ -708,8 +679,8 @@ void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float
     if (max_pts <= 0 || n_frames <= 0)
         return;
     const LkGrid g = lk_grid(n_frames, max_pts);
-    hipLaunchKernelGGL(lk_circular_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
-                       g.fpg, g.ppp, d_trk, d_status, prm);
+    hipLaunchKernelGGL(lk_circular_kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap,
+                       n_frames, g.fpg, g.ppp, d_trk, d_status, prm);
 }
 
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
@@ -719,8 +690,8 @@ void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d
     if (max_pts <= 0 || n_frames <= 0 || hop_begin < 0 || hop_end > 4 || hop_begin >= hop_end)
         return;
     const LkGrid g = lk_grid(n_frames, max_pts);
-    hipLaunchKernelGGL(lk_hops_kernel, g.grid, dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames, g.fpg, g.ppp,
-                       d_trk, d_status, prm, hop_begin, hop_end);
+    hipLaunchKernelGGL(lk_hops_kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap, n_frames,
+                       g.fpg, g.ppp, d_trk, d_status, prm, hop_begin, hop_end);
 }
 
 #endif // VO_HOST_EMUL

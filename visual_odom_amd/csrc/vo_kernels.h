@@ -10,6 +10,26 @@ namespace vo {
 // vo_params.input_format (VO_FMT_*): source bytes per pixel -- the minimum byte stride of an image is w * ingest_bpp
 constexpr int ingest_bpp(int fmt) { return fmt == VO_FMT_GRAY8 ? 1 : fmt == VO_FMT_GRAY8_X2 ? 2 : fmt <= VO_FMT_RGB8 ? 3 : 4; }
 
+// the level plan of vo_create / vo_batch_configure, shared with the CPU emulator of the tests:
+inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+// row pitch (pixels) of a bordered level: VO_BX left + w + at least VO_BY right, multiple of 16
+inline int level_stride(int w) { return align_up(VO_BX + w + VO_BY, 16); }
+// the deepest pyramid level index of a w x h image, exactly as buildOpticalFlowPyramid with the 21 x 21 window: stop at
+// lk_max_level, at the table's VO_MAX_LEVELS, or when the next level would not be larger than the window (plan_levels,
+// vowin_max_level)
+inline int plan_depth(int w, int h, int lk_max_level)
+{
+    int l = 0;
+    for (int cw = w, ch = h;; l++) {
+        const int nw = (cw + 1) / 2, nh = (ch + 1) / 2;
+        if (l == lk_max_level || l + 1 >= VO_MAX_LEVELS || nw <= 21 || nh <= 21)
+            break;
+        cw = nw;
+        ch = nh;
+    }
+    return l;
+}
+
 struct LkParams {
     int max_level;   // 3 in the reference (feature.cpp:136) -> 4 pyramid levels
     int max_count;   // 30
@@ -132,19 +152,13 @@ void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_trk, uint8_t *d_status, const LkParams &prm, int hop_begin, int hop_end,
                     hipStream_t stream);
-// one hop per frame between the images (Quad::l0 -> Quad::r0) of its pair, with cv::calcOpticalFlowPyrLK's err (lk_flow_kernel);
-// d_next / d_status / d_err: [B][cap], d_err may be null (the err epilogue is skipped)
-void launch_lk_flow(const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
-                    int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
-// the same with a win x win window (lk_flow_win_kernel<win>, odd 5 .. 19; 21 is launch_lk_flow).  Precondition: win is odd and in
-// 5 .. 21 -- there is no kernel for any other window and nothing is launched for one
-void launch_lk_flow_win(int win, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
-                        int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
-// the same with cv::calcOpticalFlowPyrLK's flags (4: the search starts at the guess d_next holds, in/out; 8: err = min eigenvalue,
-// no final in-bounds check): lk_flow_flags_kernel<win>, every odd win of 5 .. 21; flags == 0 is launch_lk_flow_win.  Preconditions:
-// win as above and no other bit in flags -- nothing is launched otherwise
-void launch_lk_flow_flags(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
-                          int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
+// one hop per frame between the images (Quad::l0 -> Quad::r0) of its pair with a win x win window and cv::calcOpticalFlowPyrLK's
+// err and flags (4: the search starts at the guess d_next holds, in/out; 8: err = min eigenvalue, no final in-bounds check).
+// flags != 0 is lk_flow_flags_kernel<win>, else win == 21 lk_flow_kernel and any other lk_flow_win_kernel<win>.
+// d_next / d_status / d_err: [B][cap], d_err may be null (the err epilogue is skipped).  Preconditions: win is odd and in 5 .. 21
+// -- there is no kernel for any other window -- and flags holds no other bit: nothing is launched otherwise
+void launch_lk_flow(int win, int flags, const PyrImage *d_imgs, const Quad *d_pairs, const float2 *d_pts, const int *d_npts, int cap,
+                    int max_pts, int n_frames, float2 *d_next, uint8_t *d_status, float *d_err, const LkParams &prm, hipStream_t stream);
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,
                           int h, int threshold, int nonmax, unsigned long long *d_nmsmask,
                           int *d_rowcnt, int *d_rowoff,
