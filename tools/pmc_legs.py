@@ -63,7 +63,7 @@ def main(src):
             rec = {"workload": wl, "frames_per_step": frames, "fetch_bytes_per_launch": f, "write_bytes_per_launch": w,
                    "hbm_bytes_per_launch": 2 * f + w, "hbm_bytes_per_launch_uncorrected": f + w,
                    "algorithmic_bytes_per_launch": b["roofline"]["bytes_per_launch"],
-                   "source": "r06 (gpurun_out/%s): rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate runs of `%s`; KB -> bytes; "
+                   "source": "%s: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate runs of `%s`; KB -> bytes; "
                              "FETCH_SIZE doubled (gfx950 correction, profiles/r01_fetch_calibration.txt); WRITE_SIZE as reported" % (tag, cmd)}
             pf, npf = pyr_counters(os.path.join(src, "pmc_%s_fetch" % wl))
             pw, npw = pyr_counters(os.path.join(src, "pmc_%s_write" % wl))
@@ -88,7 +88,7 @@ def main(src):
                                "issue_cost_bound_cycles_per_valu_instruction": ISSUE_COST, "measured_over_bound": per_cyc / ISSUE_COST,
                                "issue_floor_cycles_per_valu_instruction": ISSUE_FLOOR,
                                "dispatches_averaged": nsq["SQ_INSTS_VALU"],
-                               "source": "r06 (gpurun_out/%s): rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU "
+                               "source": "%s: rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU "
                                          "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES (its own run of `%s`), means over the lk_circular_kernel "
                                          "dispatches; the bound = the hot loop's opcode mix x measured issue costs "
                                          "(profiles/r02_lk_issue_bound.md)" % (tag, cmd)})

@@ -18,9 +18,12 @@
 //   Template: each lane loads its 2 x 8 pixels and 2 x 8 Scharr samples straight from the bordered
 //   pyramid (no border path, no staging) and keeps the 7 samples of I, Ix, Iy packed two per VGPR
 //   (12 VGPRs) for the whole level.
-//   Search image J: a 40 x 48 byte tile in LDS (1920 B per wave), filled with 16-byte loads and
-//   re-fetched only when the window leaves it; one iteration reads two unaligned 8-byte rows.
-//   Pixel arithmetic: v_perm_b32 / v_dot2_u32_u16 / v_dot2_i32_i16 / v_pk_sub_i16 (vo_lkmath.h).
+//   Search image J: a 40 x 48 byte tile in LDS (1920 B per wave), filled with 16-byte loads (two
+//   per lane, straight-line: lk_tile_refill_wave) and re-fetched only when the window leaves it; a
+//   pixel cell reads two unaligned 8-byte rows once and keeps its 8 columns lifted in registers.
+//   Pixel arithmetic: v_perm_b32 / v_dot2_u32_u16 / v_dot2_i32_i16 / v_pk_sub_i16 (vo_lkmath.h), every
+//   bilinear sample from VERTICAL pixel pairs (t[k], b[k]) against the weights packed by column: each
+//   column is lifted once (8 v_perm_b32 per cell, where horizontal pairs took 14; profiles/r07_lk_vertical_pairs.md).
 //   Reductions: v_permlane32/16_swap + v_add_u32_dpp butterflies, two sums per tree (vo_dev.h
 //   wave_sum2_exact_f32), no LDS round trips.
 // Grid: blocks are numbered so that (dispatcher: block b -> XCD b % 8) all features of one frame
@@ -65,12 +68,15 @@ constexpr uint32_t lk_seg_mask(int valid, int m)
 
 // 14-bit fixed-point bilinear weights of OpenCV's LKTrackerInvoker from the fractional parts of the
 // window corner: iw00 = cvRound((1-a)*(1-b)*2^14), iw01 = cvRound(a*(1-b)*2^14), iw10 = cvRound((1-a)*b*2^14),
-// iw11 = 2^14 - iw00 - iw01 - iw10, returned as the packed int16 pairs wt = (iw00, iw01), wb = (iw10, iw11).
+// iw11 = 2^14 - iw00 - iw01 - iw10, returned as packed int16 pairs: by row, wt = (iw00, iw01), wb = (iw10, iw11)
+// (lk_weights: the samplers over horizontal pixel pairs), or by column, wl = (iw00, iw10), wr = (iw01, iw11)
+// (lk_weights_cols: the samplers over vertical pairs, vo_lkmath.h) -- the two differ in the packing selectors' operands only.
 //   * the scale is folded into the first factor ((1-a)*2^14 is exact, so the rounded product is identical);
 //   * cvRound (round half to even) = adding 1.5 * 2^23: the f32 sum has ulp 1, so the add rounds the
 //     product to the nearest-even integer and leaves it in the low mantissa bits.  The raw bit patterns
 //     are packed / summed directly (0x4B400000 has no low 16 bits), no v_rndne / v_cvt per weight.
-__device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint32_t &wb)
+template <bool COLS>
+__device__ __forceinline__ void lk_weights_packed(float a, float b, uint32_t &w0, uint32_t &w1)
 {
     const float s = (float)(1 << LK_W_BITS), magic = 12582912.f; // 1.5 * 2^23 = 0x4B400000
     const float a1 = (1.f - a) * s, a0 = a * s, b1 = 1.f - b;
@@ -79,8 +85,16 @@ __device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint3
     const uint32_t r10 = (uint32_t)__float_as_int(a1 * b + magic);
     // iw11 = 2^14 - (r00 + r01 + r10 - 3 * 0x4B400000)   (mod 2^32)
     const uint32_t iw11 = ((1u << LK_W_BITS) + 3u * 0x4B400000u) - (r00 + r01 + r10);
-    wt = perm_b32(r01, r00, VO_SEL_LO16);
-    wb = perm_b32(iw11, r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
+    w0 = perm_b32(COLS ? r10 : r01, r00, VO_SEL_LO16);
+    w1 = perm_b32(iw11, COLS ? r01 : r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
+}
+__device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint32_t &wb)
+{
+    lk_weights_packed<false>(a, b, wt, wb);
+}
+__device__ __forceinline__ void lk_weights_cols(float a, float b, uint32_t &wl, uint32_t &wr)
+{
+    lk_weights_packed<true>(a, b, wl, wr);
 }
 
 // ---- the search tile: LK_JT_H rows of LK_JT_W bytes of J in LDS, origin (jx0, jy0) -------------------------------------
@@ -96,24 +110,63 @@ __device__ __forceinline__ bool lk_tile_misses(bool have_tile, int jx0, int jy0,
 {
     return !have_tile || inx < jx0 || inx + LkWin<W>::COLS > jx0 + LK_JT_W || iny < jy0 || iny + LkWin<W>::ROWS > jy0 + LK_JT_H;
 }
-// a new tile around corner (inx, iny): the origin -- 4-byte aligned, clamped to [-VO_BX, jx_max] x [-VO_BY, jy_max], which keeps
-// the tile inside the level's rectangle -- and the fill, 16-byte chunks c0, c0 + step, ... of the tile's LK_JT_H * LK_JT_W / 16.
-// Returns the origin.  No barrier in here: the caller orders the fill against the LDS reads around it.
+// the origin of a new tile around corner (inx, iny): 4-byte aligned, clamped to [-VO_BX, jx_max] x [-VO_BY, jy_max], which keeps
+// the tile inside the level's rectangle
 template <int W = LK_WIN>
-__device__ __forceinline__ LkOrigin lk_tile_refill(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
-                                               int inx, int iny, int c0, int step)
+__device__ __forceinline__ LkOrigin lk_tile_origin(int jx_max, int jy_max, int inx, int iny)
 {
     int jx0 = (inx - LkWin<W>::OFF_X) & ~3;
     int jy0 = iny - LkWin<W>::OFF_Y;
     jx0 = jx0 < -VO_BX ? -VO_BX : jx0 > jx_max ? jx_max : jx0;
     jy0 = jy0 < -VO_BY ? -VO_BY : jy0 > jy_max ? jy_max : jy0;
+    return LkOrigin{jx0, jy0};
+}
+// a new tile around corner (inx, iny): the origin and the fill, 16-byte chunks c0, c0 + step, ... of the tile's
+// LK_JT_H * LK_JT_W / 16 (chunk c = 3 row + col lies at LDS byte 16 c).  Returns the origin.  No barrier in here: the caller
+// orders the fill against the LDS reads around it.  The general form, for the pair kernel's half waves (dev/lk_dev.hip).
+template <int W = LK_WIN>
+__device__ __forceinline__ LkOrigin lk_tile_refill(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max, int jy_max,
+                                               int inx, int iny, int c0, int step)
+{
+    const LkOrigin org = lk_tile_origin<W>(jx_max, jy_max, inx, iny);
+    const int jx0 = org.x, jy0 = org.y;
     const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)jy0 * jstride + jx0;
     for (int c = c0; c < LK_JT_H * (LK_JT_W / 16); c += step) {
         const int row = c / (LK_JT_W / 16), col = c - row * (LK_JT_W / 16);
         const U32x4A4 v = *(const VO_GLOBAL U32x4A4 *)(tb + (uint32_t)(row * jstride + 16 * col));
         *reinterpret_cast<uint4 *>(&tile[row * LK_JT_W + 16 * col]) = make_uint4(v.a, v.b, v.c, v.d);
     }
-    return LkOrigin{jx0, jy0};
+    return org;
+}
+// The same for a whole wave, chunks (lane, lane + 64), as straight-line code: the tile has 120 chunks, so every lane owns chunk
+// `lane` and the lanes below 56 a second one, 64 further = 21 rows and one column on (row + 22, column 0 from column 2).  One
+// division by 3 per fill instead of one per chunk, and both loads are in flight before the first is waited for.
+template <int W = LK_WIN>
+__device__ __forceinline__ LkOrigin lk_tile_refill_wave(uint8_t *tile, const VO_GLOBAL uint8_t *__restrict__ Jimg, int jstride, int jx_max,
+                                                    int jy_max, int inx, int iny, int lane)
+{
+    constexpr int CPR = LK_JT_W / 16, CHUNKS = LK_JT_H * CPR; // chunks per row, chunks
+    static_assert(CPR == 3 && CHUNKS > 64 && CHUNKS <= 128, "two chunks per lane at most; 64 chunks = 21 rows + 1 chunk");
+    const LkOrigin org = lk_tile_origin<W>(jx_max, jy_max, inx, iny);
+    const VO_GLOBAL uint8_t *tb = Jimg + (ptrdiff_t)org.y * jstride + org.x;
+#ifndef VO_HOST_EMUL
+    // the chunk offsets depend on the lane and the level's stride only: seen through, they are hoisted to the level's set-up and
+    // live in registers across the iteration loop, which the two-image kernels' bound has no room for
+    asm volatile("" : "+v"(lane));
+#endif
+    const int row = (lane * 43) >> 7, col = lane - CPR * row; // lane / 3, exact below 128
+    const uint32_t g0 = (uint32_t)(row * jstride + 16 * col);
+    const int next_col = 21 * jstride + 16, next_row = 22 * jstride - 16 * (CPR - 1); // wave-uniform: one select per fill
+    const uint32_t g1 = g0 + (uint32_t)(col == CPR - 1 ? next_row : next_col);
+    const bool second = lane < CHUNKS - 64;
+    const U32x4A4 v0 = *(const VO_GLOBAL U32x4A4 *)(tb + g0);
+    U32x4A4 v1 = v0;
+    if (second)
+        v1 = *(const VO_GLOBAL U32x4A4 *)(tb + g1);
+    *reinterpret_cast<uint4 *>(&tile[16 * lane]) = make_uint4(v0.a, v0.b, v0.c, v0.d);
+    if (second)
+        *reinterpret_cast<uint4 *>(&tile[16 * lane + 1024]) = make_uint4(v1.a, v1.b, v1.c, v1.d);
+    return org;
 }
 // the one-feature kernels: the origin of a tile that covers the window of corner (inx, iny) -- the wave's own if it does, else a
 // new one, fetched between two barriers
@@ -124,19 +177,26 @@ __device__ __forceinline__ LkOrigin lk_tile_cover(uint8_t *tile, const VO_GLOBAL
     if (!lk_tile_misses<W>(have_tile, jx0, jy0, inx, iny))
         return LkOrigin{jx0, jy0};
     __syncthreads(); // single-wave workgroup: orders the LDS reads before the refill
-    const LkOrigin o = lk_tile_refill<W>(tile, Jimg, jstride, jx_max, jy_max, inx, iny, lane, 64);
+    const LkOrigin o = lk_tile_refill_wave<W>(tile, Jimg, jstride, jx_max, jy_max, inx, iny, lane);
     __syncthreads();
     return o;
 }
 // the pixel pairs of a lane's row segment in the cell at tile offset `off`, upper and lower row: two unaligned 8-byte LDS reads
 // (gfx950 handles misaligned ds_read_b64; measured equal to three aligned dwords + v_alignbyte_b32 per row, profiles/r01 notes)
-// and the 14 v_perm_b32 of lift7
+// and the 14 v_perm_b32 of lift7 (the pair kernel, dev/lk_dev.hip) ...
 __device__ __forceinline__ void lk_cell_rows(const uint8_t *tile, int off, uint32_t Jt[7], uint32_t Jb[7])
 {
     const U32x2A1 t = *reinterpret_cast<const U32x2A1 *>(&tile[off]);
     const U32x2A1 u = *reinterpret_cast<const U32x2A1 *>(&tile[off + LK_JT_W]);
     lift7(t.a, t.b, Jt);
     lift7(u.a, u.b, Jb);
+}
+// ... or, from the same two reads, the segment's 8 columns as vertical pairs: the 8 v_perm_b32 of lift8_cols (the kernels here)
+__device__ __forceinline__ void lk_cell_cols(const uint8_t *tile, int off, uint32_t Jc[8])
+{
+    const U32x2A1 t = *reinterpret_cast<const U32x2A1 *>(&tile[off]);
+    const U32x2A1 u = *reinterpret_cast<const U32x2A1 *>(&tile[off + LK_JT_W]);
+    lift8_cols(t.a, t.b, u.a, u.b, Jc);
 }
 
 // 7 waves per SIMD = at most 72 VGPRs.  Round 1 had the bound at 6 waves and the allocator happened to land on 70
@@ -265,8 +325,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     st = 0;
                 continue;
             }
-            uint32_t wt, wb; // (float)ipx == floorf(prevX): the fractional part needs no int round trip
-            lk_weights(prevX - fpx, prevY - fpy, wt, wb);
+            uint32_t wl, wr; // (float)ipx == floorf(prevX): the fractional part needs no int round trip
+            lk_weights_cols(prevX - fpx, prevY - fpy, wl, wr);
 
             // ---- 21 x 21 template straight from the bordered pyramid (registers) + structure tensor --
             // lane: pixels (ipx + c0 .. + 7, ipy + r) and the row below; the bordered layout makes
@@ -297,8 +357,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                 const uint32_t dt[8] = {dt0.a, dt0.b, dt0.c, dt0.d, dt1.a, dt1.b, dt1.c, dt1.d};
                 const uint32_t db[8] = {db0.a, db0.b, db0.c, db0.d, db1.a, db1.b, db1.c, db1.d};
                 uint32_t Ip[4];
-                bilinear7_u8(t.a, t.b, u.a, u.b, wt, wb, Ip);
-                bilinear7_deriv(dt, db, wt, wb, Ixp, Iyp);
+                bilinear7_u8_cols(t.a, t.b, u.a, u.b, wl, wr, Ip);
+                bilinear7_deriv_cols(dt, db, wl, wr, Ixp, Iyp);
                 if constexpr (LW::LAST < 7) {
                     // the last segment of a row reaches beyond the window: its pixels from LAST on get Ix = Iy = 0, once per
                     // level, so that A11 / A12 / A22, the seeds c1 / c2 and every b1 / b2 of the iteration take nothing from them
@@ -388,8 +448,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
 
             // The window corner stays in the same pixel cell for two iterations out of three, so the Gauss-Newton
             // loop is written as two loops: the outer one is entered once per cell and does everything that only
-            // depends on the cell -- admissibility test, tile test / refill, LDS address, the two row reads and the 14
-            // v_perm_b32 that lift the pixel pairs into registers; the inner one iterates while the corner stays put.
+            // depends on the cell -- admissibility test, tile test / refill, LDS address, the two row reads and the 8
+            // v_perm_b32 that lift the segment's columns into registers; the inner one iterates while the corner stays put.
             int j = 0;
             float fnx = floorf(nextX), fny = floorf(nextY);
             bool run = prm.max_count > 0;
@@ -406,8 +466,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     jy0 = o.y;
                     have_tile = true;
                 }
-                uint32_t Jt[7], Jb[7]; // the cell's pixel pairs (two window rows per lane)
-                lk_cell_rows(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jt, Jb); // uniform part on the scalar unit
+                uint32_t Jc[8]; // the cell's columns (two window rows per lane) as vertical pixel pairs
+                lk_cell_cols(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jc); // uniform part on the scalar unit
                 // fractional position of the window corner inside its pixel cell: the bilinear weights come from it, and
                 // the corner is still inside the cell exactly as long as both parts are in [0, 1).  fl(nextX - fnx) is what
                 // OpenCV itself computes (nextPt.x - inextPt.x); a true difference >= 1 or < 0 can never round into [0, 1),
@@ -416,11 +476,11 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                 // (negative values have the sign bit set), so one unsigned max + one compare replace two floors, two
                 // compares and two selects per iteration.
                 for (;;) {
-                    lk_weights(nextX - fnx, nextY - fny, wt, wb);
+                    lk_weights_cols(nextX - fnx, nextY - fny, wl, wr);
                     int b1, b2;
                     {
                         uint32_t Jp[4];
-                        blend7(Jt, Jb, wt, wb, Jp);
+                        blend7_cols(Jc, wl, wr, Jp);
                         b1 = sdot2_first(Jp[0], Ixp[0], nc1); // seeds: minus the lane's sum I * Ix, sum I * Iy
                         b2 = sdot2_first(Jp[0], Iyp[0], nc2);
 #pragma unroll
@@ -497,10 +557,10 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                         const LkOrigin o = lk_tile_cover<WIN>(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
                         jx0 = o.x;
                         jy0 = o.y;
-                        uint32_t Jt[7], Jb[7], Jp[4];
-                        lk_cell_rows(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jt, Jb);
-                        lk_weights(ex - fex, ey - fey, wt, wb);
-                        blend7(Jt, Jb, wt, wb, Jp);
+                        uint32_t Jc[8], Jp[4];
+                        lk_cell_cols(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jc);
+                        lk_weights_cols(ex - fex, ey - fey, wl, wr);
+                        blend7_cols(Jc, wl, wr, Jp);
                         uint32_t e = 0; // lane 63 duplicates lane 62's pixels: it contributes nothing
 #pragma unroll
                         for (int m = 0; m < 4; m++) {

@@ -15,6 +15,10 @@
 //     v_dot2_i32_i16 with initial accumulator 1 << 15 leave DESCALE(S, 14) in the top 16 bits;
 //   * results are re-packed two per register (v_perm_b32) so that diff = val - I is one v_pk_sub_i16
 //     and b1 += diff*Ix, b2 += diff*Iy are one v_dot2_i32_i16 each per pixel pair.
+//   * the one-feature kernels group the same four products by COLUMN (lift8_cols / blend7_cols /
+//     bilinear7_deriv_cols below): vertical pairs (t[k], b[k]) against (iw00, iw10) and (iw01, iw11), so that
+//     every column is lifted once; the horizontal composites stay for the pair kernel of the developer build and
+//     as the statement the vertical ones are tested against (tests/host_check/lk_cols_cases.h).
 // Every step is exact integer arithmetic, so the result is bit-identical to the scalar formula.  The
 // host build of this header (tests/test_device_math_on_host.py) shows that for the `#else` text of the
 // wrappers (vo_isa.h); tests/test_gpu_device_units.py runs the instructions themselves on gfx950, every
@@ -105,6 +109,58 @@ VO_HD void blend7(const uint32_t pt[7], const uint32_t pb[7], uint32_t wt, uint3
         out[m] = pk_lshr1_u16(perm_b32(acc[2 * m + 1], acc[2 * m], VO_SEL_HI16));
 }
 
+// ---- the same samples from VERTICAL pairs --------------------------------------------------------
+// The four products of a sample can be grouped by column instead of by row:
+//     S[k] = dot2((t[k], b[k]), (iw00, iw10)) + dot2((t[k+1], b[k+1]), (iw01, iw11))
+// so the 8 columns of a segment are lifted ONCE each as (256*t[k], 256*b[k]) -- one v_perm_b32 of the two loaded dwords
+// that hold column k -- where the horizontal form lifts every inner column twice (14 pairs).  The weights go in as
+// wl = (iw00, iw10), wr = (iw01, iw11); the 14 dot products, their order and every partial sum's range are the same, and
+// so is every result, bit for bit.  lk.hip's one-feature kernels sample through these.
+// byte k (0..3) of `lo` and of `hi` into the high byte of the two u16 lanes: (256*lo[k], 256*hi[k])
+#define VO_SEL_COL(k) (0x0cu | ((uint32_t)(k) << 8) | (0x0cu << 16) | ((uint32_t)((k) + 4) << 24))
+VO_HD void lift8_cols(uint32_t t_lo, uint32_t t_hi, uint32_t b_lo, uint32_t b_hi, uint32_t col[8])
+{
+#define VO_LIFT(k) col[k] = perm_b32(b_lo, t_lo, VO_SEL_COL(k)), col[(k) + 4] = perm_b32(b_hi, t_hi, VO_SEL_COL(k));
+    VO_LIFT(0) VO_LIFT(1) VO_LIFT(2) VO_LIFT(3)
+#undef VO_LIFT
+}
+
+// blend7_cols(lift8_cols(t, b), wl, wr) == bilinear7_u8(t, b, wt, wb).  iw11 = -1 is the high lane of wr: that case
+// zeroes the weight and subtracts |iw11| * 256*b[k+1], the high lane of column k + 1.
+VO_HD void blend7_cols(const uint32_t col[8], uint32_t wl, uint32_t wr, uint32_t out[4])
+{
+    uint32_t acc[8];
+    if (!(wr & 0x80000000u)) {
+#pragma unroll
+        for (int k = 0; k < 7; k++)
+            acc[k] = udot2(col[k + 1], wr, udot2(col[k], wl, 1u << 16));
+    } else {
+        const uint32_t wr0 = wr & 0xffffu, kneg = (uint32_t)(-(int32_t)((int16_t)(wr >> 16)));
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            uint32_t c = col[k + 1];
+#if defined(__HIP_DEVICE_COMPILE__)
+            // the shift below depends on the column only: seen through, it is hoisted out of a caller's loop over weights
+            // into the code that lifts the columns, i.e. from the rare case into the common one
+            asm volatile("" : "+v"(c));
+#endif
+            acc[k] = udot2(c, wr0, udot2(col[k], wl, 1u << 16)) - kneg * (c >> 16);
+        }
+    }
+    acc[7] = 0;
+#pragma unroll
+    for (int m = 0; m < 4; m++)
+        out[m] = pk_lshr1_u16(perm_b32(acc[2 * m + 1], acc[2 * m], VO_SEL_HI16));
+}
+
+VO_HD void bilinear7_u8_cols(uint32_t t_lo, uint32_t t_hi, uint32_t b_lo, uint32_t b_hi, uint32_t wl, uint32_t wr,
+                             uint32_t out[4])
+{
+    uint32_t col[8];
+    lift8_cols(t_lo, t_hi, b_lo, b_hi, col);
+    blend7_cols(col, wl, wr, out);
+}
+
 // Scharr samples: d[k] = (4*Ix | 4*Iy << 16) of pixel x+k, rows top / bottom, k = 0..7.
 // ix[m] = (Ixval[2m], Ixval[2m+1]), iy likewise; *val[k] = DESCALE(sum d*iw, 14) of the true derivative.
 VO_HD void bilinear7_deriv(const uint32_t dt[8], const uint32_t db[8], uint32_t wt, uint32_t wb, uint32_t ix[4],
@@ -117,6 +173,30 @@ VO_HD void bilinear7_deriv(const uint32_t dt[8], const uint32_t db[8], uint32_t 
                       sdot2_first(perm_b32(dt[k + 1], dt[k], VO_SEL_LO16), wt, 1 << 15));
         ay[k] = sdot2(perm_b32(db[k + 1], db[k], VO_SEL_HI16), wb,
                       sdot2_first(perm_b32(dt[k + 1], dt[k], VO_SEL_HI16), wt, 1 << 15));
+    }
+    ax[7] = ay[7] = 0;
+#pragma unroll
+    for (int m = 0; m < 4; m++) {
+        ix[m] = perm_b32((uint32_t)ax[2 * m + 1], (uint32_t)ax[2 * m], VO_SEL_HI16);
+        iy[m] = perm_b32((uint32_t)ay[2 * m + 1], (uint32_t)ay[2 * m], VO_SEL_HI16);
+    }
+}
+
+// bilinear7_deriv on (wl, wr): column k regrouped as (Ix_t[k], Ix_b[k]) and (Iy_t[k], Iy_b[k]), 16 v_perm_b32 for 28
+VO_HD void bilinear7_deriv_cols(const uint32_t dt[8], const uint32_t db[8], uint32_t wl, uint32_t wr, uint32_t ix[4],
+                                uint32_t iy[4])
+{
+    uint32_t cx[8], cy[8];
+    int32_t ax[8], ay[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        cx[k] = perm_b32(db[k], dt[k], VO_SEL_LO16);
+        cy[k] = perm_b32(db[k], dt[k], VO_SEL_HI16);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) {
+        ax[k] = sdot2(cx[k + 1], wr, sdot2_first(cx[k], wl, 1 << 15));
+        ay[k] = sdot2(cy[k + 1], wr, sdot2_first(cy[k], wl, 1 << 15));
     }
     ax[7] = ay[7] = 0;
 #pragma unroll
