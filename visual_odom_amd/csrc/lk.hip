@@ -71,7 +71,7 @@ constexpr uint32_t lk_seg_mask(int valid, int m)
 // iw11 = 2^14 - iw00 - iw01 - iw10, returned as packed int16 pairs: by row, wt = (iw00, iw01), wb = (iw10, iw11)
 // (lk_weights: the samplers over horizontal pixel pairs), or by column, wl = (iw00, iw10), wr = (iw01, iw11)
 // (lk_weights_cols: the samplers over vertical pairs, vo_lkmath.h) -- the two differ in the packing selectors' operands only.
-//   * the scale is folded into the first factor ((1-a)*2^14 is exact, so the rounded product is identical);
+//   * the scale is folded in exactly (a power of two, see below);
 //   * cvRound (round half to even) = adding 1.5 * 2^23: the f32 sum has ulp 1, so the add rounds the
 //     product to the nearest-even integer and leaves it in the low mantissa bits.  The raw bit patterns
 //     are packed / summed directly (0x4B400000 has no low 16 bits), no v_rndne / v_cvt per weight.
@@ -79,10 +79,16 @@ template <bool COLS>
 __device__ __forceinline__ void lk_weights_packed(float a, float b, uint32_t &w0, uint32_t &w1)
 {
     const float s = (float)(1 << LK_W_BITS), magic = 12582912.f; // 1.5 * 2^23 = 0x4B400000
-    const float a1 = (1.f - a) * s, a0 = a * s, b1 = 1.f - b;
-    const uint32_t r00 = (uint32_t)__float_as_int(a1 * b1 + magic);
-    const uint32_t r01 = (uint32_t)__float_as_int(a0 * b1 + magic);
-    const uint32_t r10 = (uint32_t)__float_as_int(a1 * b + magic);
+    // Written on pairs, the way the packed f32 instructions take them: (a1, b1) = 1 - (a, b) is one subtraction, (a1 * b, b1 * a)
+    // one multiply of that pair with the swapped one.  The scale moves behind the product -- a power of two goes through a
+    // rounded product unchanged, fl((a1 * s) * b1) == fl(a1 * b1) * s, and where the product underflows both forms vanish in the
+    // sum -- so "* s + magic" is one fused multiply-add with an exact product: one rounding, the one the add always had.
+    typedef float F32x2 __attribute__((vector_size(8)));
+    const F32x2 p = {a, b}, q = 1.f - p, pswap = {b, a};
+    const F32x2 x = q * pswap; // (a1 * b, b1 * a)
+    const uint32_t r00 = (uint32_t)__float_as_int(fmaf(q[0] * q[1], s, magic));
+    const uint32_t r01 = (uint32_t)__float_as_int(fmaf(x[1], s, magic));
+    const uint32_t r10 = (uint32_t)__float_as_int(fmaf(x[0], s, magic));
     // iw11 = 2^14 - (r00 + r01 + r10 - 3 * 0x4B400000)   (mod 2^32)
     const uint32_t iw11 = ((1u << LK_W_BITS) + 3u * 0x4B400000u) - (r00 + r01 + r10);
     w0 = perm_b32(COLS ? r10 : r01, r00, VO_SEL_LO16);
@@ -432,7 +438,6 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
 
             nextX -= halfWin;
             nextY -= halfWin;
-            float prevDX = 0.f, prevDY = 0.f;
             int jx0 = 0, jy0 = 0;
             bool have_tile = false;
             // tile origins that keep the 40 x 48 tile inside the level's rectangle (vo_dev.h, "reads stay inside their level"):
@@ -446,93 +451,138 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             static_assert(VO_BY >= LW::COLS - 1, "right border (at least VO_BY columns) >= the columns a row reads beyond corner w - 1");
             const int jx_max = jstride - VO_BX - LK_JT_W, jy_max = jh + VO_BY - LK_JT_H;
 
-            // The window corner stays in the same pixel cell for two iterations out of three, so the Gauss-Newton
-            // loop is written as two loops: the outer one is entered once per cell and does everything that only
-            // depends on the cell -- admissibility test, tile test / refill, LDS address, the two row reads and the 8
-            // v_perm_b32 that lift the segment's columns into registers; the inner one iterates while the corner stays put.
+            // The window corner stays in the same pixel cell for two iterations out of three, so everything that only depends on
+            // the cell -- tile test / refill, LDS address, the two row reads and the 8 v_perm_b32 that lift the segment's columns
+            // into registers -- sits behind a wave-uniform "another cell" branch at the top of ONE loop: position, floors, deltas
+            // and the iteration count live in one set of registers, where an outer loop per cell and an inner loop per iteration
+            // copied them at every cell entry and back.  The admissibility test of a new cell sits where the cell is left (and
+            // in front of the loop for the first one), so the block behind the branch has no way out of the loop.
             int j = 0;
-            float fnx = floorf(nextX), fny = floorf(nextY);
-            bool run = prm.max_count > 0;
-            while (run) {
-                const int inx = uni(vo_f2i(fnx)), iny = uni(vo_f2i(fny));
-                if (VO_BALLOT(__builtin_isunordered(fnx, fny)) != 0ull || inx < -WIN || inx >= jw || iny < -WIN || iny >= jh) {
-                    if (level == 0)
-                        st = 0;
-                    break;
-                }
+            // how the loop was left: 0 = before any iteration of this level (out stays the level's start value: (x - halfWin) +
+            // halfWin is not x), else behind an iteration (out = next + halfWin): 1 = epsilon or count, 2 / 3 = the oscillation test,
+            // the delta of the half step back in (dAx, dAy) / (dBx, dBy), 4 = the next cell is not admitted
+            int left = 0;
+            float fnx = 0.f, fny = 0.f, frx = 0.f, fry = 0.f;
+            // the cell's columns (two window rows per lane) as vertical pixel pairs: eight scalars, not an array -- an array carried
+            // round the loop becomes one 8-register tuple, copied at every cell entry -- and set by nothing before the first cell
+            uint32_t J0, J1, J2, J3, J4, J5, J6, J7;
+#ifndef VO_HOST_EMUL
+            asm volatile("" : "=v"(J0), "=v"(J1), "=v"(J2), "=v"(J3), "=v"(J4), "=v"(J5), "=v"(J6), "=v"(J7));
+#else
+            J0 = J1 = J2 = J3 = J4 = J5 = J6 = J7 = 0;
+#endif
+            int inx = 0, iny = 0;
+            bool cell = true; // the corner is in another pixel cell than the registers hold (wave-uniform)
+            // the cell of the corner, and whether the reference admits it.  x86's cvFloor(NaN) is INT_MIN: rejected (see the template)
+            auto cell_admitted = [&]() -> bool {
+                fnx = floorf(nextX);
+                fny = floorf(nextY);
+                inx = uni(vo_f2i(fnx));
+                iny = uni(vo_f2i(fny));
+                return !(VO_BALLOT(__builtin_isunordered(fnx, fny)) != 0ull || inx < -WIN || inx >= jw || iny < -WIN || iny >= jh);
+            };
+            auto enter_cell = [&]() {
                 {
                     const LkOrigin o = lk_tile_cover<WIN>(s_jt, Jimg, jstride, jx_max, jy_max, inx, iny, lane, have_tile, jx0, jy0);
                     jx0 = o.x;
                     jy0 = o.y;
                     have_tile = true;
                 }
-                uint32_t Jc[8]; // the cell's columns (two window rows per lane) as vertical pixel pairs
-                lk_cell_cols(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jc); // uniform part on the scalar unit
-                // fractional position of the window corner inside its pixel cell: the bilinear weights come from it, and
-                // the corner is still inside the cell exactly as long as both parts are in [0, 1).  fl(nextX - fnx) is what
-                // OpenCV itself computes (nextPt.x - inextPt.x); a true difference >= 1 or < 0 can never round into [0, 1),
-                // so "inside" is never wrong -- a spurious "left" (difference just below 1 rounding up to 1.0) only
-                // re-enters the same cell through the outer loop.  As raw bits, [0, 1) is "below 0x3f800000, unsigned"
-                // (negative values have the sign bit set), so one unsigned max + one compare replace two floors, two
-                // compares and two selects per iteration.
-                for (;;) {
-                    lk_weights_cols(nextX - fnx, nextY - fny, wl, wr);
-                    int b1, b2;
-                    {
-                        uint32_t Jp[4];
-                        blend7_cols(Jc, wl, wr, Jp);
-                        b1 = sdot2_first(Jp[0], Ixp[0], nc1); // seeds: minus the lane's sum I * Ix, sum I * Iy
-                        b2 = sdot2_first(Jp[0], Iyp[0], nc2);
+                uint32_t Jn[8];
+                lk_cell_cols(s_jt, (iny - jy0) * LK_JT_W + (inx - jx0) + lane_off, Jn); // uniform part on the scalar unit
+                J0 = Jn[0], J1 = Jn[1], J2 = Jn[2], J3 = Jn[3], J4 = Jn[4], J5 = Jn[5], J6 = Jn[6], J7 = Jn[7];
+                frx = nextX - fnx;
+                fry = nextY - fny;
+            };
+            // One iteration: the delta into (dx, dy), tested against the one before it in (px, py).  Returns 0 = go on, or how the
+            // loop is left (a value, not a write to `left` / `st` from in here: behind the barriers below those would live in memory).
+            // (frx, fry) = the fractional position of the window corner inside its pixel cell: the bilinear weights come from it,
+            // and the corner is still inside the cell exactly as long as both parts are in [0, 1).  fl(nextX - fnx) is what
+            // OpenCV itself computes (nextPt.x - inextPt.x); a true difference >= 1 or < 0 can never round into [0, 1),
+            // so "inside" is never wrong -- a spurious "left" (difference just below 1 rounding up to 1.0) only
+            // re-enters the same cell.  As raw bits, [0, 1) is "below 0x3f800000, unsigned" (negative values have the
+            // sign bit set), so one unsigned max + one compare replace two floors, two compares and two selects per
+            // iteration; the two differences of that test are the next iteration's weight inputs.
+            auto iterate = [&](const float px, const float py, float &dx, float &dy, const int osc) -> int {
+                lk_weights_cols(frx, fry, wl, wr);
+                int b1, b2;
+                {
+                    const uint32_t Jc[8] = {J0, J1, J2, J3, J4, J5, J6, J7};
+                    uint32_t Jp[4];
+                    blend7_cols(Jc, wl, wr, Jp);
+                    b1 = sdot2_first(Jp[0], Ixp[0], nc1); // seeds: minus the lane's sum I * Ix, sum I * Iy
+                    b2 = sdot2_first(Jp[0], Iyp[0], nc2);
 #pragma unroll
-                        for (int m = 1; m < 4; m++) {
-                            b1 = sdot2(Jp[m], Ixp[m], b1);
-                            b2 = sdot2(Jp[m], Iyp[m], b2);
-                        }
+                    for (int m = 1; m < 4; m++) {
+                        b1 = sdot2(Jp[m], Ixp[m], b1);
+                        b2 = sdot2(Jp[m], Iyp[m], b2);
                     }
-                    float fb1, fb2;
-                    wave_sum2_exact_f32(b1, b2, fb1, fb2);
-                    const float dx = (A12s * fb2 - A22s * fb1) * D;
-                    const float dy = (A12s * fb1 - A11s * fb2) * D;
-                    nextX += dx;
-                    nextY += dy;
-                    outX = nextX + halfWin;
-                    outY = nextY + halfWin;
-                    // OpenCV: delta.ddot(delta) <= epsilon in f64.  The f32 value n2 is within 2^-23 of it, so it
-                    // decides on its own unless it falls inside a 1e-6 band around epsilon (then the f64 form).  The hot
-                    // path carries ONE compare ("clearly not converged"); everything else happens once per level.
-                    const float n2 = fmaf(dy, dy, dx * dx);
-                    if (__builtin_expect(!(n2 > eps_hi), 0)) {
+                }
+                float fb1, fb2;
+                wave_sum2_exact_f32(b1, b2, fb1, fb2);
+                dx = (A12s * fb2 - A22s * fb1) * D;
+                dy = (A12s * fb1 - A11s * fb2) * D;
+                nextX += dx;
+                nextY += dy;
+                // OpenCV: delta.ddot(delta) <= epsilon in f64.  The f32 value n2 is within 2^-23 of it, so it
+                // decides on its own unless it falls inside a 1e-6 band around epsilon (then the f64 form).  The hot
+                // path carries ONE compare ("clearly not converged"); everything else happens once per level.
+                const float n2 = fmaf(dy, dy, dx * dx);
+                if (__builtin_expect(!(n2 > eps_hi), 0)) {
 #ifndef VO_HOST_EMUL
-                        asm volatile("" ::: "memory"); // keep the rare evaluation out of the hot path
+                    asm volatile("" ::: "memory"); // keep the rare evaluation out of the hot path
 #endif
-                        if (n2 < eps_lo || (double)dx * dx + (double)dy * dy <= prm.epsilon) {
-                            run = false;
-                            break;
-                        }
-                    }
-                    // OpenCV: std::abs(delta.x + prevDelta.x) < 0.01 (f32 sum compared as double).  0.01f is
-                    // the largest f32 below the double 0.01, so for an f32 s:  |s| < 0.01  <=>  |s| <= 0.01f
-                    if (j > 0 && fabsf(dx + prevDX) <= 0.01f && fabsf(dy + prevDY) <= 0.01f) {
+                    if (n2 < eps_lo || (double)dx * dx + (double)dy * dy <= prm.epsilon)
+                        return 1;
+                }
+                // OpenCV: std::abs(delta.x + prevDelta.x) < 0.01 (f32 sum compared as double).  0.01f is
+                // the largest f32 below the double 0.01, so for an f32 s:  |s| < 0.01  <=>  |s| <= 0.01f
+                if (j > 0 && fabsf(dx + px) <= 0.01f && fabsf(dy + py) <= 0.01f)
+                    return osc;
+                if (++j >= prm.max_count)
+                    return 1;
+                frx = nextX - fnx;
+                fry = nextY - fny;
+                const uint32_t ua = (uint32_t)__float_as_int(frx), ub = (uint32_t)__float_as_int(fry);
+                cell = VO_BALLOT((ua > ub ? ua : ub) >= 0x3f800000u) != 0ull; // the corner left the cell
+                if (cell && !cell_admitted())
+                    return 4;
+                return 0;
+            };
+            // the previous delta is the other half's delta: unrolled by two with the roles of the two pairs exchanged, no copy
+            float dAx = 0.f, dAy = 0.f, dBx = 0.f, dBy = 0.f;
+            bool run = prm.max_count > 0;
+            if (run && !cell_admitted()) {
+                if (level == 0)
+                    st = 0;
+                run = false;
+            }
+            if (run)
+                for (;;) {
+                    if (cell)
+                        enter_cell();
+                    if ((left = iterate(dBx, dBy, dAx, dAy, 2)) != 0)
+                        break;
+                    if (cell)
+                        enter_cell();
+                    if ((left = iterate(dAx, dAy, dBx, dBy, 3)) != 0)
+                        break;
+                }
+            if (left == 4 && level == 0) // the corner left the image behind an iteration
+                st = 0;
+            // out = next + halfWin, read only here; the rounding order of the half step is (next + halfWin) - d * 0.5
+            if (left != 0) {
 #ifndef VO_HOST_EMUL
-                        asm volatile("" ::: "memory"); // do not speculate the half-step into every iteration
+                asm volatile("" ::: "memory"); // a branch, not selects on a copy of `left` made in every iteration
 #endif
-                        outX -= dx * 0.5f;
-                        outY -= dy * 0.5f;
-                        run = false;
-                        break;
-                    }
-                    prevDX = dx;
-                    prevDY = dy;
-                    if (++j >= prm.max_count) {
-                        run = false;
-                        break;
-                    }
-                    const uint32_t ua = (uint32_t)__float_as_int(nextX - fnx), ub = (uint32_t)__float_as_int(nextY - fny);
-                    if (VO_BALLOT((ua > ub ? ua : ub) >= 0x3f800000u) != 0ull) { // the corner left the cell
-                        fnx = floorf(nextX);
-                        fny = floorf(nextY);
-                        break;
-                    }
+                outX = nextX + halfWin;
+                outY = nextY + halfWin;
+                if (left == 2 || left == 3) {
+#ifndef VO_HOST_EMUL
+                    asm volatile("" ::: "memory");
+#endif
+                    outX -= (left == 2 ? dAx : dBx) * 0.5f;
+                    outY -= (left == 2 ? dAy : dBy) * 0.5f;
                 }
             }
 

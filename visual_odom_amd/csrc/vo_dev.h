@@ -226,7 +226,8 @@ __device__ __forceinline__ void wave_sum2_exact_f32(int a, int b, float &fa, flo
     u = dpp_add<VO_DPP_ROW_HALF_MIRROR, 0xf>(u);
     u = dpp_add<VO_DPP_ROW_MIRROR, 0xf>(u);
     const float uf = (float)u;
-    const float up = __int_as_float(VO_UPDATE_DPP(0, __float_as_int(uf), VO_DPP_ROW_BCAST15, 0xa, 0xf, true));
+    // (rows 0 and 2, which row_mask 0xa leaves at `old`, are never read: `old` is the dead u, not a zero to be made first)
+    const float up = __int_as_float(VO_UPDATE_DPP(u, __float_as_int(uf), VO_DPP_ROW_BCAST15, 0xa, 0xf, true));
     const float res = fmaf(up, 65536.f, uf);
     fa = __int_as_float(VO_READLANE(__float_as_int(res), 31));
     fb = __int_as_float(VO_READLANE(__float_as_int(res), 63));
