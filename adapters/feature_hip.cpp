@@ -114,6 +114,20 @@ void featureTracking_hip(cv::Mat img_1, cv::Mat img_2, std::vector<cv::Point2f>&
     status.swap(st);
 }
 
+void featureDetectionGoodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points)
+{
+    if (image.type() != CV_8UC1)
+        throw std::runtime_error("featureDetectionGoodFeaturesToTrack_hip: an 8-bit gray image");
+    vo_ctx* c = ctx_for(image.cols, image.rows, 1);
+    vocorn_params prm;
+    vocorn_default_params(&prm); // 5000, 0.01, 5.0 (feature.cpp:53-55)
+    std::vector<cv::Point2f> out((size_t)prm.max_corners);
+    int n = 0;
+    check(c, vocorn_detect(c, image.data, image.cols, image.rows, (int)image.step, &prm, &out[0].x, prm.max_corners, &n));
+    out.resize((size_t)(n < prm.max_corners ? n : prm.max_corners));
+    points.swap(out);
+}
+
 void triangulate_hip(cv::Mat& Pl, cv::Mat& Pr, std::vector<cv::Point2f>& pl, std::vector<cv::Point2f>& pr, cv::Mat& points3D_t0)
 {
     if (Pl.type() != CV_32F || Pr.type() != CV_32F || Pl.rows != 3 || Pl.cols != 4 || Pr.rows != 3 || Pr.cols != 4)

@@ -6,6 +6,7 @@
 //   triangulate_hip           replaces cv::triangulatePoints + cv::convertPointsFromHomogeneous   main.cpp:169-171
 //   detectAndBucket_hip       replaces the head of matchingFeatures     visualOdometry.cpp:95-108
 //   featureTracking_hip       same signature as featureTracking         feature.h:52      (body feature.cpp:64-74)
+//   featureDetectionGoodFeaturesToTrack_hip   same signature as featureDetectionGoodFeaturesToTrack   feature.h:50 (body feature.cpp:49-62)
 //
 // Switch: -DUSE_HIP next to the reference's own USE_CUDA (CMakeLists.txt:5-9, visualOdometry.cpp:112-118); see
 // adapters/USE_HIP.cmake and INTEGRATION.md.  OpenCV is needed for the TYPES of the existing signatures only (cv::Mat,
@@ -26,6 +27,7 @@
 #include "feature.h"          // FeatureSet (feature.h:33-43), from the reference tree
 #include "vo_hip.h"           // C ABI of libvo_hip.so
 #include "vo_flow.h"          // ... and its two-image tracker
+#include "vo_corners.h"       // ... and its Shi-Tomasi detector
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -51,6 +53,11 @@ void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features);
 // dropped for a negative coordinate), as the reference leaves them.  Drops the pair circularMatching_hip kept, if any.
 void featureTracking_hip(cv::Mat img_1, cv::Mat img_2, std::vector<cv::Point2f>& points1, std::vector<cv::Point2f>& points2,
                          std::vector<uchar>& status);
+
+// same signature as featureDetectionGoodFeaturesToTrack (feature.h:50): cv::goodFeaturesToTrack(image, points, 5000, 0.01, 5., Mat(),
+// 3, false, 0.04) through vocorn_detect of include/vo_corners.h -- the same corners in the same order.  The reference's frame loop
+// never calls it (it detects with FAST); the pair circularMatching_hip kept stays where it is.
+void featureDetectionGoodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points);
 
 // OPT-IN, default off: the caller promises that the t0 pair of every circularMatching_hip call IS the t1 pair of the call
 // before it -- the reference's loop hands its frames over exactly so (main.cpp:157-158: imageLeft_t0 = imageLeft_t1 shares

@@ -10,7 +10,8 @@ message when cv2 is missing.
     python tools/opencv_crosscheck.py --write-golden  # also dump cv2's outputs to tests/golden/opencv_<version>.npz
 
 Calls diffed (the reference's call sites): cv2.pyrDown (inside buildOpticalFlowPyramid), cv2.calcOpticalFlowPyrLK as
-feature.cpp:136-139 calls it (win 21, maxLevel 3, 30 / 0.01, minEig 1e-3), cv2.FAST(20, nonmax), cv2.triangulatePoints +
+feature.cpp:136-139 calls it (win 21, maxLevel 3, 30 / 0.01, minEig 1e-3), cv2.FAST(20, nonmax), cv2.cornerMinEigenVal(3, 3) + cv2.goodFeaturesToTrack as feature.cpp:53-55
+calls it (against tests/host_check/corners_ref.c), cv2.triangulatePoints +
 convertPointsFromHomogeneous (main.cpp:170-171), cv2.solvePnPRansac + Rodrigues (visualOdometry.cpp:176,188; also with exactly 4 points = the P3P switch) and
 cv2.findEssentialMat + recoverPose (visualOdometry.cpp:152-153).  Expected against x86 OpenCV: pyramids and FAST
 bit-exact, LK positions within ~1e-3 px with identical status (OpenCV accumulates the 2x2 system in f32 SIMD lanes, the
@@ -70,6 +71,26 @@ def main():
     my0 = orc.fast_detect(L[0], 20, False, cap=1 << 20)
     report("FAST(20, no nonmax) corners + order", 0.0 if cv0.shape == my0.shape and np.array_equal(cv0, my0) else 1.0, 0,
            "cv2 %d / oracle %d" % (len(cv0), len(my0)))
+    # ---- Shi-Tomasi (include/vo_corners.h): cv2.cornerMinEigenVal(3, 3) and cv2.goodFeaturesToTrack as feature.cpp:49-62 calls it,
+    # against tests/host_check/corners_ref.c -- the restatement the device path is held to bit for bit.  Expected: identical bits
+    # from a build whose filter and calcMinEigenVal paths do not fuse multiply-adds (the x86-64 baseline); an FMA build (AVX2
+    # dispatch of the separable filter) may differ in the last bit of the map, and then in corners whose qualities nearly tie.
+    # The golden file takes the outputs on a 320 x 96 crop (the whole map is beyond the size limit of a committed file).
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import corners_emu as ce
+    for name, img in (("full", L[0]), ("crop", np.ascontiguousarray(L[0][140:236, 400:720]))):
+        eig_cv = cv2.cornerMinEigenVal(img, 3, ksize=3)
+        eig_my = ce.ref_map(img)
+        nbits = int((eig_cv.view(np.uint32) != eig_my.view(np.uint32)).sum())
+        report("cornerMinEigenVal(3, 3) %s" % name, float(np.abs(eig_cv - eig_my).max()), 0, "%d of %d values differ in their bits" % (nbits, eig_my.size))
+        for md in (5.0, 0.0, 10.5):
+            c_cv = cv2.goodFeaturesToTrack(img, 5000, 0.01, md, None, None, 3, False, 0.04)
+            c_cv = np.zeros((0, 2), np.float32) if c_cv is None else c_cv.reshape(-1, 2)
+            c_my = ce.ref_detect(img, 5000, 0.01, md)[0]
+            same = c_cv.shape == c_my.shape and np.array_equal(c_cv, c_my)
+            report("goodFeaturesToTrack(5000, 0.01, %g) %s corners + order" % (md, name), 0.0 if same else 1.0, 0, "cv2 %d / ref %d" % (len(c_cv), len(c_my)))
+            if name == "crop" and md == 5.0:
+                golden["corn_crop"], golden["corn_eig"], golden["corn_pts"] = img, eig_cv, c_cv
     # ---- the four LK hops
     lk = dict(winSize=(21, 21), maxLevel=3, criteria=(cv2.TERM_CRITERIA_COUNT + cv2.TERM_CRITERIA_EPS, 30, 0.01), flags=0,
               minEigThreshold=0.001)

@@ -46,6 +46,8 @@ FLOW_EXPORTS = ("voflow_track", "voflow_feature_tracking", "voflow_batch_set_pai
 WIN_EXPORTS = ("vowin_track", "vowin_feature_tracking", "vowin_batch_run", "vowin_max_level")
 # every symbol include/vo_flow_flags.h declares: the same tracker with cv::calcOpticalFlowPyrLK's flags, and the two flags
 FLAG_EXPORTS = ("voflag_track", "voflag_feature_tracking", "voflag_batch_set_guess", "voflag_batch_run")
+# include/vo_corners.h: the Shi-Tomasi detector (goodFeaturesToTrack / cornerMinEigenVal), the fifth header
+CORN_EXPORTS = ("vocorn_default_params", "vocorn_detect", "vocorn_min_eigen_map", "vocorn_batch_run", "vocorn_batch_get")
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -105,6 +107,11 @@ class VoSchedule(C.Structure):
     _fields_ = [("pose_waves", C.c_int), ("pose_streams", C.c_int), ("prepare", C.c_int), ("epnp_wide_frames", C.c_int)]
 
 
+class VoCornParams(C.Structure):
+    """vocorn_params (include/vo_corners.h)"""
+    _fields_ = [("max_corners", C.c_int), ("quality_level", C.c_double), ("min_distance", C.c_double)]
+
+
 class VoError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libvo_hip error %d: %s" % (code, msg))
@@ -150,6 +157,14 @@ def load():
     lib.voflag_batch_set_guess.argtypes = [vp, i, vp, i]
     lib.voflag_batch_run.argtypes = [vp, i, i]
     for name in FLOW_EXPORTS + WIN_EXPORTS + FLAG_EXPORTS:
+        getattr(lib, name).restype = C.c_int
+    lib.vocorn_default_params.argtypes = [C.POINTER(VoCornParams)]
+    lib.vocorn_default_params.restype = None
+    lib.vocorn_detect.argtypes = [vp, vp, i, i, i, C.POINTER(VoCornParams), vp, i, vp]
+    lib.vocorn_min_eigen_map.argtypes = [vp, vp, i, i, i, vp, i]
+    lib.vocorn_batch_run.argtypes = [vp, C.POINTER(VoCornParams), i, i]
+    lib.vocorn_batch_get.argtypes = [vp, i, vp, i, vp]
+    for name in CORN_EXPORTS[1:]:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -532,6 +547,48 @@ class Context:
         if n.value > cap:
             raise VoError(VO_ERR_ARG, "fast_detect: %d corners exceed cap %d" % (n.value, cap))
         return pts[:n.value].copy()
+
+    # ---- Shi-Tomasi detector (include/vo_corners.h) -----------------------------------------
+    def _corn_image(self, img):
+        if img is None:   # the left image of the pair the last track_frame kept
+            (h, w), stride = self._kept_shape, self._kept_shape[1]
+        else:
+            (img,), stride = _imgs(img, fmt=self.input_format)
+            h, w = img.shape[:2]
+        return img, w, h, stride
+
+    def good_features_to_track(self, img, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None):
+        """featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) = cv::goodFeaturesToTrack(img, max_corners, quality_level,
+        min_distance): corners best first, (n, 2) float32.  cap: rows to fetch (default: all that were found)"""
+        img, w, h, stride = self._corn_image(img)
+        prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        n = C.c_int(0)
+        first = 8192 if cap is None else int(cap)
+        pts = np.zeros((max(first, 1), 2), np.float32)
+        self._chk(self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), _p(pts), first, C.byref(n)))
+        if cap is None and n.value > first:   # nothing is truncated: fetch again with room for all
+            pts = np.zeros((n.value, 2), np.float32)
+            self._chk(self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), _p(pts), n.value, C.byref(n)))
+        return pts[:min(n.value, len(pts) if cap is None else first)].copy()
+
+    def corners_batch_run(self, first_image, n_images, max_corners=5000, quality_level=0.01, min_distance=5.0):
+        """the detector over images first_image .. first_image + n_images - 1 of the batch image table, enqueued"""
+        prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        self._chk(self.lib.vocorn_batch_run(self.h, C.byref(prm), int(first_image), int(n_images)))
+
+    def corners_batch_get(self, image_idx, cap=8192):
+        """(corners [min(n, cap), 2], n) of one image of the latest corners_batch_run"""
+        pts = np.zeros((max(cap, 1), 2), np.float32)
+        n = C.c_int(0)
+        self._chk(self.lib.vocorn_batch_get(self.h, int(image_idx), _p(pts), int(cap), C.byref(n)))
+        return pts[:min(n.value, cap)].copy(), n.value
+
+    def corner_min_eigen_val(self, img):
+        """cv::cornerMinEigenVal(img, 3, 3): (h, w) float32"""
+        img, w, h, stride = self._corn_image(img)
+        eig = np.zeros((h, w), np.float32)
+        self._chk(self.lib.vocorn_min_eigen_map(self.h, _pn(img), w, h, stride, _p(eig), w))
+        return eig
 
     def detect_bucket(self, img, pts, ages, **detect_kw):
         """appendNewFeatures (if fewer than redetect_below points) + bucketingFeatures

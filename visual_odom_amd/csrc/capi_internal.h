@@ -330,6 +330,19 @@ struct vo_ctx {
         int cfg[4] = {0, 0, 0, 0};   // n_images, w, h, n_frames of the table the pairs were set for
         std::vector<uint8_t> next_set; // [max_frames] the frame's d_next rows hold a guess or a run's results since the pairs were set
     } flow;
+    // ---- Shi-Tomasi detector (vocorn_*, include/vo_corners.h, capi_corners.hip): allocated by the first such call, regrown when a
+    // batch run covers more images than any before it ----
+    struct Corn {
+        int slots = 0;               // image slots the buffers below hold
+        int kcap = 0;                // power of two >= fcap: the sort's length
+        unsigned *d_ints = nullptr;  // [3][slots]: max_key, ncand, nout
+        unsigned long long *d_keys = nullptr, *d_ckeys = nullptr; // [slots][kcap]
+        int *d_status = nullptr;     // [slots][fcap]
+        float2 *d_pts = nullptr;     // [slots][fcap]
+        float *d_maps = nullptr;     // [slots][max_h * max_w] the quality maps (slot 0: vocorn_min_eigen_map's too)
+        int run_first = 0, run_n = 0; // image range of the latest vocorn_batch_run (run_n = 0: none since the table was configured)
+        int cfg[3] = {0, 0, 0};      // n_images, w, h of the table it ran on
+    } corn;
     // ---- lock-step sequence loop (vo_seq_*): S sequences x 1 frame per step, state carried on the device ----
     struct Seq {
         bool on = false;

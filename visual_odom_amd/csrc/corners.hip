@@ -1,0 +1,347 @@
+// corners.hip -- the Shi-Tomasi detector of include/vo_corners.h: cv::cornerMinEigenVal(img, eig, 3, 3) and
+// cv::goodFeaturesToTrack(img, pts, maxCorners, qualityLevel, minDistance, noArray(), 3, false, 0.04) of OpenCV 4.5 on the level-0
+// image of the image table, bit for bit what tests/host_check/corners_ref.c restates from upstream.
+//
+//   corn_map_kernel      one thread per image column, walking down it: the quality map in upstream's own summation order, and its
+//                        maximum (minMaxLoc) by one atomicMax per workgroup
+//   corn_cand_kernel     one workgroup per 64 x 16 tile of the map: threshold(TOZERO) at (float)(max * qualityLevel), dilate 3 x 3,
+//                        candidates `val != 0 && val == dilated` appended to the image's list as (ordered quality bits, y w + x)
+//   corn_select_kernel   one workgroup per image: sort, minDistance suppression, the corners in order
+//
+// Why a thread per column.  boxFilter sums the f32 products in f64, and its column pass (ColumnSum<double, float>) is a RUNNING sum
+// down the whole column: SUM += row(y + 1); out = SUM; SUM -= row(y - 1).  The f64 operations are not exact in general -- a dy of
+// one ulp gives a product 70 bits under the sum's top bit -- and an inexact step leaves a residual in SUM that every row below
+// inherits (about 1e-19 in a flat region under a textured one, where the plain three-term sum gives 0).  So the sum is not
+// order-free, and the kernel sums in upstream's order, which is serial in y.  The columns of 256 images are 318 k threads.
+//
+// The candidate test is upstream's literally (thresholded value against the 3 x 3 maximum of thresholded values) on the stored map,
+// so the candidate list is upstream's own tmpCorners and needs no argument about non-positive values.
+//
+// Pixels are fetched with REFLECT_101 index arithmetic on the image's own w x h, not from the bordered level: the border is filled by
+// the pyramid stage, and this detector runs on an image that has been uploaded and nothing else (a "stale" image of the batch API
+// is fine here).  Every load stays inside rows 0 .. h - 1, columns 0 .. w - 1.
+//
+// Numerics (no FMA contraction: -ffp-contract=off, as the emulator build): Sobel as upstream's separable f32 filter with the scale
+// folded into the smoothing taps, products in f32, row sums (c(x-1) + c(x)) + c(x+1) in f64 (RowSum's ksize == 3 branch), the running
+// column sum, one cast to f32.  The box sum's border samples are the COV image reflected -- the cov of the reflected POSITION --
+// never cov of the reflected source (dx changes sign under reflection, so dx dy would).
+#include "vo_corners_dev.h"
+
+namespace vo {
+
+constexpr int CM_T = 256, CM_COLS = CM_T - 2;     // map kernel: threads per workgroup; columns it owns (+ one halo column each side)
+constexpr int CT_W = 64, CT_H = 16;               // candidate kernel: tile
+constexpr int CV_W = CT_W + 2, CV_H = CT_H + 2;   // ... and its values: + the 3 x 3 neighbours of the tile's pixels
+constexpr int CORN_SELECT_THREADS = 1024;
+
+__device__ __forceinline__ int corn_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// map: [n][map_stride] floats, slot s = image first + s, rows tight (w floats).  max_key: [n] or null.
+__global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+                                                        unsigned *__restrict__ max_key)
+{
+    __shared__ float s_cov[3][CM_T];
+    __shared__ unsigned s_max;
+    const int tid = threadIdx.x, slot = blockIdx.y;
+    const PyrImage &im = imgs[first + slot];
+    const int w = im.w[0], h = im.h[0], stride = im.stride[0];
+    const VO_GLOBAL uint8_t *__restrict__ src = (const VO_GLOBAL uint8_t *)im.lvl[0];
+    float *__restrict__ map = maps + (size_t)slot * map_stride;
+    // this thread's cov column: x of the COV image, which outside the image is the cov of the reflected position rx (boxFilter
+    // reflects the cov image); its Sobel reads the source around rx, reflected in turn
+    const int x = (int)blockIdx.x * CM_COLS - 1 + tid;
+    const int rx = reflect101(corn_clamp(x, -1, w), w), xa = reflect101(rx - 1, w), xc = reflect101(rx + 1, w);
+    const bool owner = tid >= 1 && tid <= CM_COLS && x < w; // (x >= 0 then)
+    if (tid == 0)
+        s_max = 0;
+    const float sf = (float)(1.0 / (255.0 * 4.0 * 3.0)), sf2 = sf * 2.f;
+    double sum[3] = {0, 0, 0}, r_prev[3] = {0, 0, 0}, r_cur[3] = {0, 0, 0}; // SUM, row(y - 1), row(y) of ColumnSum
+    unsigned best = 0;
+    for (int yy = -1; yy <= h; yy++) { // cov row yy enters the column sum; the map row yy - 1 leaves it
+        const int ry = reflect101(yy, h);
+        float rd[3], rs[3];
+        for (int j = 0; j < 3; j++) { // RowFilter<uchar, float>: s = k0 p(x-1); s += k1 p(x); s += k2 p(x+1)
+            const VO_GLOBAL uint8_t *row = src + (ptrdiff_t)reflect101(ry + j - 1, h) * stride;
+            const float pa = (float)row[xa], pb = (float)row[rx], pc = (float)row[xc];
+            float s = -1.f * pa;
+            s += 0.f * pb;
+            s += 1.f * pc;
+            rd[j] = s;
+            s = sf * pa;
+            s += sf2 * pb;
+            s += sf * pc;
+            rs[j] = s;
+        }
+        const float dx = (rd[0] + rd[2]) * sf + rd[1] * sf2; // SymmColumnSmallFilter, symmetric
+        const float dy = rs[2] - rs[0];                      // ... and its [-1, 0, 1] branch
+        s_cov[0][tid] = dx * dx;
+        s_cov[1][tid] = dx * dy;
+        s_cov[2][tid] = dy * dy;
+        __syncthreads();
+        double r[3] = {0, 0, 0};
+        if (owner)
+            for (int k = 0; k < 3; k++) // RowSum<float, double>, ksize == 3
+                r[k] = ((double)s_cov[k][tid - 1] + (double)s_cov[k][tid]) + (double)s_cov[k][tid + 1];
+        __syncthreads();
+        if (!owner)
+            continue;
+        if (yy <= 0) { // SUM = 0; SUM += row(-1); SUM += row(0)
+            for (int k = 0; k < 3; k++) {
+                sum[k] += r[k];
+                r_prev[k] = r_cur[k];
+                r_cur[k] = r[k];
+            }
+            continue;
+        }
+        float box[3];
+        for (int k = 0; k < 3; k++) { // s0 = SUM + row(y + 1); D = (float)s0; SUM = s0 - row(y - 1)
+            const double s0 = sum[k] + r[k];
+            box[k] = (float)s0;
+            sum[k] = s0 - r_prev[k];
+            r_prev[k] = r_cur[k];
+            r_cur[k] = r[k];
+        }
+        const float ea = box[0] * 0.5f, eb = box[1], ec = box[2] * 0.5f; // calcMinEigenVal
+        const float e = (ea + ec) - sqrtf((ea - ec) * (ea - ec) + eb * eb);
+        map[(size_t)(yy - 1) * w + x] = e;
+        const unsigned key = corn_ord(e);
+        best = key > best ? key : best;
+    }
+    if (!max_key) // (uniform)
+        return;
+    if (best)
+        atomicMax(&s_max, best);
+    __syncthreads();
+    if (tid == 0 && s_max)
+        atomicMax(&max_key[slot], s_max);
+}
+
+__global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_x, CornArgs a)
+{
+    __shared__ float s_val[CV_H * CV_W];
+    __shared__ unsigned long long s_list[CT_W * CT_H];
+    __shared__ int s_cnt, s_base;
+    const int tid = threadIdx.x, slot = blockIdx.y;
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * CT_W, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * CT_H;
+    const float *__restrict__ map = a.maps + (size_t)slot * a.map_stride;
+    if (tid == 0)
+        s_cnt = 0;
+    // the map at x0 - 1 .. x0 + 64, y0 - 1 .. y0 + 16, clamped into the image (a clamped value is never a candidate's neighbour)
+    for (int i = tid; i < CV_H * CV_W; i += 256)
+        s_val[i] = map[(size_t)corn_clamp(y0 - 1 + i / CV_W, 0, h - 1) * w + corn_clamp(x0 - 1 + i % CV_W, 0, w - 1)];
+    __syncthreads();
+    // minMaxLoc's maxVal is a double; threshold() casts the product to the map's type
+    const float thresh = (float)((double)corn_unord(a.max_key[slot]) * a.quality);
+    for (int i = tid; i < CT_W * CT_H; i += 256) {
+        const int lx = i % CT_W, ly = i / CT_W, x = x0 + lx, y = y0 + ly;
+        if (x < 1 || x > w - 2 || y < 1 || y > h - 2)
+            continue;
+        const float *q = s_val + ly * CV_W + lx; // top-left neighbour
+        const float v = q[CV_W + 1] > thresh ? q[CV_W + 1] : 0.f;
+        if (v == 0.f)
+            continue;
+        float m = v;
+        for (int j = 0; j < 3; j++)
+            for (int k = 0; k < 3; k++) {
+                const float t = q[j * CV_W + k] > thresh ? q[j * CV_W + k] : 0.f;
+                m = t > m ? t : m;
+            }
+        if (v == m)
+            s_list[atomicAdd(&s_cnt, 1)] = ((unsigned long long)corn_ord(v) << 32) | (unsigned)(y * w + x);
+    }
+    __syncthreads();
+    if (tid == 0)
+        s_base = s_cnt ? atomicAdd(&a.ncand[slot], s_cnt) : 0;
+    __syncthreads();
+    unsigned long long *keys = a.keys + (size_t)slot * a.kcap;
+    for (int i = tid; i < s_cnt; i += 256)
+        if (s_base + i < a.lcap)
+            keys[s_base + i] = s_list[i];
+}
+
+// bitonic sort of keys[0 .. n), n a power of two, by the whole workgroup (every key is distinct)
+__device__ void corn_sort(unsigned long long *keys, int n, bool descending)
+{
+    const int tid = threadIdx.x, T = blockDim.x;
+    for (int k = 2; k <= n; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < n / 2; t += T) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const unsigned long long ki = keys[i], kl = keys[l];
+                const bool up = ((i & k) == 0) != descending; // this pair belongs to an ascending run
+                if ((ki > kl) == up) {
+                    keys[i] = kl;
+                    keys[l] = ki;
+                }
+            }
+            __syncthreads();
+        }
+}
+
+// The rest of goodFeaturesToTrack for one image per workgroup.
+//   sort        std::sort with greaterThanPtr = descending by (quality, address): the 64-bit keys, which are distinct.
+//   suppression upstream's loop walks the sorted list and accepts a candidate iff no ACCEPTED candidate before it lies in the 3 x 3
+//               cells around its own closer than minDistance.  That is the lexicographically first maximal independent set of the
+//               conflict relation (same 3 x 3 cell neighbourhood and dx^2 + dy^2 < minDistance^2, symmetric), computed in rounds:
+//               an undecided candidate is rejected once a better conflicting one is accepted, accepted once every better
+//               conflicting one is rejected.  The best undecided candidate is decided in every round, so the loop ends; decisions
+//               are final and each is the serial loop's, by induction over the rank.  A round reads only decisions of EARLIER
+//               rounds (status carries the round), so the round count is a property of the input: the depth of its dependency chain.
+//   cells       found through a second sorted list (cell, rank): the three cell rows around a candidate are three contiguous
+//               ranges of it, each by one binary search.  O(candidates) memory whatever the cell size.
+//   maxCorners  the loop stops at maxCorners accepted = the first maxCorners accepted in rank order.
+__global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornArgs a, int w, int h)
+{
+    __shared__ int s_part[CORN_SELECT_THREADS];
+    __shared__ int s_flag[3];
+    const int tid = threadIdx.x, T = blockDim.x, slot = blockIdx.x;
+    const int n = a.ncand[slot];
+    if (n > a.lcap) { // (uniform) nothing is silently truncated: the host reports VO_ERR_OVERFLOW
+        if (tid == 0) {
+            a.nout[slot] = -1;
+            if (a.rounds)
+                a.rounds[slot] = 0;
+        }
+        return;
+    }
+    unsigned long long *keys = a.keys + (size_t)slot * a.kcap, *ckeys = a.ckeys + (size_t)slot * a.kcap;
+    int *st = a.status + (size_t)slot * a.lcap;
+    float2 *pts = a.pts + (size_t)slot * a.lcap;
+    int np = 1;
+    while (np < n)
+        np <<= 1;
+    for (int i = n + tid; i < np; i += T)
+        keys[i] = 0; // (below every key: corn_ord is never 0 for a value that passed the threshold)
+    __syncthreads();
+    corn_sort(keys, np, true);
+    const int limit = a.max_corners > 0 && a.max_corners < n ? a.max_corners : n;
+    if (a.lim <= 1) { // minDistance < 1, or so small that no two pixels conflict: the first maxCorners of the list
+        for (int i = tid; i < limit; i += T) {
+            const int idx = (int)(unsigned)keys[i];
+            pts[i] = make_float2((float)(idx % w), (float)(idx / w));
+        }
+        if (tid == 0) {
+            a.nout[slot] = limit;
+            if (a.rounds)
+                a.rounds[slot] = 0;
+        }
+        return;
+    }
+    const int cell = a.cell, gw = (w + cell - 1) / cell, gh = (h + cell - 1) / cell;
+    for (int i = tid; i < np; i += T) {
+        if (i < n) {
+            const int idx = (int)(unsigned)keys[i];
+            ckeys[i] = ((unsigned long long)(unsigned)((idx / w) / cell * gw + (idx % w) / cell) << 32) | (unsigned)i;
+            st[i] = 0;
+        } else
+            ckeys[i] = ~0ull;
+    }
+    if (tid < 3)
+        s_flag[tid] = 0;
+    __syncthreads();
+    corn_sort(ckeys, np, false);
+    int round = 0;
+    for (;;) {
+        round++;
+        if (tid == 0)
+            s_flag[(round + 1) % 3] = 0; // (read last in round - 2)
+        bool left = false;
+        for (int i = tid; i < n; i += T) {
+            if (st[i] != 0) // (st is read and written by different threads inside a round without atomics, on purpose: an aligned
+                continue;   // int is never torn, and the round stamp makes a value written in this round read as "undecided")
+            const int idx = (int)(unsigned)keys[i], x = idx % w, y = idx / w, xc = x / cell, yc = y / cell;
+            const int c0 = xc > 0 ? xc - 1 : 0, c1 = xc < gw - 1 ? xc + 1 : gw - 1;
+            int verdict = 1; // 1 accept, 0 reject, -1 wait
+            for (int yy = (yc > 0 ? yc - 1 : 0); yy <= (yc < gh - 1 ? yc + 1 : gh - 1) && verdict != 0; yy++) {
+                const unsigned long long lo_key = (unsigned long long)(unsigned)(yy * gw + c0) << 32;
+                const unsigned hi_cell = (unsigned)(yy * gw + c1);
+                int lo = 0, hi = n; // first entry >= lo_key
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ckeys[mid] < lo_key)
+                        lo = mid + 1;
+                    else
+                        hi = mid;
+                }
+                for (int p = lo; p < n; p++) {
+                    const unsigned long long ck = ckeys[p];
+                    if ((unsigned)(ck >> 32) > hi_cell)
+                        break;
+                    const int j = (int)(unsigned)ck;
+                    if (j >= i)
+                        continue;
+                    const int jdx = (int)(unsigned)keys[j], ddx = x - jdx % w, ddy = y - jdx / w;
+                    if (ddx * ddx + ddy * ddy >= a.lim)
+                        continue;
+                    const int sj = st[j];
+                    if (sj == 0 || (sj >> 1) >= round)
+                        verdict = -1; // undecided before this round
+                    else if (sj & 1) {
+                        verdict = 0;
+                        break;
+                    }
+                }
+            }
+            if (verdict >= 0)
+                st[i] = round << 1 | verdict;
+            else
+                left = true;
+        }
+        if (left)
+            s_flag[round % 3] = 1;
+        __syncthreads();
+        if (!s_flag[round % 3])
+            break;
+    }
+    // one scan over the rank-ordered accept flags: contiguous chunks, chunk totals through LDS
+    const int chunk = (n + T - 1) / T, b = tid * chunk < n ? tid * chunk : n, e = b + chunk < n ? b + chunk : n;
+    int mine = 0;
+    for (int i = b; i < e; i++)
+        mine += st[i] & 1;
+    s_part[tid] = mine;
+    __syncthreads();
+    int off = 0, total = 0;
+    for (int t = 0; t < T; t++) {
+        off += t < tid ? s_part[t] : 0;
+        total += s_part[t];
+    }
+    const int cut = a.max_corners > 0 && a.max_corners < total ? a.max_corners : total;
+    for (int i = b; i < e; i++)
+        if (st[i] & 1) {
+            if (off < cut) {
+                const int idx = (int)(unsigned)keys[i];
+                pts[off] = make_float2((float)(idx % w), (float)(idx / w));
+            }
+            off++;
+        }
+    if (tid == 0) {
+        a.nout[slot] = cut;
+        if (a.rounds)
+            a.rounds[slot] = round;
+    }
+}
+
+#ifndef VO_HOST_EMUL
+hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    hipError_t e = hipMemsetAsync(a.max_key, 0, sizeof(unsigned) * (size_t)n, stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.ncand, 0, sizeof(int) * (size_t)n, stream);
+    if (e != hipSuccess)
+        return e;
+    const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
+    hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key);
+    hipLaunchKernelGGL(corn_cand_kernel, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a);
+    hipLaunchKernelGGL(corn_select_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h);
+    return hipGetLastError();
+}
+
+void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream)
+{
+    hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, 1), dim3(CM_T), 0, stream, d_imgs, image, d_map, (size_t)0, (unsigned *)nullptr);
+}
+#endif
+
+} // namespace vo

@@ -1,0 +1,59 @@
+// vo_corners_dev.h -- what corners.hip (the Shi-Tomasi detector's kernels), its host code capi_corners.hip and the CPU emulator
+// harness of the tests share: the argument record of the kernels and their launch wrapper.
+#pragma once
+#include "vo_dev.h"
+
+#include <string.h>
+
+namespace vo {
+
+// One run over n image slots (slot s = image `first + s` of the image table).  Every per-slot array is indexed by the slot.
+struct CornArgs {
+    unsigned *max_key;         // [n] ordered bits (corn_ord) of the quality map's maximum; 0 before the run
+    int *ncand;                // [n] candidates that passed the threshold (may exceed lcap: nothing beyond it is stored); 0 before
+    int *nout;                 // [n] corners found, -1: the candidate list overflowed
+    int *rounds;               // [n] rounds the suppression took, or null (the library does not ask; the emulator harness does)
+    float *maps;               // [n][map_stride] the quality maps, rows tight (w floats)
+    size_t map_stride;
+    unsigned long long *keys;  // [n][kcap] candidates as (corn_ord(quality) << 32 | y * w + x), sorted descending by the select kernel
+    unsigned long long *ckeys; // [n][kcap] (cell << 32 | rank), ascending
+    int *status;               // [n][lcap] 0 undecided, else round << 1 | accepted
+    float2 *pts;               // [n][lcap] the corners, best first
+    int lcap, kcap;            // list capacity; kcap = the power of two >= lcap
+    double quality;            // qualityLevel
+    int max_corners;           // <= 0: no limit
+    int cell;                  // cvRound(minDistance), >= 1
+    int lim;                   // two candidates of neighbouring cells conflict iff dx^2 + dy^2 < lim (= ceil(minDistance^2)); <= 1: none can
+};
+
+// A float's bits as an unsigned that orders like the float (negative values included): the map maximum by atomicMax, the sort key
+__host__ __device__ inline unsigned corn_ord(float v)
+{
+    unsigned u;
+    memcpy(&u, &v, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ inline float corn_unord(unsigned k)
+{
+    const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+inline int corn_pow2(int n)
+{
+    int p = 1;
+    while (p < n)
+        p <<= 1;
+    return p;
+}
+
+#ifndef VO_HOST_EMUL
+// the whole detector over n slots: map + maximum, candidates, sort + suppression + output (three launches on `stream`; max_key and
+// ncand are zeroed first).  Returns the first HIP error of the memsets and launches.
+hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream);
+// cv::cornerMinEigenVal of image `image` into map [h][w] (tight)
+void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream);
+#endif
+
+} // namespace vo
