@@ -288,30 +288,28 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
         const int ni = hop == 0 ? q.r0 : hop == 1 ? q.r1 : hop == 2 ? q.l1 : q.l0;
         const PyrImage &I = imgs[pi];
         const PyrImage &J = imgs[ni];
-        float outX = 0.f, outY = 0.f;
+        // `out` enters the level loop as the point the hop starts from, and every level starts at out * m: m = 2^-level at the
+        // deepest level, 2 at every other -- one wave-uniform factor, chosen on the scalar unit, where a select between the scaled
+        // start point and 2 * out took two v_cndmask_b32 on the position.  (x * 2.f is x + x bit for bit, NaN and +-inf included.)
+        float outX = prm.max_level >= 0 ? prevPtX : 0.f, outY = prm.max_level >= 0 ? prevPtY : 0.f;
+        if constexpr (FLAGS) {
+            if ((flags & VO_LK_USE_INITIAL_FLOW) && prm.max_level >= 0) { // OpenCV: nextPts[ptidx] * (float)(1. / (1 << level)), one exact multiply
+                const float2 g = trk[(size_t)frame * cap + f];
+                outX = unif(g.x);
+                outY = unif(g.y);
+            }
+        }
         int st = 1;
         float errv = 0.f; // (ERR)
 
         for (int level = prm.max_level; level >= 0; level--) {
             const float scale = __int_as_float((127 - level) << 23); // 2^-level, exact (no divide)
             float prevX = prevPtX * scale, prevY = prevPtY * scale;
-            float nextX, nextY;
-            if (level == prm.max_level) {
-                nextX = prevX;
-                nextY = prevY;
-                if constexpr (FLAGS) {
-                    if (flags & VO_LK_USE_INITIAL_FLOW) { // OpenCV: nextPts[ptidx] * (float)(1. / (1 << level)), one exact multiply
-                        const float2 g = trk[(size_t)frame * cap + f];
-                        nextX = unif(g.x) * scale;
-                        nextY = unif(g.y) * scale;
-                    }
-                }
-            } else {
-                nextX = outX * 2.f;
-                nextY = outY * 2.f;
-            }
-            outX = nextX;
-            outY = nextY;
+            // (chosen as an integer: a wave-uniform select between floats is a v_cndmask_b32, between integers an s_cselect_b32)
+            const float start = __int_as_float(level == prm.max_level ? (127 - level) << 23 : 0x40000000);
+            outX *= start;
+            outY *= start;
+            float nextX = outX, nextY = outY;
 
             const int iw = I.w[level], ih = I.h[level], istride = I.stride[level];
             const int jw = J.w[level], jh = J.h[level], jstride = J.stride[level];
@@ -322,7 +320,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             prevX -= halfWin;
             prevY -= halfWin;
             const float fpx = floorf(prevX), fpy = floorf(prevY);
-            const int ipx = uni(vo_f2i(fpx)), ipy = uni(vo_f2i(fpy));
+            const int ipx = uni(cvt_i32_f32(fpx)), ipy = uni(cvt_i32_f32(fpy));
             // x86's cvFloor(NaN) is INT_MIN (cvttss2si), i.e. "left of the window": OpenCV rejects a NaN coordinate here.
             // v_cvt_i32_f32(NaN) is 0, which would ADMIT it -- so NaN is rejected on the float (one
             // v_cmp_u_f32 into a scalar pair).  +-inf and finite values beyond int32 saturate to the rejected side on both.
@@ -430,7 +428,7 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     st = 0;
                 continue;
             }
-            D = 1.f / D;
+            D = rcp_normal_f32(D); // FLT_EPSILON <= D < 2^29 (vo_isa.h)
             // b1, b2 carry the same 2^-20 as the A's; a power of two moves through the rounded products unchanged
             // (A12 * (S * 2^-20) == (A12 * 2^-20) * S bit for bit), so it is folded into the A's once per level
             const float A11s = A11 * FLT_SCALE, A12s = A12 * FLT_SCALE, A22s = A22 * FLT_SCALE;
@@ -462,7 +460,14 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // halfWin is not x), else behind an iteration (out = next + halfWin): 1 = epsilon or count, 2 / 3 = the oscillation test,
             // the delta of the half step back in (dAx, dAy) / (dBx, dBy), 4 = the next cell is not admitted
             int left = 0;
-            float fnx = 0.f, fny = 0.f, frx = 0.f, fry = 0.f;
+            // floors and fractions of the corner: set by cell_admitted / enter_cell before anything reads them, by nothing before
+            // that (like the columns below: no moves per level to zero what the first cell overwrites)
+            float fnx, fny, frx, fry;
+#ifndef VO_HOST_EMUL
+            asm volatile("" : "=v"(fnx), "=v"(fny), "=v"(frx), "=v"(fry));
+#else
+            fnx = fny = frx = fry = 0.f;
+#endif
             // the cell's columns (two window rows per lane) as vertical pixel pairs: eight scalars, not an array -- an array carried
             // round the loop becomes one 8-register tuple, copied at every cell entry -- and set by nothing before the first cell
             uint32_t J0, J1, J2, J3, J4, J5, J6, J7;
@@ -477,8 +482,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             auto cell_admitted = [&]() -> bool {
                 fnx = floorf(nextX);
                 fny = floorf(nextY);
-                inx = uni(vo_f2i(fnx));
-                iny = uni(vo_f2i(fny));
+                inx = uni(cvt_i32_f32(fnx));
+                iny = uni(cvt_i32_f32(fny));
                 return !(VO_BALLOT(__builtin_isunordered(fnx, fny)) != 0ull || inx < -WIN || inx >= jw || iny < -WIN || iny >= jh);
             };
             auto enter_cell = [&]() {

@@ -233,15 +233,17 @@ __device__ __forceinline__ void wave_sum2_exact_f32(int a, int b, float &fa, flo
     fb = __int_as_float(VO_READLANE(__float_as_int(res), 63));
 }
 
-// Three exact sums (the structure tensor A11, A12, A22) in one tree: two half-swaps fold a|b and c|0 into two
-// registers, the 16-lane swap folds those into one (rows: a, c, b, 0; 4-value sums < 2^30), one quad step gives
+// Three exact sums (the structure tensor A11, A12, A22) in one tree: two half-swaps fold a|b and c|(unread) into two
+// registers, the 16-lane swap folds those into one (rows: a, c, b, unread; 4-value sums < 2^30), one quad step gives
 // 8-value sums < 2^31, then the signed-high / unsigned-low halves finish with three DPP steps each and one fma.
 // 22 VALU instead of two wave_sum2 calls (32).
 __device__ __forceinline__ void wave_sum3_exact_f32(int a, int b, int c, float &fa, float &fb, float &fc)
 {
-    int z = 0;
     VO_PERMLANE32_SWAP(a, b);
     int t1 = a + b;
+    // c's partner only feeds the fourth row, whose total nobody reads: the dead `a`, not a zero to be made first (|a| < 2^28
+    // in every lane after the swap too, so the row's sums stay below 2^31 like the other three)
+    int z = a;
     VO_PERMLANE32_SWAP(c, z);
     int t2 = c + z;
     VO_PERMLANE16_SWAP(t1, t2);

@@ -175,6 +175,45 @@ VO_HD uint32_t pk_absdiff_i16(uint32_t a, uint32_t b)
 #endif
 }
 
+// v_cvt_i32_f32 on a VGPR: truncation towards zero, SATURATING, NaN -> 0 (vo_dev.h, vo_f2i, has what x86 does instead).  Named
+// directly for a wave-uniform value that is broadcast next (lk.hip: the floors of the window corner): written as a cast the
+// compiler moves the broadcast in front of the conversion and needs a second one behind it -- v_readfirstlane_b32,
+// v_cvt_i32_f32 from the scalar, v_readfirstlane_b32 -- where convert + one broadcast do.
+VO_HD int32_t cvt_i32_f32(float v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int32_t r;
+    asm("v_cvt_i32_f32 %0, %1" : "=v"(r) : "v"(v));
+    return r;
+#else
+    if (v != v)
+        return 0;
+    if (v >= 2147483648.f)
+        return 2147483647;
+    if (v <= -2147483648.f)
+        return -2147483647 - 1;
+    return (int32_t)v;
+#endif
+}
+
+// 1 / d, correctly rounded, for 2^-23 <= d < 2^29: v_rcp_f32 (1 ulp) and ONE Newton step, r + r * (1 - d * r), both halves fused.
+// The compiler's own division is eleven instructions: it scales operands that need it (denormal or huge d, a denormal quotient:
+// two v_div_scale_f32 and the scale inside v_div_fmas_f32), refines the reciprocal once and the quotient twice, and patches
+// d = 0, +-inf, NaN (v_div_fixup_f32).  In this range nothing is scaled or patched, and on gfx950 the first step already lands on
+// the correctly rounded quotient of EVERY operand: tests/host_check/rcp_check.hip compares this function with the device's
+// 1.0f / d on all 52 * 2^23 floats of the range (tests/test_gpu_lk_level_setup.py; profiles/r09_lk_level_setup.md has the run,
+// which the seven-instruction form -- the compiler's chain without scale and fix-up -- passes too).  Outside the range it is
+// NOT the quotient: d = 0 and +-inf give NaN.
+VO_HD float rcp_normal_f32(float d)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const float r = __builtin_amdgcn_rcpf(d);
+    return __builtin_fmaf(__builtin_fmaf(-d, r, 1.f), r, r);
+#else
+    return 1.f / d;
+#endif
+}
+
 // (acc << 1) | (x < 0): one v_alignbit_b32 shifts a comparison's sign bit into a ring mask (a compare + select + or
 // per bit cost 2.5 x as much issue time, profiles/r02_valu_issue_cost.txt; fast.hip)
 VO_HD uint32_t shift_in_sign(uint32_t acc, int x)
