@@ -28,6 +28,7 @@
 #include "vo_hip.h"           // C ABI of libvo_hip.so
 #include "vo_flow.h"          // ... and its two-image tracker
 #include "vo_corners.h"       // ... and its Shi-Tomasi detector
+#include "vo_corners_mask.h"  // ... with goodFeaturesToTrack's mask argument
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -58,6 +59,11 @@ void featureTracking_hip(cv::Mat img_1, cv::Mat img_2, std::vector<cv::Point2f>&
 // 3, false, 0.04) through vocorn_detect of include/vo_corners.h -- the same corners in the same order.  The reference's frame loop
 // never calls it (it detects with FAST); the pair circularMatching_hip kept stays where it is.
 void featureDetectionGoodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points);
+
+// cv::goodFeaturesToTrack(image, points, maxCorners, qualityLevel, minDistance, mask, 3, false, 0.04) through vocmask_detect of
+// include/vo_corners_mask.h: mask is empty (no mask) or CV_8UC1 of the image's size, non-zero = allowed -- what a KLT front end
+// passes to top its point set up away from the points it still tracks.  maxCorners <= 0: no limit.
+void goodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points, int maxCorners, double qualityLevel, double minDistance, cv::Mat mask);
 
 // OPT-IN, default off: the caller promises that the t0 pair of every circularMatching_hip call IS the t1 pair of the call
 // before it -- the reference's loop hands its frames over exactly so (main.cpp:157-158: imageLeft_t0 = imageLeft_t1 shares

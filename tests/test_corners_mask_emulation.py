@@ -1,0 +1,129 @@
+"""The product's masked Shi-Tomasi kernels (visual_odom_amd/csrc/corners.hip: the masked map kernel, the candidate and select
+kernels under a mask table, the disc kernel) run on the CPU through the coroutine emulator (tests/host_check/corners_mask_emu.cpp) and
+held BIT FOR BIT to the reference of corners_mask_cases.py -- which is first held to corners_ref.c where there is no mask.  Every
+image and every mask sits in a heap block of exactly (h - 1) * stride + w bytes, the mask stride differs from the image stride, and
+the last test runs the same harness as a stand-alone ASan + UBSan program.  CPU only."""
+import numpy as np
+import pytest
+
+import corners_emu as ce
+import corners_mask_cases as cm
+
+SHAPES = [(5, 4), (17, 13), (64, 16), (65, 17), (131, 67), (300, 40)]   # (300, 40): two map workgroups (254 columns each), five tiles
+
+
+def same(got, want, what):
+    pts, n, ncand = got
+    rpts, rn, rcand = want
+    assert (n, ncand) == (rn, rcand), what
+    assert np.array_equal(pts, rpts), "%s: corner list or its order differs" % (what,)
+
+
+def test_reference_without_a_mask_is_corners_ref():
+    """the numpy reference against cr_detect: no mask, and a mask of all 255"""
+    for w, h in [(32, 32), (33, 35), (65, 33), (131, 67), (300, 40)]:
+        for img in (ce.noise(w, h, 1), ce.blobs(w, h, 2)):
+            for md in (0.0, 1.0, 5.0, 10.5):
+                for mc in (0, 17):
+                    want = ce.ref_detect(img, mc, 0.01, md)
+                    same(cm.ref_detect(img, None, mc, 0.01, md), want, (w, h, md, mc))
+                    same(cm.ref_detect(img, np.full((h, w), 255, np.uint8), mc, 0.01, md), want, (w, h, md, mc, "all 255"))
+
+
+def test_case_table_separates_the_wrong_implementations():
+    """what each wrong reading of the mask would give differs from the reference on the inputs the table holds for it"""
+    w, h = 131, 67
+    img = ce.noise(w, h, 21)
+    eig = ce.ref_map(img)
+    for name, gen in cm.NOISE_MASKS:
+        mask = gen(w, h)
+        # "detect unmasked, filter afterwards": other corners at min_distance 5
+        plain = ce.ref_detect(img, 0, 0.01, 5.0)[0]
+        filtered = plain[mask[plain[:, 1].astype(int), plain[:, 0].astype(int)] != 0]
+        assert not np.array_equal(filtered, cm.ref_detect(img, mask, 0, 0.01, 5.0)[0]), name
+        # "mask the map before the dilate": a masked-out neighbour no longer suppresses; more candidates at min_distance 0
+        val = np.where(mask != 0, eig, np.float32(0))
+        pad = np.zeros((h + 2, w + 2), np.float32)
+        pad[1:-1, 1:-1] = val
+        dil = np.max([pad[j:j + h, k:k + w] for j in range(3) for k in range(3)], axis=0)
+        thr = np.float32(float(eig[mask != 0].max()) * 0.01)
+        wrong = int(((val > thr) & (val == dil))[1:-1, 1:-1].sum())
+        assert wrong != cm.ref_detect(img, mask, 0, 0.01, 0.0)[2], name
+    for (sw, sh), count in cm.STRONG_OUTSIDE_CORNERS.items():
+        simg, smask = cm.strong_outside(sw, sh)
+        assert cm.ref_detect(simg, smask, 0, 0.05, 5.0)[1] == count, (sw, sh)
+        # "max over the whole map": the excluded square sets a threshold no allowed pixel passes
+        seig = ce.ref_map(simg)
+        assert not (seig[smask != 0] > np.float32(float(seig.max()) * 0.05)).any(), (sw, sh)
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_masked_corners_bit_for_bit(shape):
+    w, h = shape
+    for name, img, mask, mc, q, md in cm.mask_cases(w, h):
+        want = cm.ref_detect(img, mask, mc, q, md)
+        same(cm.emu_detect([img], [mask], mc, q, md, stride=w + 3, mask_stride=w + 6)[0], want, name)
+        if "all_zero" in name or "border_ring" in name:
+            assert want[1] == 0 and want[2] == 0, name
+        if "all_255" in name or "all_1" in name:   # the bytes of the unmasked kernels
+            plain = ce.emu_detect([img], mc, q, md, stride=w + 3)[0]
+            same(cm.emu_detect([img], [mask], mc, q, md, mask_stride=w + 1)[0], plain[:3], name)
+
+
+def test_batch_of_three_where_the_middle_image_has_no_mask():
+    w, h = 65, 17
+    imgs = [ce.noise(w, h, 7), ce.blobs(w, h, 8), ce.squares(w, h, 9)]
+    masks = [cm.checker(w, h), None, cm.left_half(w, h)]
+    for s, got in enumerate(cm.emu_detect(imgs, masks, 0, 0.01, 5.0, stride=w + 7, mask_stride=w + 2)):
+        same(got, cm.ref_detect(imgs[s], masks[s], 0, 0.01, 5.0), s)
+    same(cm.emu_detect(imgs, masks, 0, 0.01, 5.0)[1], ce.emu_detect(imgs, 0, 0.01, 5.0)[1][:3], "the image without a mask")
+    for s, got in enumerate(cm.emu_detect(imgs, masks, 0, 0.01, 5.0, first=1, n=2, mask_stride=w + 9)):   # a range that starts at one
+        same(got, cm.ref_detect(imgs[1 + s], masks[1 + s], 0, 0.01, 5.0), 1 + s)
+
+
+def test_only_masked_in_candidates_count_against_the_capacity():
+    w, h = 65, 17
+    img, mask = ce.noise(w, h, 9), cm.left_half(w, h)
+    ncand = cm.ref_detect(img, mask, 0, 0.01, 5.0)[2]
+    assert 0 < ncand < ce.ref_detect(img, 0, 0.01, 5.0)[2]
+    same(cm.emu_detect([img], [mask], 0, 0.01, 5.0, lcap=ncand)[0], cm.ref_detect(img, mask, 0, 0.01, 5.0), "exactly full")
+    assert cm.emu_detect([img], [mask], 0, 0.01, 5.0, lcap=ncand - 1)[0][1] == -1   # one too many: the overflow mark
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=["%dx%d" % s for s in SHAPES])
+def test_disc_mask_is_the_definition(shape):
+    w, h = shape
+    for name, kept, r in cm.disc_cases(w, h):
+        want = cm.ref_disc_mask(w, h, kept, r)
+        assert np.array_equal(cm.emu_disc(w, h, kept, r, mask_stride=w + 5), want), name
+        if name == "whole-image":
+            assert not want.any()
+            assert cm.ref_detect(ce.noise(w, h, 3), want)[1] == 0
+    halves = cm.ref_disc_mask(9, 9, [(2.5, 3.5), (-0.5, 6.5)], 0)
+    assert halves[4, 2] == 0 and halves[6, 0] == 0 and int((halves == 0).sum()) == 2   # 2.5 -> 2, 3.5 -> 4, -0.5 -> 0, 6.5 -> 6
+
+
+def test_detect_under_a_disc_mask_keeps_its_distance():
+    w, h = 131, 67
+    img = ce.noise(w, h, 5)
+    kept = ce.ref_detect(img, 40, 0.01, 8.0)[0] + np.float32(0.3)
+    mask = cm.emu_disc(w, h, kept, 5)
+    got = cm.emu_detect([img], [mask], 60, 0.01, 5.0)[0]
+    same(got, cm.ref_detect(img, mask, 60, 0.01, 5.0), "replenish")
+    centres = np.rint(kept)
+    d2 = ((got[0][:, None, :] - centres[None, :, :]) ** 2).sum(axis=2)
+    assert got[1] == 60 and d2.min() > 25
+
+
+def test_standalone_under_asan_and_ubsan(tmp_path):
+    """the same harness as a stand-alone program built with -fsanitize=address,undefined, run as a child: images, masks and lists in
+    exactly sized heap blocks, a list that is exactly full, a partial tile in both directions, discs that hang over every edge"""
+    w, h = 65, 17
+    imgs = [ce.noise(w, h, 9), ce.periodic(w, h), ce.blobs(w, h, 4)]
+    masks = [cm.random_half(w, h), None, cm.checker(w, h)]
+    lcap = max(cm.ref_detect(i, m, 0, 0.01, 6.0)[2] for i, m in zip(imgs, masks))
+    kept = np.array([(-3.0, 8.0), (w + 2.0, 2.0), (30.5, -4.0), (12.5, h + 5.0), (64.4, 16.2), (0.0, 0.0), (np.nan, 1.0), (1e20, 2.0)], np.float32)
+    res, disc = cm.run_standalone(tmp_path, imgs, masks, 0, 0.01, 6.0, cap=lcap, lcap=lcap, kept=kept, radius=7, stride=w + 3, mask_stride=w + 5)
+    for img, mask, got in zip(imgs, masks, res):
+        same(got, cm.ref_detect(img, mask, 0, 0.01, 6.0), "stand-alone")
+    assert np.array_equal(disc, cm.ref_disc_mask(w, h, kept, 7))

@@ -48,6 +48,8 @@ WIN_EXPORTS = ("vowin_track", "vowin_feature_tracking", "vowin_batch_run", "vowi
 FLAG_EXPORTS = ("voflag_track", "voflag_feature_tracking", "voflag_batch_set_guess", "voflag_batch_run")
 # include/vo_corners.h: the Shi-Tomasi detector (goodFeaturesToTrack / cornerMinEigenVal), the fifth header
 CORN_EXPORTS = ("vocorn_default_params", "vocorn_detect", "vocorn_min_eigen_map", "vocorn_batch_run", "vocorn_batch_get")
+# include/vo_corners_mask.h: the same detector with goodFeaturesToTrack's mask argument, the sixth header
+CMASK_EXPORTS = ("vocmask_detect", "vocmask_disc_mask", "vocmask_replenish", "vocmask_batch_set_mask", "vocmask_batch_set_kept", "vocmask_batch_run")
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -165,6 +167,14 @@ def load():
     lib.vocorn_batch_run.argtypes = [vp, C.POINTER(VoCornParams), i, i]
     lib.vocorn_batch_get.argtypes = [vp, i, vp, i, vp]
     for name in CORN_EXPORTS[1:]:
+        getattr(lib, name).restype = C.c_int
+    lib.vocmask_detect.argtypes = [vp, vp, i, i, i, vp, i, C.POINTER(VoCornParams), vp, i, vp]
+    lib.vocmask_disc_mask.argtypes = [vp, i, i, vp, i, i, vp, i]
+    lib.vocmask_replenish.argtypes = [vp, vp, i, i, i, vp, i, i, C.POINTER(VoCornParams), vp, i, vp]
+    lib.vocmask_batch_set_mask.argtypes = [vp, i, vp, i]
+    lib.vocmask_batch_set_kept.argtypes = [vp, i, vp, i, i]
+    lib.vocmask_batch_run.argtypes = [vp, C.POINTER(VoCornParams), i, i]
+    for name in CMASK_EXPORTS:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -557,24 +567,76 @@ class Context:
             h, w = img.shape[:2]
         return img, w, h, stride
 
-    def good_features_to_track(self, img, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None):
-        """featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) = cv::goodFeaturesToTrack(img, max_corners, quality_level,
-        min_distance): corners best first, (n, 2) float32.  cap: rows to fetch (default: all that were found)"""
-        img, w, h, stride = self._corn_image(img)
-        prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+    def _corn_fetch_all(self, call, cap):
+        """call(pts, cap, n) -> rc: a detector entry point with its outputs left open; fetched again when more were found than the
+        first buffer holds (nothing is truncated).  Returns the corners, (n, 2) float32"""
         n = C.c_int(0)
         first = 8192 if cap is None else int(cap)
         pts = np.zeros((max(first, 1), 2), np.float32)
-        self._chk(self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), _p(pts), first, C.byref(n)))
-        if cap is None and n.value > first:   # nothing is truncated: fetch again with room for all
+        self._chk(call(_p(pts), first, C.byref(n)))
+        if cap is None and n.value > first:
             pts = np.zeros((n.value, 2), np.float32)
-            self._chk(self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), _p(pts), n.value, C.byref(n)))
+            self._chk(call(_p(pts), n.value, C.byref(n)))
         return pts[:min(n.value, len(pts) if cap is None else first)].copy()
 
-    def corners_batch_run(self, first_image, n_images, max_corners=5000, quality_level=0.01, min_distance=5.0):
-        """the detector over images first_image .. first_image + n_images - 1 of the batch image table, enqueued"""
+    @staticmethod
+    def _mask(mask, w, h):
+        """a (h, w) uint8 mask as the ABI takes it: (array, byte stride); row-contiguous views go as they are"""
+        m = np.asarray(mask)
+        if m.shape != (h, w):
+            raise ValueError("mask: shape %s, the image is %s" % (m.shape, (h, w)))
+        if m.dtype != np.uint8 or m.strides[1] != 1 or m.strides[0] < w:
+            m = np.ascontiguousarray(m, np.uint8)
+        return m, int(m.strides[0])
+
+    def good_features_to_track(self, img, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None, mask=None):
+        """featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) = cv::goodFeaturesToTrack(img, max_corners, quality_level,
+        min_distance, mask): corners best first, (n, 2) float32.  cap: rows to fetch (default: all that were found).  mask: (h, w)
+        uint8, non-zero = allowed (vocmask_detect, include/vo_corners_mask.h); None = no mask (vocorn_detect)"""
+        img, w, h, stride = self._corn_image(img)
         prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
-        self._chk(self.lib.vocorn_batch_run(self.h, C.byref(prm), int(first_image), int(n_images)))
+        if mask is None:
+            return self._corn_fetch_all(lambda pts, c, n: self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), pts, c, n), cap)
+        m, ms = self._mask(mask, w, h)
+        return self._corn_fetch_all(lambda pts, c, n: self.lib.vocmask_detect(self.h, _pn(img), w, h, stride, _p(m), ms, C.byref(prm), pts, c, n), cap)
+
+    def replenish_corners(self, img, kept, radius, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None):
+        """new corners of img away from the points that are kept: the detector under the disc mask of `kept` [n, 2] with `radius`,
+        built on the device (vocmask_replenish).  max_corners = target - len(kept) is the caller's to pass; 0 means no limit"""
+        img, w, h, stride = self._corn_image(img)
+        k = _f32(kept, (-1, 2))
+        prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        return self._corn_fetch_all(lambda pts, c, n: self.lib.vocmask_replenish(self.h, _pn(img), w, h, stride, _pn(k if len(k) else None), len(k),
+                                                                                  int(radius), C.byref(prm), pts, c, n), cap)
+
+    def corner_disc_mask(self, w, h, kept, radius):
+        """the disc mask of include/vo_corners_mask.h, built on the device: (h, w) uint8, 0 within radius of a kept point, else 255"""
+        k = _f32(kept, (-1, 2))
+        out = np.zeros((int(h), int(w)), np.uint8)
+        self._kept_shape = (0, 0)
+        self._chk(self.lib.vocmask_disc_mask(self.h, int(w), int(h), _pn(k if len(k) else None), len(k), int(radius), _p(out), int(w)))
+        return out
+
+    def corners_batch_set_mask(self, image_idx, mask):
+        """the mask of one image of the batch table for corners_batch_run(masked=True); None removes it"""
+        if mask is None:
+            self._chk(self.lib.vocmask_batch_set_mask(self.h, int(image_idx), None, 0))
+            return
+        m = np.asarray(mask)
+        m, ms = self._mask(m, m.shape[1], m.shape[0])
+        self._chk(self.lib.vocmask_batch_set_mask(self.h, int(image_idx), _p(m), ms))
+
+    def corners_batch_set_kept(self, image_idx, kept, radius):
+        """... built on the device as the disc mask of `kept` [n, 2]"""
+        k = _f32(kept, (-1, 2))
+        self._chk(self.lib.vocmask_batch_set_kept(self.h, int(image_idx), _pn(k if len(k) else None), len(k), int(radius)))
+
+    def corners_batch_run(self, first_image, n_images, max_corners=5000, quality_level=0.01, min_distance=5.0, masked=False):
+        """the detector over images first_image .. first_image + n_images - 1 of the batch image table, enqueued.  masked: under the
+        masks set so far (vocmask_batch_run; an image without one runs unmasked)"""
+        prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        run = self.lib.vocmask_batch_run if masked else self.lib.vocorn_batch_run
+        self._chk(run(self.h, C.byref(prm), int(first_image), int(n_images)))
 
     def corners_batch_get(self, image_idx, cap=8192):
         """(corners [min(n, cap), 2], n) of one image of the latest corners_batch_run"""

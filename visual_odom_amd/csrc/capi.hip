@@ -395,6 +395,11 @@ int vo_batch_configure(vo_ctx *c, int n_images, int w, int h, int n_frames)
     if (c->prm.rectify && (w != c->prm.rect_w || h != c->prm.rect_h))
         return fail(c, VO_ERR_ARG, "image size differs from vo_params.rect_w x rect_h: the context's rectification maps are for that size only");
     VO_HIP_TRY(c, hipSetDevice(c->device));
+    if (c->cmask.any) { // every configuration drops the detector's masks (vo_corners_mask.h)
+        VO_HIP_TRY(c, hipMemsetAsync(c->cmask.d_table, 0, sizeof(uint8_t *) * (size_t)c->max_images, c->sel->stream));
+        std::fill(c->cmask.has.begin(), c->cmask.has.end(), 0);
+        c->cmask.any = false;
+    }
     if (c->seq.on) { // leaving the lock-step sequence loop: its steps may still be in flight
         int rcs = sync_all(c);
         if (rcs != VO_OK)

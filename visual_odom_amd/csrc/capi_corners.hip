@@ -7,7 +7,9 @@
 #include "../../include/vo_corners.h"
 #include "vo_corners_dev.h"
 
-namespace {
+// (namespace vo_capi: capi_corners_mask.hip -- vocmask_*, the same detector under a mask -- shares the argument checks, the image
+// set-up, the buffers and the fetch; they are declared in capi_internal.h)
+namespace vo_capi {
 
 int ensure_corn(vo_ctx *c, int slots)
 {
@@ -67,7 +69,7 @@ CornArgs corn_args(vo_ctx *c, const vocorn_params &p)
     return a;
 }
 
-int check_params(vo_ctx *c, const char *who, const vocorn_params *in, vocorn_params *p)
+int corn_check_params(vo_ctx *c, const char *who, const vocorn_params *in, vocorn_params *p)
 {
     if (in)
         *p = *in;
@@ -82,7 +84,7 @@ int check_params(vo_ctx *c, const char *who, const vocorn_params *in, vocorn_par
 
 // the image of a synchronous call in the image table: uploaded as it is (never rectified), or the kept pair's left image.
 // *image: its index in the table.
-int sync_image(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, int *image)
+int corn_sync_image(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, int *image)
 {
     if (c->seq.on)
         return fail(c, VO_ERR_STATE, (std::string(who) + " inside the sequence loop (vo_seq_*)").c_str());
@@ -94,7 +96,7 @@ int sync_image(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int
 }
 
 // counts of slot s after a run, then its corners: the two waits of a result that may not fit
-int fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *n_out)
+int corn_fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *n_out)
 {
     vo_ctx::Corn &k = c->corn;
     const size_t S = (size_t)k.slots;
@@ -113,7 +115,38 @@ int fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *n_out
     return VO_OK;
 }
 
-} // namespace
+int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked)
+{
+    const std::string name(who);
+    vocorn_params p;
+    int rc = corn_check_params(c, who, params, &p);
+    if (rc != VO_OK)
+        return rc;
+    if (c->seq.on)
+        return fail(c, VO_ERR_STATE, (name + " inside the sequence loop (vo_seq_*)").c_str());
+    if (c->n_images == 0)
+        return fail(c, VO_ERR_STATE, (name + " before vo_batch_configure").c_str());
+    if (first_image < 0 || n_images < 1 || first_image > c->n_images - n_images)
+        return fail(c, VO_ERR_ARG, (name + ": image range outside the configured table").c_str());
+    rc = ensure_corn(c, n_images);
+    if (rc != VO_OK)
+        return rc;
+    VO_HIP_TRY(c, hipSetDevice(c->device));
+    vo_ctx::Corn &k = c->corn;
+    k.run_n = 0;
+    CornArgs a = corn_args(c, p);
+    if (masked && c->cmask.any) { // (no image has a mask: the unmasked kernels)
+        a.masks = c->cmask.d_table + first_image;
+        a.mask_pitch = c->w;
+    }
+    VO_HIP_TRY(c, launch_corners(c->d_imgs, first_image, n_images, c->w, c->h, a, c->sel->stream));
+    k.run_first = first_image;
+    k.run_n = n_images;
+    k.cfg[0] = c->n_images, k.cfg[1] = c->w, k.cfg[2] = c->h;
+    return VO_OK;
+}
+
+} // namespace vo_capi
 
 extern "C" {
 
@@ -133,11 +166,11 @@ int vocorn_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const
     if (!n_out || cap < 0 || (cap > 0 && !pts_out))
         return fail(c, VO_ERR_ARG, "vocorn_detect: null output, or cap < 0");
     vocorn_params p;
-    int rc = check_params(c, "vocorn_detect", params, &p);
+    int rc = corn_check_params(c, "vocorn_detect", params, &p);
     if (rc != VO_OK)
         return rc;
     int image = 0;
-    rc = sync_image(c, "vocorn_detect", img, w, h, stride, &image);
+    rc = corn_sync_image(c, "vocorn_detect", img, w, h, stride, &image);
     if (rc != VO_OK)
         return rc;
     rc = ensure_corn(c, 1);
@@ -145,7 +178,7 @@ int vocorn_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const
         return rc;
     c->corn.run_n = 0; // (slot 0 no longer holds a batch run's image)
     VO_HIP_TRY(c, launch_corners(c->d_imgs, image, 1, w, h, corn_args(c, p), c->sel->stream));
-    return fetch(c, "vocorn_detect", 0, pts_out, cap, n_out);
+    return corn_fetch(c, "vocorn_detect", 0, pts_out, cap, n_out);
 }
 
 int vocorn_min_eigen_map(vo_ctx *c, const uint8_t *img, int w, int h, int stride, float *eig_out, int eig_stride_floats)
@@ -155,7 +188,7 @@ int vocorn_min_eigen_map(vo_ctx *c, const uint8_t *img, int w, int h, int stride
     if (!eig_out || eig_stride_floats < w)
         return fail(c, VO_ERR_ARG, "vocorn_min_eigen_map: null output, or a row stride smaller than the width");
     int image = 0;
-    int rc = sync_image(c, "vocorn_min_eigen_map", img, w, h, stride, &image);
+    int rc = corn_sync_image(c, "vocorn_min_eigen_map", img, w, h, stride, &image);
     if (rc != VO_OK)
         return rc;
     rc = ensure_corn(c, 1);
@@ -175,27 +208,7 @@ int vocorn_batch_run(vo_ctx *c, const vocorn_params *params, int first_image, in
 {
     if (!c)
         return VO_ERR_ARG;
-    vocorn_params p;
-    int rc = check_params(c, "vocorn_batch_run", params, &p);
-    if (rc != VO_OK)
-        return rc;
-    if (c->seq.on)
-        return fail(c, VO_ERR_STATE, "vocorn_batch_run inside the sequence loop (vo_seq_*)");
-    if (c->n_images == 0)
-        return fail(c, VO_ERR_STATE, "vocorn_batch_run before vo_batch_configure");
-    if (first_image < 0 || n_images < 1 || first_image > c->n_images - n_images)
-        return fail(c, VO_ERR_ARG, "vocorn_batch_run: image range outside the configured table");
-    rc = ensure_corn(c, n_images);
-    if (rc != VO_OK)
-        return rc;
-    VO_HIP_TRY(c, hipSetDevice(c->device));
-    vo_ctx::Corn &k = c->corn;
-    k.run_n = 0;
-    VO_HIP_TRY(c, launch_corners(c->d_imgs, first_image, n_images, c->w, c->h, corn_args(c, p), c->sel->stream));
-    k.run_first = first_image;
-    k.run_n = n_images;
-    k.cfg[0] = c->n_images, k.cfg[1] = c->w, k.cfg[2] = c->h;
-    return VO_OK;
+    return corn_batch_run(c, "vocorn_batch_run", params, first_image, n_images, /*masked*/ false);
 }
 
 int vocorn_batch_get(vo_ctx *c, int image_idx, float *pts_out, int cap, int *n_out)
@@ -212,7 +225,7 @@ int vocorn_batch_get(vo_ctx *c, int image_idx, float *pts_out, int cap, int *n_o
     if (image_idx < k.run_first || image_idx >= k.run_first + k.run_n)
         return fail(c, VO_ERR_ARG, "vocorn_batch_get: image outside the range of the latest vocorn_batch_run");
     VO_HIP_TRY(c, hipSetDevice(c->device));
-    return fetch(c, "vocorn_batch_get", image_idx - k.run_first, pts_out, cap, n_out);
+    return corn_fetch(c, "vocorn_batch_get", image_idx - k.run_first, pts_out, cap, n_out);
 }
 
 } // extern "C"

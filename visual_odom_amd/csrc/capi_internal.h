@@ -23,6 +23,10 @@
 #include <vector>
 
 using namespace vo;
+namespace vo {
+struct CornArgs; // vo_corners_dev.h
+}
+struct vocorn_params; // include/vo_corners.h
 
 #define VO_SEQ_INFLIGHT 8 // steps the host may run ahead of the device
 // timing events of one run: [0..3] tracking stream (3 stages), [4..7] post streams (3 stages), [8] start of DETECT on
@@ -343,6 +347,16 @@ struct vo_ctx {
         int run_first = 0, run_n = 0; // image range of the latest vocorn_batch_run (run_n = 0: none since the table was configured)
         int cfg[3] = {0, 0, 0};      // n_images, w, h of the table it ran on
     } corn;
+    // ---- the detector's masks (vocmask_*, include/vo_corners_mask.h, capi_corners_mask.hip): allocated by the first such call ----
+    struct CornMask {
+        bool ready = false;
+        // (entry max_images of each: the synchronous calls', so that they never touch what the batch calls set)
+        uint8_t *d_masks = nullptr;        // [max_images + 1][max_w * max_h] the mask of image i, rows tight (w bytes)
+        float2 *d_kept = nullptr;          // [max_images + 1][cap] the kept points of image i on their way to the disc kernel
+        const uint8_t **d_table = nullptr; // [max_images + 1] what a run reads: the mask of image i, or null for an image without one
+        std::vector<uint8_t> has;          // [max_images] host mirror of d_table: the image has a mask
+        bool any = false;                  // some image has one (vo_batch_configure drops them all)
+    } cmask;
     // ---- lock-step sequence loop (vo_seq_*): S sequences x 1 frame per step, state carried on the device ----
     struct Seq {
         bool on = false;
@@ -537,6 +551,13 @@ int seq_push(vo_ctx *c, int seq, const void *left, const void *right, int stride
 int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_t *l1, const uint8_t *r1, int w, int h, int stride, const float *pts, int n, bool defer_t1 = false);
 int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride, bool plain = false);
 int flush_deferred(vo_ctx *c, hipStream_t on);
+// the Shi-Tomasi detector's host side (capi_corners.hip), shared with its masked calls (capi_corners_mask.hip)
+int ensure_corn(vo_ctx *c, int slots);
+vo::CornArgs corn_args(vo_ctx *c, const vocorn_params &p);
+int corn_check_params(vo_ctx *c, const char *who, const vocorn_params *in, vocorn_params *p);
+int corn_sync_image(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, int *image);
+int corn_fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *n_out);
+int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked);
 struct DeferGuard { // the deferred t1 pair never outlives the call whose host pointers it holds
     vo_ctx *c;
     ~DeferGuard() { c->defer.n = 0; }

@@ -7,6 +7,9 @@
 //   corn_cand_kernel     one workgroup per 64 x 16 tile of the map: threshold(TOZERO) at (float)(max * qualityLevel), dilate 3 x 3,
 //                        candidates `val != 0 && val == dilated` appended to the image's list as (ordered quality bits, y w + x)
 //   corn_select_kernel   one workgroup per image: sort, minDistance suppression, the corners in order
+// and goodFeaturesToTrack's mask argument (include/vo_corners_mask.h): the map kernel's masked twin takes the maximum over the allowed
+// pixels, the candidate kernel drops the masked-out local maxima, and
+//   corn_disc_kernel     one wavefront per kept point: zeros over its disc in a mask that holds 0xFF
 //
 // Why a thread per column.  boxFilter sums the f32 products in f64, and its column pass (ColumnSum<double, float>) is a RUNNING sum
 // down the whole column: SUM += row(y + 1); out = SUM; SUM -= row(y - 1).  The f64 operations are not exact in general -- a dy of
@@ -36,9 +39,10 @@ constexpr int CORN_SELECT_THREADS = 1024;
 
 __device__ __forceinline__ int corn_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-// map: [n][map_stride] floats, slot s = image first + s, rows tight (w floats).  max_key: [n] or null.
-__global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
-                                                        unsigned *__restrict__ max_key)
+// The body of the two map kernels.  mask: the slot's mask (rows mask_pitch bytes apart) or null.  minMaxLoc(eig, 0, &maxVal, 0, 0,
+// mask) takes the maximum over the allowed pixels only (none: max_key stays 0); the map itself is the same with and without one.
+__device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+                                              unsigned *__restrict__ max_key, const uint8_t *__restrict__ mask, int mask_pitch)
 {
     __shared__ float s_cov[3][CM_T];
     __shared__ unsigned s_max;
@@ -59,6 +63,12 @@ __global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restri
     unsigned best = 0;
     for (int yy = -1; yy <= h; yy++) { // cov row yy enters the column sum; the map row yy - 1 leaves it
         const int ry = reflect101(yy, h);
+        // the mask byte of the map row this iteration completes: one coalesced byte per pixel beside the 4-byte store, fetched with
+        // the iteration's pixels.  It is a fourth row stream and, unlike two of the three pixel rows, never a cache hit: the masked
+        // kernel takes 0.67 ms where the plain one takes 0.53 (256 images of 1241 x 376)
+        uint8_t allowed = 1;
+        if (mask && owner && yy >= 1)
+            allowed = mask[(size_t)(yy - 1) * mask_pitch + x];
         float rd[3], rs[3];
         for (int j = 0; j < 3; j++) { // RowFilter<uchar, float>: s = k0 p(x-1); s += k1 p(x); s += k2 p(x+1)
             const VO_GLOBAL uint8_t *row = src + (ptrdiff_t)reflect101(ry + j - 1, h) * stride;
@@ -105,7 +115,8 @@ __global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restri
         const float e = (ea + ec) - sqrtf((ea - ec) * (ea - ec) + eb * eb);
         map[(size_t)(yy - 1) * w + x] = e;
         const unsigned key = corn_ord(e);
-        best = key > best ? key : best;
+        if (allowed)
+            best = key > best ? key : best;
     }
     if (!max_key) // (uniform)
         return;
@@ -114,6 +125,20 @@ __global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restri
     __syncthreads();
     if (tid == 0 && s_max)
         atomicMax(&max_key[slot], s_max);
+}
+
+// map: [n][map_stride] floats, slot s = image first + s, rows tight (w floats).  max_key: [n] or null.
+__global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+                                                        unsigned *__restrict__ max_key)
+{
+    corn_map_body(imgs, first, maps, map_stride, max_key, nullptr, 0);
+}
+
+// ... under masks [n] (CornArgs::masks: a slot's entry may be null)
+__global__ __launch_bounds__(CM_T) void corn_map_masked_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+                                                               unsigned *__restrict__ max_key, const uint8_t *const *__restrict__ masks, int mask_pitch)
+{
+    corn_map_body(imgs, first, maps, map_stride, max_key, masks[blockIdx.y], mask_pitch);
 }
 
 __global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_x, CornArgs a)
@@ -130,8 +155,10 @@ __global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_
     for (int i = tid; i < CV_H * CV_W; i += 256)
         s_val[i] = map[(size_t)corn_clamp(y0 - 1 + i / CV_W, 0, h - 1) * w + corn_clamp(x0 - 1 + i % CV_W, 0, w - 1)];
     __syncthreads();
-    // minMaxLoc's maxVal is a double; threshold() casts the product to the map's type
-    const float thresh = (float)((double)corn_unord(a.max_key[slot]) * a.quality);
+    const uint8_t *__restrict__ mask = a.masks ? a.masks[slot] : nullptr; // (uniform)
+    // minMaxLoc's maxVal is a double (0 under a mask that allows no pixel); threshold() casts the product to the map's type
+    const unsigned mk = a.max_key[slot];
+    const float thresh = (float)((double)(mk ? corn_unord(mk) : 0.f) * a.quality);
     for (int i = tid; i < CT_W * CT_H; i += 256) {
         const int lx = i % CT_W, ly = i / CT_W, x = x0 + lx, y = y0 + ly;
         if (x < 1 || x > w - 2 || y < 1 || y > h - 2)
@@ -146,8 +173,10 @@ __global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_
                 const float t = q[j * CV_W + k] > thresh ? q[j * CV_W + k] : 0.f;
                 m = t > m ? t : m;
             }
-        if (v == m)
-            s_list[atomicAdd(&s_cnt, 1)] = ((unsigned long long)corn_ord(v) << 32) | (unsigned)(y * w + x);
+        // the mask is read for the pixels that passed only (a few thousand per image), before the append: a masked-out pixel
+        // never enters tmpCorners, but it has taken part in the threshold and the dilate above like any other
+        if (v == m && (!mask || mask[(size_t)y * a.mask_pitch + x]))
+            s_list[atomicAdd(&s_cnt, 1)] =((unsigned long long)corn_ord(v) << 32) | (unsigned)(y * w + x);
     }
     __syncthreads();
     if (tid == 0)
@@ -321,6 +350,34 @@ __global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornAr
     }
 }
 
+// The disc mask of include/vo_corners_mask.h over a mask that holds 0xFF: one wavefront per kept point writes zeros over the part of
+// its disc that lies inside the image.  Centre (cvRound(x), cvRound(y)), round-half-to-even; a point with a NaN, infinite or
+// |coordinate| >= 2^30 is skipped; pixel (px, py) is cleared iff (px - cx)^2 + (py - cy)^2 <= radius^2 in integers (inside the clipped
+// box both offsets are at most radius <= 256, and cx +- radius stays far inside int).  Every writer stores the same byte, so
+// overlapping discs need no atomics and the result does not depend on order.
+constexpr int CD_T = 256, CD_WAVES = CD_T / 64;
+__global__ __launch_bounds__(CD_T) void corn_disc_kernel(const float2 *__restrict__ kept, int n_kept, int radius, uint8_t *__restrict__ mask, int w, int h,
+                                                         int pitch)
+{
+    const int lane = (int)threadIdx.x % 64, p = (int)blockIdx.x * CD_WAVES + (int)threadIdx.x / 64;
+    if (p >= n_kept) // (uniform per wavefront)
+        return;
+    const float2 k = kept[p];
+    if (!(fabsf(k.x) < 1073741824.f) || !(fabsf(k.y) < 1073741824.f)) // (NaN fails the comparison too)
+        return;
+    const int cx = __float2int_rn(k.x), cy = __float2int_rn(k.y);
+    const int x0 = cx - radius > 0 ? cx - radius : 0, x1 = cx + radius < w - 1 ? cx + radius : w - 1;
+    const int y0 = cy - radius > 0 ? cy - radius : 0, y1 = cy + radius < h - 1 ? cy + radius : h - 1;
+    if (x0 > x1 || y0 > y1) // the disc misses the image
+        return;
+    const int bw = x1 - x0 + 1, cells = bw * (y1 - y0 + 1), r2 = radius * radius;
+    for (int i = lane; i < cells; i += 64) {
+        const int px = x0 + i % bw, py = y0 + i / bw, dx = px - cx, dy = py - cy;
+        if (dx * dx + dy * dy <= r2)
+            mask[(size_t)py * pitch + px] = 0;
+    }
+}
+
 #ifndef VO_HOST_EMUL
 hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream)
 {
@@ -332,8 +389,12 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
     if (e != hipSuccess)
         return e;
     const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
-    hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key);
-    hipLaunchKernelGGL(corn_cand_kernel, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a);
+    if (a.masks)
+        hipLaunchKernelGGL(corn_map_masked_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key,
+                           a.masks, a.mask_pitch);
+    else
+        hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key);
+    hipLaunchKernelGGL(corn_cand_kernel,dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a);
     hipLaunchKernelGGL(corn_select_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h);
     return hipGetLastError();
 }
@@ -341,6 +402,15 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
 void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream)
 {
     hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, 1), dim3(CM_T), 0, stream, d_imgs, image, d_map, (size_t)0, (unsigned *)nullptr);
+}
+
+hipError_t launch_corner_disc_mask(const float2 *d_kept, int n_kept, int radius, uint8_t *d_mask, int w, int h, hipStream_t stream)
+{
+    hipError_t e = hipMemsetAsync(d_mask, 0xFF, (size_t)w * h, stream);
+    if (e != hipSuccess || n_kept <= 0)
+        return e;
+    hipLaunchKernelGGL(corn_disc_kernel, dim3((n_kept + CD_WAVES - 1) / CD_WAVES), dim3(CD_T), 0, stream, d_kept, n_kept, radius, d_mask, w, h, w);
+    return hipGetLastError();
 }
 #endif
 

@@ -24,6 +24,10 @@ struct CornArgs {
     int max_corners;           // <= 0: no limit
     int cell;                  // cvRound(minDistance), >= 1
     int lim;                   // two candidates of neighbouring cells conflict iff dx^2 + dy^2 < lim (= ceil(minDistance^2)); <= 1: none can
+    // goodFeaturesToTrack's mask argument (include/vo_corners_mask.h).  As initialised here: no mask, and the run is what it was.
+    const uint8_t *const *masks = nullptr; // [n] the slot's mask (h rows of w bytes, mask_pitch bytes apart; non-zero: allowed), or
+                                           // null for a slot without one.  A null table: no slot has one
+    int mask_pitch = 0;
 };
 
 // A float's bits as an unsigned that orders like the float (negative values included): the map maximum by atomicMax, the sort key
@@ -50,10 +54,13 @@ inline int corn_pow2(int n)
 
 #ifndef VO_HOST_EMUL
 // the whole detector over n slots: map + maximum, candidates, sort + suppression + output (three launches on `stream`; max_key and
-// ncand are zeroed first).  Returns the first HIP error of the memsets and launches.
+// ncand are zeroed first).  Returns the first HIP error of the memsets and launches.  With a.masks the map pass is the masked twin.
 hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream);
 // cv::cornerMinEigenVal of image `image` into map [h][w] (tight)
 void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream);
+// the disc mask of include/vo_corners_mask.h into mask [h][w] (tight): 0xFF everywhere, then 0 within `radius` of every kept point
+// (a memset and, with n_kept > 0, one launch on `stream`)
+hipError_t launch_corner_disc_mask(const float2 *d_kept, int n_kept, int radius, uint8_t *d_mask, int w, int h, hipStream_t stream);
 #endif
 
 } // namespace vo
