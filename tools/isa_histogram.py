@@ -2,6 +2,8 @@
 
     hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only lk.hip -o lk.s
     python tools/isa_histogram.py lk.s lk_circular_kernel [--cost profiles/r02_valu_issue_cost.txt] [--blocks a,b,c]
+    python tools/isa_histogram.py lk.s lk_circular_queue_kernel ...     # the same body behind the ticket draw: its blocks carry
+                                                                        # other numbers (.LBB1_n), their VALU counts are the same
 
 For every basic block of the kernel (labels `.LBB0_n:` and the fall-through markers `; %bb.n:`) it prints the number of
 VALU / SALU / LDS / VMEM instructions and the block's VALU issue cost = sum over opcodes of count x measured cost

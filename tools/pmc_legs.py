@@ -21,11 +21,16 @@ ISSUE_FLOOR = 3.65  # the same mix with every opcode at the floor of its class (
                     # 3.68, cell entry 3.65, level set-up 3.77 -- the smallest of the three): no issue schedule beats it, a BOUND
 
 
-def counters(d, kernel="lk_circular_kernel"):
+# the fused LK launch of a leg: the static kernel, or -- batches of 16 frames and more -- the one that draws its work items
+LK_KERNELS = ("lk_circular_kernel", "lk_circular_queue_kernel")
+
+
+def counters(d, kernel=LK_KERNELS):
     acc = {}
+    names = (kernel,) if isinstance(kernel, str) else tuple(kernel)
     for f in glob.glob(os.path.join(d, "**", "*_counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
-            if kernel in r["Kernel_Name"]:
+            if any(k in r["Kernel_Name"] for k in names):
                 acc.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
     return {k: sum(v) / len(v) for k, v in acc.items()}, {k: len(v) for k, v in acc.items()}
 
@@ -89,8 +94,8 @@ def main(src):
                                "issue_floor_cycles_per_valu_instruction": ISSUE_FLOOR,
                                "dispatches_averaged": nsq["SQ_INSTS_VALU"],
                                "source": "%s: rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU "
-                                         "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES (its own run of `%s`), means over the lk_circular_kernel "
-                                         "dispatches; the bound = the hot loop's opcode mix x measured issue costs "
+                                         "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES (its own run of `%s`), means over the lk_circular_kernel / "
+                                         "lk_circular_queue_kernel dispatches; the bound = the hot loop's opcode mix x measured issue costs "
                                          "(profiles/r02_lk_issue_bound.md)" % (tag, cmd)})
     for name, legs in (("lk_traffic.json", traffic_legs), ("lk_issue.json", issue_legs)):
         path = os.path.join(ROOT, "profiles", name)

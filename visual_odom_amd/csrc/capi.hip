@@ -299,6 +299,7 @@ vo_ctx *vo_create(int device, int max_w, int max_h, int max_pts, int max_frames)
     ok = ok && o.pinned(&c->h_feat_stage, features_stage_bytes(c->fcap), hipHostMallocMapped, &c->d_feat_stage);
     ok = ok && o.device(&c->d_ages, B * cap, /*zero*/ true);
     ok = ok && o.device(&c->d_overflow, B, /*zero*/ true);
+    ok = ok && o.device(&c->lk_queues.d_next, (size_t)LKQ_WORDS, /*zero*/ true);
     for (int k = 0; k < 2; k++) {
         ok = ok && o.device(&c->d_pts_det[k], B * cap);
         ok = ok && o.device(&c->d_npts_det[k], B, /*zero*/ true);

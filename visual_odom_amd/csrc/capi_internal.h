@@ -316,6 +316,7 @@ struct vo_ctx {
     bool have_P = false;
     std::vector<int> h_npts;
     int *d_overflow = nullptr;     // [B] VO_STAGE_DETECT capacity flags (bit 0: feature list, bit 1: bucketed set)
+    LkQueues lk_queues;            // the ticket counters of lk_circular_queue_kernel (two sets, zero at allocation) + the launch parity
     Quad *quads_cur = nullptr;     // the quad table the launches read: d_quads, or one phase of seq.d_quads
     std::vector<Quad> h_quads;     // host copy of d_quads (stale-pyramid check)
     std::vector<uint8_t> img_stale; // image re-uploaded since its pyramid was last built

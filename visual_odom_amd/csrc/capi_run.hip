@@ -187,7 +187,7 @@ int run_lk(vo_ctx *c, const Run &R)
                            c->d_status2[wset], lp, 1, 4, trk);
         } else
             launch_lk_circular(c->d_imgs, c->quads_cur, cur_pts(c), cur_npts(c), cap, c->max_pts_set, B, c->d_trk2[wset],
-                               c->d_status2[wset], lp, trk);
+                               c->d_status2[wset], lp, trk, &c->lk_queues);
         c->trk_last = wset;
         c->trk_next = wset ^ 1;
         if (sq.on) { // the ring slots holding this step's pairs may be overwritten once this LK has finished

@@ -347,12 +347,12 @@ static void launch_lk_circular_pair(const PyrImage *d_imgs, const Quad *d_quads,
 // VO_LK_PAIR=1: the pair kernel.  Read per launch (tools/dev_variants_check.py flips it between two contexts of one process).
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
                         int cap, int max_pts, int n_frames, float2 *d_trk, uint8_t *d_status,
-                        const LkParams &prm, hipStream_t stream)
+                        const LkParams &prm, hipStream_t stream, LkQueues *queues)
 {
     if (dev_knob("VO_LK_PAIR", 0) == 1)
         launch_lk_circular_pair(d_imgs, d_quads, d_pts, d_npts, cap, max_pts, n_frames, d_trk, d_status, prm, stream);
     else
-        launch_lk_circular_product(d_imgs, d_quads, d_pts, d_npts, cap, max_pts, n_frames, d_trk, d_status, prm, stream);
+        launch_lk_circular_product(d_imgs, d_quads, d_pts, d_npts, cap, max_pts, n_frames, d_trk, d_status, prm, stream, queues);
 }
 #endif // VO_HOST_EMUL
 

@@ -29,6 +29,8 @@
 // Grid: blocks are numbered so that (dispatcher: block b -> XCD b % 8) all features of one frame
 // run on ONE XCD, i.e. the frame's four pyramids are pulled into one L2 only, eight frames at a time.
 // Batches of fewer than 8 frames split each frame's feature list into contiguous parts over 8/fpg XCDs.
+// lk_circular_queue_kernel (round 10, batches of 16 frames and more): the same numbering handed out as tickets of per-XCD queues,
+// so that an XCD that runs dry takes work from the others (vo_lkqueue.h, profiles/r10_lk_xcd_queue.md).
 // lk_hops_kernel (round 6): the same body for hops [begin, end) of the chain -- the synchronous drop-in calls on the kept pair
 // launch hop 0 while the new pair is still crossing PCIe (capi_run.hip); lk_circular_kernel is what every other launch runs.
 // lk_flow_kernel: the same body for ONE hop between an arbitrary (prev, next) pair of the image table, with the err output of
@@ -39,6 +41,7 @@
 // W of 5 .. 21: the search starts at the caller's guess, err is the min eigenvalue of the level-0 structure tensor.
 #include "vo_kernels.h"
 #include "vo_lkmath.h"
+#include "vo_lkqueue.h"
 
 #include <float.h>
 #include <type_traits>
@@ -240,13 +243,13 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                                                  float2 *__restrict__ trk,     // [B][4][cap]
                                                  uint8_t *__restrict__ status, // [B][4][cap]
                                                  const LkParams prm, int hop_begin, int hop_end, float *__restrict__ err = nullptr,
-                                                 int flags = 0)
+                                                 int flags = 0, int bid = blockIdx.x /* the work item: see below */)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_jt[LK_JT_H * LK_JT_W];
 
     // XCD-aware block numbering: block id b runs on XCD b % 8 (observed dispatcher behaviour, used
-    // for L2 affinity only): XCD x works on frames x, x + 8, x + 16, ... one frame after another
-    const int bid = blockIdx.x;
+    // for L2 affinity only): XCD x works on frames x, x + 8, x + 16, ... one frame after another.  `bid` is the workgroup's own
+    // number in every kernel but lk_circular_queue_kernel, which draws it (vo_lkqueue.h).
     const int xcd = bid & 7, slot = bid >> 3;
     const int grp = slot / ppp, fi = slot - grp * ppp;
     const int frame = grp * fpg + (xcd & (fpg - 1));
@@ -680,6 +683,63 @@ __global__ VO_LK_ATTRS void lk_circular_kernel(const PyrImage *__restrict__ imgs
     lk_circular_body<false, false>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, 0, 4);
 }
 
+// The same chain with the work item drawn from the per-XCD ticket queues of vo_lkqueue.h (batches of LKQ_MIN_FRAMES frames and
+// more): lane 0 takes a ticket of its XCD's queue -- relaxed, agent scope: the queues are shared by the eight XCDs, so the
+// counter must not live in one XCD's L2 --, the wave gets it through a scalar, and a wave that finds its queue dry takes from the
+// next one; the wave that finds all eight dry marks its XCD's counter, and the XCD's later waves end at their first draw.
+// `next`: this launch's eight counters, LKQ_STRIDE words apart; `other`: the set of the launch before, which nothing reads any
+// more (launches on the tracking stream do not overlap) and block 0 zeroes for the launch after this one.  Results are those of
+// lk_circular_kernel bit for bit: only which workgroup computes a feature changes.
+__device__ __forceinline__ unsigned lk_queue_draw(unsigned *next, int q)
+{
+#ifdef VO_HOST_EMUL // (lanes run one at a time between yields: the plain read-modify-write is atomic)
+    unsigned t = 0;
+    if (threadIdx.x == 0)
+        t = next[LKQ_STRIDE * q]++;
+#else
+    unsigned t = 0;
+    if (threadIdx.x == 0)
+        t = __hip_atomic_fetch_add(&next[LKQ_STRIDE * q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+    return (unsigned)uni((int)t);
+}
+// lk_queue_take's mark, in the shape of the draw: lane 0's atomic, its result through a scalar and dropped.  Nothing needs the
+// result; written as an atomic nobody waits for, the allocator ends at 72 registers and 23 spilled ones, where in
+// this shape the kernel keeps lk_circular_kernel's 64 (profiles/r10_lk_xcd_queue.md, section 4).  One workgroup per XCD and
+// launch comes here, or the few that find the queues dry at the same time.
+__device__ __forceinline__ void lk_queue_mark(unsigned *next, int q)
+{
+    unsigned t = 0;
+#ifdef VO_HOST_EMUL
+    if (threadIdx.x == 0)
+        next[LKQ_STRIDE * q] |= LKQ_ALL_DRY;
+    (void)uni((int)t);
+#else
+    if (threadIdx.x == 0)
+        t = __hip_atomic_fetch_or(&next[LKQ_STRIDE * q], LKQ_ALL_DRY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("" ::"s"(uni((int)t)));
+#endif
+}
+__global__ VO_LK_ATTRS void lk_circular_queue_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads,
+                                                     const float2 *__restrict__ pts_in, const int *__restrict__ n_pts, int cap,
+                                                     int n_frames, int fpg /* 8 */, int ppp, float2 *__restrict__ trk,
+                                                     uint8_t *__restrict__ status, LkParams prm, int items /* per queue */,
+                                                     unsigned *next, unsigned *other)
+{
+    if (blockIdx.x == 0 && threadIdx.x < (unsigned)LKQ_QUEUES) {
+#ifdef VO_HOST_EMUL
+        other[LKQ_STRIDE * threadIdx.x] = 0u;
+#else
+        __hip_atomic_store(&other[LKQ_STRIDE * threadIdx.x], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+    }
+    const int bid = lk_queue_take((int)(blockIdx.x & 7), items, [&](int q) { return lk_queue_draw(next, q); },
+                                  [&](int q) { lk_queue_mark(next, q); });
+    if (bid < 0)
+        return;
+    lk_circular_body<false, false>(imgs, quads, pts_in, n_pts, cap, n_frames, fpg, ppp, trk, status, prm, 0, 4, nullptr, 0, bid);
+}
+
 // Hops hop_begin .. hop_end - 1 only: the synchronous drop-in calls (capi_run.hip) launch hop 0 -- which reads the t0 pair
 // only -- while the t1 pair is still crossing PCIe and its pyramids are being built on another stream, then hops 1 .. 3.
 __global__ VO_LK_ATTRS void lk_hops_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads,
@@ -789,10 +849,22 @@ void launch_lk_flow(int win, int flags, const PyrImage *d_imgs, const Quad *d_pa
 
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
                         int cap, int max_pts, int n_frames, float2 *d_trk, uint8_t *d_status,
-                        const LkParams &prm, hipStream_t stream)
+                        const LkParams &prm, hipStream_t stream, LkQueues *queues)
 {
     if (max_pts <= 0 || n_frames <= 0)
         return;
+    // batches of 16 frames and more: the work items from the per-XCD queues (a context without counters, or a launch whose
+    // ticket range would not fit an int, keeps the static split)
+    if (queues != nullptr && queues->d_next != nullptr && n_frames >= LKQ_MIN_FRAMES &&
+        (long long)((n_frames + 7) / 8) * max_pts < (1ll << 26)) {
+        const LkQueueGrid g = lk_queue_grid(n_frames, max_pts);
+        const int set = queues->launches++ & 1;
+        unsigned *const cur = queues->d_next + set * (LKQ_QUEUES * LKQ_STRIDE);
+        unsigned *const oth = queues->d_next + (set ^ 1) * (LKQ_QUEUES * LKQ_STRIDE);
+        hipLaunchKernelGGL(lk_circular_queue_kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap,
+                           n_frames, g.fpg, g.ppp, d_trk, d_status, prm, g.items, cur, oth);
+        return;
+    }
     const LkGrid g = lk_grid(n_frames, max_pts);
     hipLaunchKernelGGL(lk_circular_kernel, dim3((unsigned)g.blocks), dim3(64), 0, stream, d_imgs, d_quads, d_pts, d_npts, cap,
                        n_frames, g.fpg, g.ppp, d_trk, d_status, prm);

@@ -4,6 +4,7 @@
 
 #include "../../include/vo_hip.h" // VO_FMT_*, VO_SEQ_ROW, VO_SEQ_F_*
 #include "vo_dev.h"
+#include "vo_lkqueue.h"
 
 namespace vo {
 
@@ -145,9 +146,16 @@ void launch_pyramid_fused(const PyrImage *d_imgs, int n_images, int n_levels, co
 // pyramid.hip: a staged host image over PCIe by a kernel (+ optionally n_pts float2 and their count from pinned memory)
 void launch_pull_image(const void *src_pinned_dev, void *dst, size_t bytes, hipStream_t stream, const void *pts_pinned_dev = nullptr,
                        void *pts_dst = nullptr, int n_pts = 0, int *count_dst = nullptr);
+// queues (optional): the context's ticket counters for lk_circular_queue_kernel (vo_lkqueue.h: LKQ_WORDS words, zero when
+// allocated) and the number of queue launches so far -- launch k draws from set k & 1 and zeroes the other.  Batches of
+// LKQ_MIN_FRAMES frames and more go through the queues; without them, and below that, lk_circular_kernel's static split.
+struct LkQueues {
+    unsigned *d_next = nullptr;
+    unsigned launches = 0;
+};
 void launch_lk_circular(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts,
                         int cap, int max_pts, int n_frames, float2 *d_trk, uint8_t *d_status,
-                        const LkParams &prm, hipStream_t stream);
+                        const LkParams &prm, hipStream_t stream, LkQueues *queues = nullptr);
 // hops hop_begin .. hop_end - 1 of the chain (lk_hops_kernel; [0, 1) + [1, 4) == launch_lk_circular bit for bit)
 void launch_lk_hops(const PyrImage *d_imgs, const Quad *d_quads, const float2 *d_pts, const int *d_npts, int cap, int max_pts,
                     int n_frames, float2 *d_trk, uint8_t *d_status, const LkParams &prm, int hop_begin, int hop_end,
