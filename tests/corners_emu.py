@@ -6,53 +6,30 @@ The libraries loaded into python are built WITHOUT sanitizer flags whatever the 
 harness as a STAND-ALONE program with its own main(): every image and list in an exactly sized heap block, built with
 -fsanitize=address,undefined (runtimes linked statically) and run as a child.  Nothing instrumented is loaded into python."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT, vp
-
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-REF_SRC = os.path.join(SRC_DIR, "corners_ref.c")
-EMU_SRC = os.path.join(SRC_DIR, "corners_emu.cpp")
-EMU_DEPS = [EMU_SRC, os.path.join(SRC_DIR, "hip_emu.h")] + [os.path.join(CSRC, f) for f in ("corners.hip", "vo_corners_dev.h", "vo_dev.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-_ref = _emu = None
-
-
-def _stale(target, deps):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
+import emu_build
+from conftest import vp
 
 
 def load_ref():
-    """libcorners_ref.so (plain C, -ffp-contract=off), built when the source is newer and loaded once per session"""
-    global _ref
-    if _ref is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "libcorners_ref.so")
-        if _stale(so, [REF_SRC]):
-            subprocess.check_call(["gcc", "-std=c99", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-o", so, REF_SRC, "-lm"])
-        _ref = C.CDLL(so)
-        _ref.cr_min_eigen_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        _ref.cr_cell.argtypes = [C.c_double]
-        _ref.cr_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    return _ref
+    """libcorners_ref.so (plain C, -ffp-contract=off), built when stale and loaded once per session"""
+    lib = emu_build.shared("corners_ref", cc="gcc", flags=["-std=c99", "-ffp-contract=off", "-Wall"], libs=["-lm"])
+    lib.cr_min_eigen_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
+    lib.cr_cell.argtypes = [C.c_double]
+    lib.cr_detect.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    return lib
 
 
 def load_emu():
-    global _emu
-    if _emu is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "libcorners_emu.so")
-        if _stale(so, EMU_DEPS):
-            subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, EMU_SRC])
-        _emu = C.CDLL(so)
-        _emu.ce_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        _emu.ce_detect.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    return _emu
+    """libcorners_emu.so: the detector with and without a mask (ce_map, ce_detect; cme_detect, cme_disc for corners_mask_cases.py)"""
+    lib = emu_build.shared("corners_emu")
+    lib.ce_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    lib.ce_detect.argtypes = [C.c_void_p] + [C.c_int] * 7 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.cme_detect.argtypes = [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.cme_disc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    return lib
 
 
 def strided(img, stride):
@@ -111,13 +88,7 @@ def emu_detect(imgs, max_corners=0, quality_level=0.01, min_distance=5.0, cap=No
 def run_standalone(tmp_path, imgs, max_corners, quality_level, min_distance, cap, lcap, stride=None):
     """the images through the stand-alone ASan + UBSan program, run as a child: no report, exit status 0.  Returns (map of image 0,
     [(corners, n, candidates, rounds)])"""
-    out_dir = os.path.join(OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "corners_emu_main")
-    if _stale(exe, EMU_DEPS):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DCORNERS_EMU_MAIN", "-o", exe, EMU_SRC])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = emu_build.sanitized_program("corners_emu", "CORNERS_EMU_MAIN")
     h, w = imgs[0].shape
     stride = w if stride is None else stride
     n = len(imgs)
@@ -126,9 +97,7 @@ def run_standalone(tmp_path, imgs, max_corners, quality_level, min_distance, cap
         f.write(np.array([n, w, h, stride, max_corners, lcap, cap], np.int32).tobytes())
         f.write(np.array([quality_level, min_distance], np.float64).tobytes())
         f.write(np.stack([strided(i, stride) for i in imgs]).tobytes())
-    p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-    assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, text[-4000:]
+    emu_build.run_clean(exe, [fin, fout], 600)
     raw = np.fromfile(fout, np.uint8)
     eig = raw[:4 * w * h].view(np.float32).reshape(h, w)
     cnt = raw[4 * w * h:4 * w * h + 12 * n].view(np.int32).reshape(3, n)

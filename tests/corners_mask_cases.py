@@ -1,5 +1,5 @@
 """The Shi-Tomasi detector under a mask (include/vo_corners_mask.h) as the tests see it: the reference, the case table, and the
-product's masked kernels run through the coroutine emulator (tests/host_check/corners_mask_emu.cpp).
+product's masked kernels run through the coroutine emulator (tests/host_check/corners_emu.cpp).
 
 THE REFERENCE is independent of the kernels.  The quality map is corners_ref.c's (corners_emu.ref_map); the rest is what OpenCV 4.5's
 goodFeaturesToTrack does with a mask, in numpy: minMaxLoc over the allowed pixels (f64; 0 when there is none), threshold(TOZERO) at
@@ -11,18 +11,11 @@ checks that first).  THE DISC MASK reference is written from the header's defini
 The libraries loaded into python are built WITHOUT sanitizer flags whatever the environment says.  The sanitizer tier is the same
 harness as a STAND-ALONE program with its own main(), built with -fsanitize=address,undefined (runtimes linked statically) and run
 as a child, as corners_emu.run_standalone does.  Nothing instrumented is loaded into python."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import corners_emu as ce
+import emu_build
 from conftest import vp
-
-EMU_SRC = os.path.join(ce.SRC_DIR, "corners_mask_emu.cpp")
-EMU_DEPS = [EMU_SRC] + ce.EMU_DEPS[1:]
-_emu = None
 
 
 # ---- the reference -----------------------------------------------------------------------------------------------------------
@@ -163,19 +156,6 @@ def disc_cases(w, h):
 
 # ---- the emulator ------------------------------------------------------------------------------------------------------------
 
-def load_emu():
-    global _emu
-    if _emu is None:
-        os.makedirs(ce.OUT_DIR, exist_ok=True)
-        so = os.path.join(ce.OUT_DIR, "libcorners_mask_emu.so")
-        if ce._stale(so, EMU_DEPS):
-            subprocess.check_call(ce.CXX + ["-O2", "-fPIC", "-shared", "-o", so, EMU_SRC])
-        _emu = C.CDLL(so)
-        _emu.cme_detect.argtypes = [C.c_void_p] * 3 + [C.c_int] * 8 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        _emu.cme_disc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    return _emu
-
-
 def _pack(imgs, masks, stride, mask_stride):
     h, w = imgs[0].shape
     buf = np.stack([ce.strided(i, stride) for i in imgs])
@@ -196,7 +176,7 @@ def emu_detect(imgs, masks, max_corners=0, quality_level=0.01, min_distance=5.0,
     lcap = w * h if lcap is None else lcap
     pts = np.zeros((n, max(cap, 1), 2), np.float32)
     nout, ncand = np.zeros(n, np.int32), np.zeros(n, np.int32)
-    rc = load_emu().cme_detect(vp(buf), vp(mbuf), vp(on), len(imgs), first, n, w, h, stride, mask_stride, max_corners, quality_level, min_distance,
+    rc = ce.load_emu().cme_detect(vp(buf), vp(mbuf), vp(on), len(imgs), first, n, w, h, stride, mask_stride, max_corners, quality_level, min_distance,
                                lcap, vp(pts), cap, vp(nout), vp(ncand))
     assert rc == 0
     return [(pts[s, :max(0, min(int(nout[s]), cap))].copy(), int(nout[s]), int(ncand[s])) for s in range(n)]
@@ -215,20 +195,14 @@ def emu_disc(w, h, kept, radius, mask_stride=None):
     mask_stride = w if mask_stride is None else mask_stride
     k = np.ascontiguousarray(kept, np.float32).reshape(-1, 2)
     out = np.zeros((h - 1) * mask_stride + w, np.uint8)
-    assert load_emu().cme_disc(vp(k) if len(k) else None, len(k), int(radius), w, h, mask_stride, vp(out)) == 0
+    assert ce.load_emu().cme_disc(vp(k) if len(k) else None, len(k), int(radius), w, h, mask_stride, vp(out)) == 0
     return _unstride(out, w, h, mask_stride)
 
 
 def run_standalone(tmp_path, imgs, masks, max_corners, quality_level, min_distance, cap, lcap, kept, radius, stride, mask_stride):
     """the images and masks through the stand-alone ASan + UBSan program, run as a child: no report, exit status 0.  Returns
     ([(corners, n, candidates)], disc mask of `kept`)"""
-    out_dir = os.path.join(ce.OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "corners_mask_emu_main")
-    if ce._stale(exe, EMU_DEPS):
-        subprocess.check_call(ce.CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                        "-static-libasan", "-static-libubsan", "-DCORNERS_MASK_EMU_MAIN", "-o", exe, EMU_SRC])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = emu_build.sanitized_program("corners_emu", "CORNERS_MASK_EMU_MAIN")
     h, w = imgs[0].shape
     n = len(imgs)
     k = np.ascontiguousarray(kept, np.float32).reshape(-1, 2)
@@ -238,9 +212,7 @@ def run_standalone(tmp_path, imgs, masks, max_corners, quality_level, min_distan
         f.write(np.array([n, w, h, stride, mask_stride, max_corners, lcap, cap, len(k), radius], np.int32).tobytes())
         f.write(np.array([quality_level, min_distance], np.float64).tobytes())
         f.write(buf.tobytes() + mbuf.tobytes() + on.tobytes() + k.tobytes())
-    p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-    assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, text[-4000:]
+    emu_build.run_clean(exe, [fin, fout], 600)
     raw = np.fromfile(fout, np.uint8)
     cnt = raw[:8 * n].view(np.int32).reshape(2, n)
     pts = raw[8 * n:8 * n + 8 * n * cap].view(np.float32).reshape(n, cap, 2)

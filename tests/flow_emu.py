@@ -5,38 +5,19 @@ The library loaded into python is built WITHOUT sanitizer flags whatever the env
 harness as a STAND-ALONE program with its own main(): every pyramid level in an exactly sized heap block, built with
 -fsanitize=address,undefined (runtimes linked statically) and run as a child.  Nothing instrumented is loaded into python."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from conftest import ROOT, vp
-
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("flow_emu.cpp", "emu_pyramid.h", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "post.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_tri.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-_lib = None
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
+import emu_build
+from conftest import vp
 
 
 def load():
-    """libflow_emu.so, built when a source is newer and loaded once per session"""
-    global _lib
-    if _lib is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "libflow_emu.so")
-        if _stale(so):
-            subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, os.path.join(SRC_DIR, "flow_emu.cpp")])
-        _lib = C.CDLL(so)
-        _lib.fe_track.restype = C.c_int
-        _lib.fe_compact.restype = C.c_int
-    return _lib
+    """libflow_emu.so, built when stale and loaded once per session"""
+    lib = emu_build.shared("flow_emu")
+    lib.fe_track.restype = C.c_int
+    lib.fe_compact.restype = C.c_int
+    return lib
 
 
 def track(lib, c, flags=0, guess=None, want_err=True, n_frames=1, counts=None, frame=0, n=None, max_count=30):
@@ -73,13 +54,7 @@ def compact(lib, pts0, nxt, status, threads):
 def run_standalone(tmp_path, c, flags=0, guess=None, what=None):
     """the case (one frame) through the stand-alone ASan + UBSan program, run as a child: no report, exit status 0.  Returns
     (next, status, err) and the compaction of that result (n_out, the rewritten status, keep_idx)"""
-    out_dir = os.path.join(OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "flow_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DFLOW_EMU_MAIN", "-o", exe, os.path.join(SRC_DIR, "flow_emu.cpp")])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = emu_build.sanitized_program("flow_emu", "FLOW_EMU_MAIN")
     h, w = c["prev"].shape
     n = len(c["pts"])
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
@@ -88,9 +63,7 @@ def run_standalone(tmp_path, c, flags=0, guess=None, what=None):
         f.write(np.array([0.01], np.float64).tobytes() + np.array([1e-3], np.float32).tobytes())
         f.write(c["prev"].tobytes() + c["next"].tobytes() + c["pts"].tobytes())
         f.write(np.ascontiguousarray(c["pts"] if guess is None else guess, np.float32).tobytes())
-    p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-    assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, (what, text[-4000:])
+    emu_build.run_clean(exe, [fin, fout], 600, what)
     raw = np.fromfile(fout, np.uint8)
     nxt = raw[:8 * n].view(np.float32).reshape(n, 2)
     err = raw[8 * n:12 * n].view(np.float32)

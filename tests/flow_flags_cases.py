@@ -12,35 +12,24 @@ min_eig=-1)), a value e is the checker's minEig bit for bit iff the same call gi
 min_eig = nextafter(e, +inf) in f32 -- the checker casts the threshold to f32 and tests minEig < thr.  eig_sets() holds the four
 point sets of the issue's table with the counts asserted from the checker's side; check_min_eigenvals() is the comparison."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 import flow_cases as fc
 import flow_win_cases as wc
-from conftest import ROOT, vp
+from conftest import vp
 
 FLAG_GUESS, FLAG_EIG = 4, 8
-SRC = os.path.join(ROOT, "tests", "host_check", "lk_flags_ref.c")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
 # CFLAGS of oracle/Makefile
-CFLAGS = ["-O2", "-std=c11", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall", "-Wextra", "-Wno-unused-parameter"]
+CFLAGS = ["-std=c11", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-Wall", "-Wextra", "-Wno-unused-parameter"]
 _CACHE = {}
-_lib = None
 
 
 def ref_lib():
-    global _lib
-    if _lib is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "liblk_flags_ref.so")
-        deps = [SRC] + [os.path.join(ROOT, "oracle", f) for f in ("orc_lk.c", "vo_oracle.h", "orc_internal.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            subprocess.check_call(["gcc"] + CFLAGS + ["-shared", "-o", so, SRC, "-lm"])
-        _lib = C.CDLL(so)
-        _lib.lkf_initial_flow.restype = C.c_int
-    return _lib
+    lib = emu_build.shared("lk_flags_ref", cc="gcc", flags=CFLAGS, libs=["-lm"])
+    lib.lkf_initial_flow.restype = C.c_int
+    return lib
 
 
 def driver(prev, nxt, pts, guess, win=21, max_level=3, max_count=30, eps=0.01, min_eig=1e-3, want_err=True):

@@ -28,59 +28,34 @@ int fe_track(const uint8_t *prev, const uint8_t *next, int w, int h, int max_lev
     using namespace vo;
     if (!lk_for_window(win, [](auto) {}) || (flags & ~(VO_LK_USE_INITIAL_FLOW | VO_LK_GET_MIN_EIGENVALS)) || n_frames < 1)
         return -1;
-    const Plan p = plan(w, h, max_level);
     const uint8_t *imgs[2] = {prev, next};
-    Heap heap(p, imgs, 2, w, h);
+    Heap heap(plan(w, h, max_level), imgs, 2, w, h);
     const PyrImage *d_imgs = heap.tab.data();
-    const PassPlan pp = pass_plan(p.levels, p.lw, p.lh, p.ls, /*wide border items*/ false);
-    for (int l = 0; l < p.levels; l++) {
-        const uint32_t nwg = pass_grid(pp, l, 2, 0);
-        for (uint32_t b = 0; b < nwg; b++)
-            emu::run_block(64, b, 0, 0, [&] { pyr_pass_kernel(d_imgs, l, p.levels, pp, 2u, 0); });
-    }
+    build_fused_pyramids(heap, 2);
     if (n <= 0)
-        return p.levels;
-    LkParams prm;
-    prm.max_level = p.levels - 1;
-    prm.max_count = max_count;
-    prm.epsilon = eps * eps;
-    prm.min_eig = min_eig;
-    prm.full_chain = 0;
-    const int cap = n + 3; // (cap != n: the frame stride of the outputs is the capacity)
-    std::vector<Quad> pairs((size_t)n_frames, Quad{0, 1, 1, 0});
-    std::vector<int> npts((size_t)n_frames, n);
-    int most = counts ? 0 : n;
-    for (int f = 0; counts && f < n_frames; f++) {
-        npts[(size_t)f] = counts[f] < 0 ? 0 : counts[f] > n ? n : counts[f];
-        most = npts[(size_t)f] > most ? npts[(size_t)f] : most;
-    }
-    std::vector<float2> in((size_t)n_frames * cap), out((size_t)n_frames * cap, make_float2(123456.f, -7.f));
-    std::vector<uint8_t> st((size_t)n_frames * cap, (uint8_t)0xA5);
-    std::vector<float> er((size_t)n_frames * cap, -1.f);
-    for (int f = 0; f < n_frames; f++) {
-        memcpy(&in[(size_t)f * cap], pts, sizeof(float2) * (size_t)n);
-        if (flags & VO_LK_USE_INITIAL_FLOW)
-            memcpy(&out[(size_t)f * cap], next_io + (size_t)f * 2 * n, sizeof(float2) * (size_t)n);
-    }
-    if (most > 0) { // launch_lk_flow of lk.hip over the largest count (the library's max_pts), a loop over the blocks as the launch
-        const LkGrid g = lk_grid(n_frames, most);
+        return heap.p.levels;
+    const LkParams prm = lk_params(heap.p, /*full_chain*/ 0, max_count, eps, min_eig);
+    ChainBatch bt(nullptr, n_frames, pts, 0, counts, n, 1); // (the pair and the points of every frame are the call's)
+    std::vector<float> er((size_t)n_frames * bt.cap, -1.f);
+    if (flags & VO_LK_USE_INITIAL_FLOW)
+        for (int f = 0; f < n_frames; f++)
+            memcpy(&bt.out[(size_t)f * bt.cap], next_io + (size_t)f * 2 * n, sizeof(float2) * (size_t)n);
+    if (bt.most > 0) { // launch_lk_flow of lk.hip over the largest count (the library's max_pts), a loop over the blocks as the launch
+        const LkGrid g = lk_grid(n_frames, bt.most);
         lk_for_window(win, [&](auto wc) {
             lk_flow_route<decltype(wc)::value>(flags, [&](auto kernel, auto... tail) {
                 for (int b = 0; b < g.blocks; b++)
                     emu::run_block(64, (unsigned)b, 0, 0, [&] {
-                        kernel(d_imgs, pairs.data(), in.data(), npts.data(), cap, n_frames, g.fpg, g.ppp, out.data(), st.data(),
+                        kernel(d_imgs, bt.q.data(), bt.in.data(), bt.npts.data(), bt.cap, n_frames, g.fpg, g.ppp, bt.out.data(), bt.st.data(),
                                err ? er.data() : nullptr, prm, tail...);
                     });
             });
         });
     }
-    for (int f = 0; f < n_frames; f++) {
-        memcpy(next_io + (size_t)f * 2 * n, &out[(size_t)f * cap], sizeof(float2) * (size_t)n);
-        memcpy(status + (size_t)f * n, &st[(size_t)f * cap], (size_t)n);
-        if (err)
-            memcpy(err + (size_t)f * n, &er[(size_t)f * cap], sizeof(float) * (size_t)n);
-    }
-    return p.levels;
+    bt.copy_back(next_io, status);
+    for (int f = 0; err && f < n_frames; f++)
+        memcpy(err + (size_t)f * n, &er[(size_t)f * bt.cap], sizeof(float) * (size_t)n);
+    return heap.p.levels;
 }
 
 // flow_compact_kernel over one frame by a workgroup of `threads` threads.  status [n] is rewritten; out0 / out1 [n][2], idx [n]

@@ -33,21 +33,13 @@ void launch(unsigned gx, unsigned gy, unsigned gz, int threads, F body)
 int g_pyr_lds = 2; // (default: the product chain) ke_set_pyr_lds: which pyramid chain build_pyramids emulates (0 / 1: three kernels with the column-walk / LDS pyr_down; 2: fused passes)
 
 // the PYRAMID stage of capi.hip's run_stages with the emulated kernels
-void build_pyramids(const Plan &p, const vo::PyrImage *d_imgs, int n_img)
+void build_pyramids(Heap &heap, int n_img)
 {
     using namespace vo;
-    if (g_pyr_lds == 2 || g_pyr_lds == 3) { // the fused passes (3: workgroups in dispatch order, what launches of fewer than 16 images use)
-        const int remap = g_pyr_lds == 2;
-        // the fused passes (round 4; what launch_pyramid_fused enqueues): one launch per level
-        const PassPlan pp = pass_plan(p.levels, p.lw, p.lh, p.ls, /*wide border items*/ remap != 0); // (the product's two regimes: many images =
-                                                                                                       //  XCD-pinned order + wide items, a few = dispatch order + thin)
-        for (int l = 0; l < p.levels; l++)
-            {
-                const uint32_t nwg = pass_grid(pp, l, (int)n_img, remap);
-                launch(nwg, 1, 1, 64, [&] { pyr_pass_kernel(d_imgs, l, p.levels, pp, (uint32_t)n_img, remap); });
-            }
-        return;
-    }
+    const Plan &p = heap.p;
+    const PyrImage *d_imgs = heap.tab.data();
+    if (g_pyr_lds == 2 || g_pyr_lds == 3) // the fused passes in the product's two regimes: many images = XCD-pinned order + wide items (2), a few = dispatch order + thin (3)
+        return build_fused_pyramids(heap, n_img, g_pyr_lds == 2);
     // the three-kernel chain: level 0's border + Scharr image, the pyr_down chain, then the other levels
     for (int first = 0, last = 1; first < p.levels; first = last, last = p.levels) {
         if (first == 1)
@@ -380,7 +372,7 @@ int ke_bordered_level(const uint8_t *img, int w, int h, int max_level, int level
     if (level < 0 || level >= p.levels)
         return -1;
     Heap heap(p, &img, 1, w, h);
-    build_pyramids(p, heap.tab.data(), 1);
+    build_pyramids(heap, 1);
     const int n = (int)heap.level_elems(level);
     if (n > cap)
         return -2;
@@ -488,7 +480,7 @@ int ke_run(const uint8_t *imgs, int n_img, int w, int h, int max_level, int want
     Heap heap(p, img_ptr.data(), n_img, w, h);
     std::vector<PyrImage> &tab = heap.tab;
     const PyrImage *d_imgs = tab.data();
-    build_pyramids(p, d_imgs, n_img);
+    build_pyramids(heap, n_img);
 
     if (want_level >= 0 && want_level < p.levels) {
         const int l = want_level;
@@ -505,12 +497,7 @@ int ke_run(const uint8_t *imgs, int n_img, int w, int h, int max_level, int want
         return p.levels;
 
     Quad quad{0, 1, 2, 3};
-    LkParams prm;
-    prm.max_level = p.levels - 1;
-    prm.max_count = max_count;
-    prm.epsilon = eps * eps;
-    prm.min_eig = min_eig;
-    prm.full_chain = full_chain;
+    const LkParams prm = lk_params(p, full_chain, max_count, eps, min_eig);
     std::vector<float2> out((size_t)4 * n);
     const int cap = n, n_frames = 1, fpg = 1, parts = 8, ppp = (n + parts - 1) / parts;
     if (g_lk_pair == 1) {

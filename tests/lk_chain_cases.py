@@ -9,15 +9,14 @@ to +-12 pixels, so tiles are refilled within a level.  Points: a grid that holds
 3 and 9 frames (parts of a frame's list over 8 and 4 XCDs; a group of 8 frames and a partial one), frame f with its own quad (the
 four images rotated by f) and its own number of points.  The checker's answers are computed once per session and never modified."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 import flow_cases as fc
 import flow_flags_cases as gc
 import flow_win_cases as wc
-from conftest import ROOT, vp
+from conftest import vp
 from test_oracle_images import smooth_image
 
 SHAPES = ((131, 97), (169, 169))          # (w, h)
@@ -122,30 +121,11 @@ def eig_set(shape, win, orc):
 
 
 # ---- the batched chain on the CPU emulator -----------------------------------------------------------------------------------
-SRC = os.path.join(ROOT, "tests", "host_check", "chain_emu.cpp")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-DEPS = [SRC] + [os.path.join(ROOT, "tests", "host_check", f) for f in ("emu_pyramid.h", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-_lib = None
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
-
-
 def emu_lib():
     """libchain_emu.so, built WITHOUT sanitizer flags whatever the environment says (nothing instrumented is loaded into python)"""
-    global _lib
-    if _lib is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "libchain_emu.so")
-        if _stale(so):
-            subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, SRC])
-        _lib = C.CDLL(so)
-        _lib.ce_chain.restype = C.c_int
-    return _lib
+    lib = emu_build.shared("chain_emu")
+    lib.ce_chain.restype = C.c_int
+    return lib
 
 
 def _inputs(shape, n_frames):
@@ -167,22 +147,14 @@ def emu_chain(shape, n_frames, full_chain=1, split=0):
 
 def emu_chain_standalone(tmp_path, shape, n_frames, full_chain=1, split=0):
     """the same launch through the stand-alone ASan + UBSan program, run as a child: no report, exit status 0"""
-    out_dir = os.path.join(OUT_DIR, "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "chain_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DCHAIN_EMU_MAIN", "-o", exe, SRC])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = emu_build.sanitized_program("chain_emu", "CHAIN_EMU_MAIN")
     w, h = shape
     imgs, q, cnt, pts, n = _inputs(shape, n_frames)
     fin, fout = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     with open(fin, "wb") as f:
         f.write(np.array([w, h, 3, 4, n_frames, n, full_chain, split], np.int32).tobytes())
         f.write(imgs.tobytes() + q.tobytes() + cnt.tobytes() + pts.tobytes())
-    p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
-    text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-    assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, text[-4000:]
+    emu_build.run_clean(exe, [fin, fout], 900)
     raw = np.fromfile(fout, np.uint8)
     k = n_frames * 4 * n
     return raw[:8 * k].view(np.float32).reshape(n_frames, 4, n, 2), raw[8 * k:9 * k].reshape(n_frames, 4, n), cnt

@@ -3,6 +3,7 @@ test_lk_cols_on_host.py (g++, the host text of vo_lkmath.h) and test_gpu_lk_cols
 import os
 import subprocess
 
+import emu_build
 from conftest import ROOT
 
 SRC_DIR = os.path.join(ROOT, "tests", "host_check")
@@ -11,7 +12,7 @@ RECORD = 48   # bytes of a ColsOut: val[4], ix[4], iy[4]
 
 def build_host(out_dir):
     exe = os.path.join(out_dir, "lk_cols_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", exe, os.path.join(SRC_DIR, "lk_cols_host.cpp")])
+    emu_build.build(exe, os.path.join(SRC_DIR, "lk_cols_host.cpp"), emu_build.FLAGS + ["-O2"])
     return exe
 
 

@@ -1,18 +1,17 @@
 """Inputs of the tests of lk_circular_queue_kernel (test_lk_queue_emulation.py on the CPU emulator, test_gpu_lk_queue.py on the
-MI355X) and the emulator harness tests/host_check/chain_queue_emu.cpp.
+MI355X) and their side of the emulator harness tests/host_check/chain_emu.cpp (cq_chain).
 
 Frames: the 96 x 88 "deep" case of lk_setup_cases.py (three levels; points inside, near and outside the image), frame f with the
 case's four images rotated by f and the case's points, repeated up to 64 and rotated by f, so that no two frames of a group of
 eight are alike.  What is compared is always the library (or the emulated kernel) against itself under the other split of the
 work: the static lk_circular_kernel is the reference, bit for bit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
 import lk_setup_cases as sc
-from conftest import ROOT, vp
+from conftest import vp
 
 W, H = sc.W, sc.H_DEEP
 N = 64
@@ -39,28 +38,6 @@ def points(n_frames):
 
 
 # ---- the emulator ----------------------------------------------------------------------------------------------------------------
-SRC = os.path.join(ROOT, "tests", "host_check", "chain_queue_emu.cpp")
-OUT_DIR = os.path.join(ROOT, "tests", "_build")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-DEPS = [SRC] + [os.path.join(ROOT, "tests", "host_check", f) for f in ("emu_pyramid.h", "hip_emu.h")] + \
-       [os.path.join(CSRC, f) for f in ("lk.hip", "dev/lk_dev.hip", "pyramid.hip", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_lkqueue.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-_lib = None
-
-
-def emu_lib():
-    """libchain_queue_emu.so, built without sanitizer flags whatever the environment says (nothing instrumented is loaded into python)"""
-    global _lib
-    if _lib is None:
-        os.makedirs(OUT_DIR, exist_ok=True)
-        so = os.path.join(OUT_DIR, "libchain_queue_emu.so")
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
-            subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared", "-o", so, SRC])
-        _lib = C.CDLL(so)
-        _lib.cq_chain.restype = C.c_int
-    return _lib
-
-
 def emu_chain(counts, full_chain, order, first_xcd=3, surplus_div=8):
     """(trk [F, 4, N, 2], status [F, 4, N], stats) of one emulated launch over len(counts) frames; order -1: lk_circular_kernel,
     0 / 1 / 2: the queue kernel with its workgroups in dispatch order / reversed / those of XCD first_xcd first.  stats:
@@ -71,7 +48,9 @@ def emu_chain(counts, full_chain, order, first_xcd=3, surplus_div=8):
     imgs, q, pts = np.ascontiguousarray(np.stack(images())), quads(nf), points(nf)
     trk, st = np.zeros((nf, 4, N, 2), np.float32), np.zeros((nf, 4, N), np.uint8)
     stats = np.zeros(5, np.int32)
-    levels = emu_lib().cq_chain(vp(imgs), 4, W, H, 3, vp(q), nf, vp(pts), vp(cnt), N, int(full_chain), int(order), int(first_xcd),
-                                int(surplus_div), vp(trk), vp(st), vp(stats))
-    assert levels == sc.depth(H, 3) + 1, levels   # (negative: the counters' own checks, chain_queue_emu.cpp)
+    lib = emu_build.shared("chain_emu")   # (the library of lk_chain_cases.py, without sanitizer flags whatever the environment says)
+    lib.cq_chain.restype = C.c_int
+    levels = lib.cq_chain(vp(imgs), 4, W, H, 3, vp(q), nf, vp(pts), vp(cnt), N, int(full_chain), int(order), int(first_xcd), int(surplus_div),
+                          vp(trk), vp(st), vp(stats))
+    assert levels == sc.depth(H, 3) + 1, levels   # (negative: the counters' own checks, chain_emu.cpp)
     return trk, st, tuple(int(v) for v in stats)

@@ -3,6 +3,7 @@ test_gpu_lk_level_setup.py."""
 import os
 import subprocess
 
+import emu_build
 from conftest import ROOT
 
 SRC_DIR = os.path.join(ROOT, "tests", "host_check")
@@ -12,7 +13,7 @@ SAMPLES = 1 << 20
 
 def build_host(out_dir):
     exe = os.path.join(out_dir, "rcp_host")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-o", exe, os.path.join(SRC_DIR, "rcp_host.cpp")])
+    emu_build.build(exe, os.path.join(SRC_DIR, "rcp_host.cpp"), emu_build.FLAGS + ["-O2"])
     return exe
 
 

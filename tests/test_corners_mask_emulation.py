@@ -1,5 +1,5 @@
 """The product's masked Shi-Tomasi kernels (visual_odom_amd/csrc/corners.hip: the masked map kernel, the candidate and select
-kernels under a mask table, the disc kernel) run on the CPU through the coroutine emulator (tests/host_check/corners_mask_emu.cpp) and
+kernels under a mask table, the disc kernel) run on the CPU through the coroutine emulator (tests/host_check/corners_emu.cpp) and
 held BIT FOR BIT to the reference of corners_mask_cases.py -- which is first held to corners_ref.c where there is no mask.  Every
 image and every mask sits in a heap block of exactly (h - 1) * stride + w bytes, the mask stride differs from the image stride, and
 the last test runs the same harness as a stand-alone ASan + UBSan program.  CPU only."""

@@ -8,13 +8,12 @@ is an AddressSanitizer abort.  Every destination row is checked OUTSIDE its w co
 kernel runs with fewer and with more waves than rows; the pull kernel's grid is a function of the shape (its launcher's), so it
 has one grid per case, plus the workgroups that carry the call's points.  Unit test of device code, not a product path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
+import emu_build
+from conftest import BUILD_DIR, SAN_FLAGS, vp
 
 GRAY8_X2, BGR8, RGB8, BGRA8, RGBA8 = 1, 2, 3, 4, 5
 BPP = {GRAY8_X2: 2, BGR8: 3, RGB8: 3, BGRA8: 4, RGBA8: 4}
@@ -25,17 +24,7 @@ GUARD = 0xA5
 
 @pytest.fixture(scope="module")
 def ife():
-    src_dir = os.path.join(ROOT, "tests", "host_check")
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    so = os.path.join(BUILD_DIR, "libingest_fmt_emu.so")
-    csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
-    deps = [os.path.join(src_dir, f) for f in ("ingest_fmt_emu.cpp", "hip_emu.h")]
-    deps += [os.path.join(csrc, f) for f in ("ingest_fmt.hip", "vo_isa.h", "vo_dev.h", "vo_kernels.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas", "-Wno-attributes"] + SAN_FLAGS + ["-o", so,
-                               os.path.join(src_dir, "ingest_fmt_emu.cpp")])
-    lib = C.CDLL(so)
+    lib = emu_build.shared("ingest_fmt_emu", SAN_FLAGS, BUILD_DIR)
     lib.ife_seq_ingest.restype = C.c_int
     lib.ife_pull.restype = C.c_int
     return lib

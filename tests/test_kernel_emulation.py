@@ -5,34 +5,18 @@ handling -- everything of the LK data path except the silicon.  The -m gpu tests
 comparisons on the MI355X through the C ABI; this file is what lets a kernel change be checked
 before any GPU time is spent.  Unit test of device code, not a product path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import device_vectors as dv
-from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
+import emu_build
+from conftest import BUILD_DIR, SAN_FLAGS, vp
 
 
 @pytest.fixture(scope="module")
 def kemu():
-    src_dir = os.path.join(ROOT, "tests", "host_check")
-    out_dir = BUILD_DIR
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libkernel_emu.so")
-    csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
-    deps = [os.path.join(src_dir, f) for f in ("kernel_emu.cpp", "emu_pyramid.h", "hip_emu.h")]
-    deps += [os.path.join(csrc, f) for f in ("lk.hip", "pyramid.hip", "fast.hip", "dev/lk_dev.hip", "dev/pyramid_dev.hip", "dev/fast_dev.hip",
-                                               "vo_dev_hooks.h", "vo_dev.h", "vo_kernels.h", "vo_lkmath.h", "vo_isa.h", "vo_svd_wide.h",
-                                               "vo_linalg.h", "vo_epnp.h", "pnp.hip", "vo_p3p.h", "vo_math.h",
-                                               "vo_seqtail.h", "vo_integrate.h", "post.hip", "vo_tri.h",
-                                               "essential.hip", "vo_fivept.h", "seq.hip")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-Wno-unknown-pragmas", "-Wno-attributes"] + SAN_FLAGS + ["-o", so,
-                               os.path.join(src_dir, "kernel_emu.cpp")])
-    lib = C.CDLL(so)
+    lib = emu_build.shared("kernel_emu", SAN_FLAGS, BUILD_DIR)
     lib.ke_run.restype = C.c_int
     return lib
 

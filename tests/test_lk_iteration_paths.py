@@ -1,5 +1,5 @@
 """Every way out of the LK Gauss-Newton iteration, on the CPU: the real lk.hip through the SIMT emulator of tests/host_check
-(kernel_emu.cpp, built here WITHOUT sanitizer flags under a file name of its own) against the checker -- the cases of
+(kernel_emu.cpp, loaded here WITHOUT sanitizer flags whatever the environment says) against the checker -- the cases of
 tests/lk_iteration_cases.py, each crossed with max_count in {1, 2, 30} and epsilon in {1e-30, 0.01, 10}.  Status is compared on every
 hop, positions as raw bits on every hop the checker reports alive.
 
@@ -8,29 +8,18 @@ the window corner plus half a window is formed behind the loop, by how it was le
 the wrong half, before the first iteration, or with the half step of the oscillation test in another rounding order: the sweep
 takes every exit at the first, the second and a later iteration, in levels above 0 and at level 0."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emu_build
 import lk_iteration_cases as ic
-from conftest import ROOT, vp
+from conftest import vp
 
 
 @pytest.fixture(scope="module")
 def iemu():
-    src_dir = os.path.join(ROOT, "tests", "host_check")
-    csrc = os.path.join(ROOT, "visual_odom_amd", "csrc")
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libkernel_emu_iteration.so")
-    deps = [os.path.join(src_dir, f) for f in os.listdir(src_dir)] + [os.path.join(d, f) for d in (csrc, os.path.join(csrc, "dev")) for f in os.listdir(d)
-                                                                     if f.endswith((".h", ".hip"))]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes",
-                               "-o", so, os.path.join(src_dir, "kernel_emu.cpp")])
-    lib = C.CDLL(so)
+    lib = emu_build.shared("kernel_emu")
     lib.ke_run.restype = C.c_int
     return lib
 

@@ -14,7 +14,7 @@ import pytest
 
 import lk_setup_cases as sc
 from conftest import vp
-from test_lk_iteration_paths import iemu  # noqa: F401  (the fixture: libkernel_emu_iteration.so, built once for both files)
+from test_lk_iteration_paths import iemu  # noqa: F401  (the fixture: libkernel_emu.so without sanitizer flags, loaded once for both files)
 
 
 def run_chain(lib, c, prm, variant=0):

@@ -1,4 +1,4 @@
-"""lk_circular_queue_kernel against lk_circular_kernel on the CPU emulator (tests/host_check/chain_queue_emu.cpp): 17 frames of
+"""lk_circular_queue_kernel against lk_circular_kernel on the CPU emulator (tests/host_check/chain_emu.cpp: cq_chain): 17 frames of
 the 96 x 88 "deep" case -- two groups of eight and a partial third -- with 0, 1, 5, 64, ... points, the queue kernel's workgroups
 run in dispatch order, in reverse and with one XCD's workgroups before all others.  Tracks and status of all four hops, rows a
 frame does not track included (they keep the fill), equal bit for bit in the default mode and with full_chain."""

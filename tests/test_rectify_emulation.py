@@ -12,33 +12,20 @@ exactly sized heap blocks, built with -fsanitize=address,undefined (the runtimes
 starts in whatever environment the suite runs in, which it inherits unchanged apart from the sanitizers' own option variables)
 and run as a child over the barrel and edge cases.  Nothing instrumented is loaded into python.  Unit test of device code, not a product path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import BUILD_DIR, ROOT, SAN_FLAGS, vp
+import emu_build
+from conftest import BUILD_DIR, SAN_FLAGS, vp
 from rectify_cases import HEIGHTS, MAP_KINDS, WIDTHS, make_image, make_maps, remap_ref
 
 GUARD = 0xA5
-SRC_DIR = os.path.join(ROOT, "tests", "host_check")
-CSRC = os.path.join(ROOT, "visual_odom_amd", "csrc")
-DEPS = [os.path.join(SRC_DIR, f) for f in ("rectify_emu.cpp", "hip_emu.h")] + [os.path.join(CSRC, f) for f in ("rectify.hip", "vo_rectify.h", "vo_isa.h", "vo_dev.h", "vo_kernels.h")]
-CXX = ["g++", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-Wno-attributes"]
-
-
-def _stale(target):
-    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in DEPS)
 
 
 @pytest.fixture(scope="module")
 def rfe():
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    so = os.path.join(BUILD_DIR, "librectify_emu.so")
-    if _stale(so):
-        subprocess.check_call(CXX + ["-O2", "-fPIC", "-shared"] + SAN_FLAGS + ["-o", so, os.path.join(SRC_DIR, "rectify_emu.cpp")])
-    lib = C.CDLL(so)
+    lib = emu_build.shared("rectify_emu", SAN_FLAGS, BUILD_DIR)
     lib.rfe_pack.restype = C.c_int
     lib.rfe_rectify.restype = C.c_int
     return lib
@@ -108,13 +95,7 @@ def test_pack_refuses_a_far_displacement_that_is_inside(rfe):
 @pytest.mark.parametrize("kind", ["barrel", "edges"])
 def test_rectify_kernel_standalone_under_sanitizers(tmp_path, kind):
     """ASan + UBSan over the kernel source and the packing in a program of its own: exactly sized raw planes and maps, no report"""
-    out_dir = os.path.join(ROOT, "tests", "_build", "san")
-    os.makedirs(out_dir, exist_ok=True)
-    exe = os.path.join(out_dir, "rectify_emu_main")
-    if _stale(exe):
-        subprocess.check_call(CXX + ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                                     "-static-libasan", "-static-libubsan", "-DRECTIFY_EMU_MAIN", "-o", exe, os.path.join(SRC_DIR, "rectify_emu.cpp")])
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:detect_stack_use_after_return=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    exe = emu_build.sanitized_program("rectify_emu", "RECTIFY_EMU_MAIN")
     for w, h in ((33, 37), (519, 32), (64, 32)):
         maps, sides, imgs, want = case(kind, w, h)
         pitch, n_waves = (32 + w + 24 + 15) // 16 * 16, 7
@@ -125,9 +106,7 @@ def test_rectify_kernel_standalone_under_sanitizers(tmp_path, kind):
             for mx, my in maps:
                 f.write(mx.tobytes() + my.tobytes())
             f.write(np.stack(imgs).tobytes())
-        p = subprocess.run([exe, fin, fout], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
-        text = "\n".join(l for l in p.stdout.splitlines() if "doesn't fully support makecontext/swapcontext" not in l)
-        assert p.returncode == 0 and "ERROR" not in text and "runtime error" not in text, text[-4000:]
+        emu_build.run_clean(exe, [fin, fout], 300)
         dst = np.fromfile(fout, np.uint8).reshape(len(imgs), h, pitch)
         assert np.array_equal(dst[:, :, :w], want)
         assert np.all(dst[:, :, w:] == GUARD)
