@@ -475,6 +475,10 @@ int vo_seq_get_trajectory(vo_ctx *ctx, int seq, int first, int count, double *ro
 
 /* one pyramid level of one image back to the host (tests): out must hold w_l*h_l bytes (NULL: only the size is returned) */
 int vo_batch_get_pyramid_level(vo_ctx *ctx, int image_idx, int level, uint8_t *out, int *w_l, int *h_l);
+/* the whole bordered planes of one level of one image back to the host (tests): the pixel plane with its REFLECT_101 border and
+ * the packed Scharr plane (Ix | Iy << 16, zero outside the image), [rows][stride] each, rows = h_l + 2 * VO_BY, the image at row
+ * VO_BY = 24, column VO_BX = 32.  Any of the four may be NULL (pix and der NULL: only the sizes are returned). */
+int vo_batch_get_level_planes(vo_ctx *ctx, int image_idx, int level, uint8_t *pix, uint32_t *der, int *stride, int *rows);
 
 /* algorithmic HBM bytes of one frame at the current configuration:
  * bytes[0] = pyramid, [1] = LK, [2] = post (filter + triangulation + PnP), for n points */

@@ -233,6 +233,23 @@ def main():
     expect("vo_batch_get_pyramid_level", OK, ctx, 0, 0, NULL, C.byref(n_out), C.byref(n2))  # sizes only
     if (n_out.value, n2.value) != (W, H):
         fails.append("vo_batch_get_pyramid_level(out = NULL) did not return the level's size")
+    p_stride, p_rows = (32 + W + 24 + 15) // 16 * 16, H + 2 * 24   # level 0's bordered plane: VO_BX + w + VO_BY columns rounded up to 16
+    pix, der = np.full((p_rows, p_stride), 7, np.uint8), np.full((p_rows, p_stride), 7, np.uint32)
+    expect("vo_batch_get_level_planes", ARG, NULL, 0, 0, vp(pix), vp(der), C.byref(n_out), C.byref(n2))
+    for bad in ((-1, 0), (4, 0), (0, -1), (0, 5)):
+        expect("vo_batch_get_level_planes", ARG, ctx, bad[0], bad[1], vp(pix), vp(der), C.byref(n_out), C.byref(n2))
+    n_out.value = n2.value = 0
+    expect("vo_batch_get_level_planes", OK, ctx, 0, 0, NULL, NULL, C.byref(n_out), C.byref(n2))  # sizes only
+    if (n_out.value, n2.value) != (p_stride, p_rows):
+        fails.append("vo_batch_get_level_planes(pix = der = NULL) did not return the plane's stride and rows")
+    expect("vo_batch_get_level_planes", OK, ctx, 0, 0, NULL, NULL, NULL, NULL)
+    expect("vo_batch_get_level_planes", OK, ctx, 0, 0, vp(pix), NULL, NULL, NULL)   # each array alone (blank images, built above)
+    if pix.any() or not (der == 7).all():
+        fails.append("vo_batch_get_level_planes(der = NULL) did not fill pix alone")
+    pix[:] = 7
+    expect("vo_batch_get_level_planes", OK, ctx, 0, 0, NULL, vp(der), NULL, NULL)
+    if der.any() or not (pix == 7).all():
+        fails.append("vo_batch_get_level_planes(pix = NULL) did not fill der alone")
     expect("vo_model_bytes", ARG, NULL, W, H, 10, vp(dbuf))
     expect("vo_model_bytes", ARG, ctx, W, H, 10, NULL)
     expect("vo_model_bytes", ARG, ctx, 0, H, 10, vp(dbuf))

@@ -23,6 +23,7 @@ SHAPES = ((131, 97), (169, 169))          # (w, h)
 SHIFTS = ((0.0, 0.0), (11.6, -3.4), (-7.3, 12.0), (-12.0, -9.7))
 BATCHES = (1, 3, 9)
 WINDOWS = (5, 13, 19, 21)
+ALL_WINDOWS = tuple(range(5, 22, 2))      # lk_flow_flags_kernel<W> is one binary per window: the flag tests run every one
 _CACHE = {}
 
 
@@ -118,6 +119,14 @@ def eig_set(shape, win, orc):
         _CACHE[key] = dict(img=img, pts=pts, win=win, adm=adm, verifiable=ver, below=ver & ~st3,
                            want_no_err=fc.freeze(gc.plain_no_err(orc, img, img, pts, win=win, max_level=0)))
     return _CACHE[key]
+
+
+def flag_cases(shape, win, orc):
+    """(guess case, eig record, the pair of the eig record as a flow case) of one window, with the test's premise: the checker
+    started at the guess tracks at least 15 points and loses at least 15"""
+    g, s = guess_case(shape, win, orc), eig_set(shape, win, orc)
+    assert (g["want"][1] == 1).sum() >= 15 and (g["want"][1] == 0).sum() >= 15, (shape, win)
+    return g, s, dict(prev=s["img"], next=s["img"], pts=s["pts"], win=win, lk_max_level=0)
 
 
 # ---- the batched chain on the CPU emulator -----------------------------------------------------------------------------------

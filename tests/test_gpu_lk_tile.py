@@ -85,3 +85,16 @@ def test_two_image_calls(ctx, orc, shape, win):
         gc.check_min_eigenvals(orc, s, _track(ctx, e, min_eigenvals=True), (shape, win, "min eigenvalue"))
     finally:
         ctx.set_params(lk_max_level=3)
+
+
+@pytest.mark.parametrize("win", lc.ALL_WINDOWS)
+def test_flag_kernels_of_every_window(ctx, orc, win):
+    """lk_flow_flags_kernel<W> is nine binaries: voflag_track of each with a guess and with min_eigenvals against the checker
+    (tests/test_lk_tile_emulation.py runs the same cases on the emulator)"""
+    shape = lc.SHAPES[0]
+    try:
+        g, s, e = lc.flag_cases(shape, win, orc)
+        fc.assert_same(_track(ctx, g, guess=g["guess"]), g["want"], (shape, win, "guess"))
+        gc.check_min_eigenvals(orc, s, _track(ctx, e, min_eigenvals=True), (shape, win, "min eigenvalue"))
+    finally:
+        ctx.set_params(lk_max_level=3)

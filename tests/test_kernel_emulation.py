@@ -74,10 +74,11 @@ def test_emulated_borders(kemu, orc, shape, pyr_kernel):
     """every pixel of the bordered allocation that a kernel may read: REFLECT_101 of the level around it (VO_BY rows above /
     below, VO_BX columns left, at least VO_BY right -- the fill runs to the end of the row), derivatives zero outside the
     image (calcSharrDeriv's constant border of the derivative image, which LK reads for off-image windows)"""
-    BX, BY = 32, 24
+    from pyramid_planes import BX, BY, expected_planes
     rng = np.random.default_rng(shape[1])
     img = rng.integers(0, 256, shape, dtype=np.uint8)
     ref = orc.build_pyramid(img, 3)
+    want = expected_planes(orc, img, 3)
     h, w = shape
     for l in range(len(ref)):
         cap = 4 << 20
@@ -90,23 +91,12 @@ def test_emulated_borders(kemu, orc, shape, pyr_kernel):
         assert (lh, lw) == ref[l].shape and ls % 16 == 0 and ls - BX - lw >= BY
         pix = pix[:ls * (lh + 2 * BY)].reshape(lh + 2 * BY, ls)
         der = der[:ls * (lh + 2 * BY)].reshape(lh + 2 * BY, ls)
-        right = ls - BX - lw
-
-        def refl(n, lo, hi):   # cv::borderInterpolate(BORDER_REFLECT_101), repeated for levels narrower than the border
-            idx = np.arange(lo, hi)
-            if n == 1:
-                return np.zeros_like(idx)
-            period = 2 * (n - 1)
-            idx = np.mod(idx, period)
-            return np.where(idx >= n, period - idx, idx)
-        expect = ref[l][refl(lh, -BY, lh + BY)][:, refl(lw, -BX, lw + right)]
+        expect, packed = want[l]                # (tests/pyramid_planes.py: the definition the device test shares)
         assert np.array_equal(pix, expect), l
         inside = np.zeros_like(der, bool)
         inside[BY:BY + lh, BX:BX + lw] = True
         assert not der[~inside].any(), l
-        d = orc.scharr(ref[l]).astype(np.int64) * 4
-        packed = ((d[..., 0] & 0xffff) | ((d[..., 1] & 0xffff) << 16)).astype(np.uint32)
-        assert np.array_equal(der[BY:BY + lh, BX:BX + lw], packed), l
+        assert np.array_equal(der[BY:BY + lh, BX:BX + lw], packed[BY:BY + lh, BX:BX + lw]), l
 
 
 def _oracle_hops(orc, L0, R0, L1, R1, pts, **kw):

@@ -54,6 +54,16 @@ def test_emulated_two_image_calls(orc, shape, win):
     gc.check_min_eigenvals(orc, s, flow_emu.track(lib, e, flags=gc.FLAG_EIG)[0], (shape, win, "min eigenvalue"))
 
 
+@pytest.mark.parametrize("win", [w for w in lc.ALL_WINDOWS if w not in lc.WINDOWS])
+def test_emulated_flag_kernels_of_the_other_windows(orc, win):
+    """USE_INITIAL_FLOW and GET_MIN_EIGENVALS of the windows the test above leaves out, at 131 x 97: with it, every case of
+    test_gpu_lk_tile.py::test_flag_kernels_of_every_window runs here too, so a failure on the device alone is the device's"""
+    shape, lib = lc.SHAPES[0], flow_emu.load()
+    g, s, e = lc.flag_cases(shape, win, orc)
+    fc.assert_same(flow_emu.track(lib, g, flags=gc.FLAG_GUESS, guess=g["guess"])[0], g["want"], (shape, win, "guess"))
+    gc.check_min_eigenvals(orc, s, flow_emu.track(lib, e, flags=gc.FLAG_EIG)[0], (shape, win, "min eigenvalue"))
+
+
 def test_emulated_two_image_batch(orc):
     """three frames of one launch with their own counts (parts of a frame's list over 4 XCDs), W = 13"""
     shape, win = lc.SHAPES[1], 13

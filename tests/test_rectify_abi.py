@@ -15,7 +15,7 @@ from visual_odom_amd import _lib, rectify, run
 
 NEW_FIELDS = ("rectify", "rect_w", "rect_h", "rect_map_stride", "rect_map_x_left", "rect_map_y_left", "rect_map_x_right", "rect_map_y_right")
 INPUT_FORMAT_OFFSET = 72   # what it was before the fields were appended: 2 int, 2 double, 3 int + 1 float, 1 double, 1 int (+ 4 padding), 2 double
-N_EXPORTS = 51
+N_EXPORTS = 52            # (51 when rectification came; vo_batch_get_level_planes since)
 
 
 def test_struct_size_and_offsets_against_a_compiled_probe(tmp_path):

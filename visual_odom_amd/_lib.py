@@ -35,7 +35,7 @@ EXPORTS = (
     "vo_batch_configure", "vo_batch_upload_image", "vo_batch_upload_image_dev", "vo_batch_set_quads",
     "vo_batch_set_points", "vo_batch_set_projection", "vo_batch_run", "vo_batch_run_timed", "vo_batch_run_slot", "vo_batch_slot_times",
     "vo_batch_sync", "vo_batch_get_tracks", "vo_batch_get_filtered", "vo_batch_get_pose",
-    "vo_batch_get_pyramid_level", "vo_model_bytes", "vo_essential_pose", "vo_batch_get_essential",
+    "vo_batch_get_pyramid_level", "vo_batch_get_level_planes", "vo_model_bytes", "vo_essential_pose", "vo_batch_get_essential",
     "vo_seq_configure", "vo_seq_reset", "vo_seq_push_pair", "vo_seq_push_pair_dev", "vo_seq_push_pairs", "vo_seq_step", "vo_seq_sync",
     "vo_seq_get_state", "vo_seq_get_trajectory", "vo_set_schedule", "vo_get_schedule", "vo_get_probe_log",
     "vo_export_schedule", "vo_import_schedule", "vo_kept_pair_id",
@@ -863,6 +863,15 @@ class Context:
         out = np.zeros((h.value, w.value), np.uint8)
         self._chk(self.lib.vo_batch_get_pyramid_level(self.h, idx, level, _p(out), C.byref(w), C.byref(h)))
         return out
+
+    def batch_get_level_planes(self, idx, level):
+        """(pix uint8, der uint32), [rows][stride] each: the whole bordered pixel plane and packed Scharr plane of one level"""
+        stride, rows = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.vo_batch_get_level_planes(self.h, idx, level, None, None, C.byref(stride), C.byref(rows)))
+        pix = np.zeros((rows.value, stride.value), np.uint8)
+        der = np.zeros((rows.value, stride.value), np.uint32)
+        self._chk(self.lib.vo_batch_get_level_planes(self.h, idx, level, _p(pix), _p(der), None, None))
+        return pix, der
 
     def model_bytes(self, w, h, n_points):
         b = np.zeros(3, np.float64)

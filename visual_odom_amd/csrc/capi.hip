@@ -1209,6 +1209,28 @@ int vo_batch_get_pyramid_level(vo_ctx *c, int idx, int level, uint8_t *out, int 
     return VO_OK;
 }
 
+int vo_batch_get_level_planes(vo_ctx *c, int idx, int level, uint8_t *pix, uint32_t *der, int *stride, int *rows)
+{
+    if (!c)
+        return VO_ERR_ARG;
+    if (idx < 0 || idx >= c->n_images || level < 0 || level >= c->levels)
+        return fail(c, VO_ERR_ARG, "vo_batch_get_level_planes: bad image / level");
+    VO_HIP_TRY(c, hipSetDevice(c->device));
+    const int n_rows = c->lh[level] + 2 * VO_BY;
+    if (stride)
+        *stride = c->lstride[level];
+    if (rows)
+        *rows = n_rows;
+    const size_t off = (size_t)idx * c->img_bytes + c->loff[level], n = (size_t)c->lstride[level] * n_rows;
+    if (pix)
+        VO_HIP_TRY(c, hipMemcpyAsync(pix, c->d_pix + off, n, hipMemcpyDeviceToHost, c->sel->stream));
+    if (der)
+        VO_HIP_TRY(c, hipMemcpyAsync(der, c->d_der + off, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->sel->stream));
+    if (pix || der)
+        VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    return VO_OK;
+}
+
 int vo_model_bytes(const vo_ctx *c, int w, int h, int n_points, double *b)
 {
     if (!c || !b || w < 1 || h < 1 || n_points < 0)
