@@ -13,7 +13,8 @@
 // cv::Point2f): no OpenCV algorithm is called.  Where the OpenCV headers are not installed (this repository's test build)
 // the same file compiles against a type-only stand-in that the include path provides (oracle/ref_dropin/Makefile:
 // -I oracle/ref_shim); oracle/ref_dropin compiles THIS file with the reference's unmodified sources and
-// tests/test_gpu_parity.py::test_reference_sources_run_on_libvo_hip runs the result on the GPU.
+// tests/test_gpu_parity.py::test_reference_sources_run_on_libvo_hip runs the result on the GPU; tests/test_gpu_adapter.py calls
+// featureTracking_hip, featureDetectionGoodFeaturesToTrack_hip and goodFeaturesToTrack_hip there one by one.
 #pragma once
 
 #if __has_include(<opencv2/core.hpp>)

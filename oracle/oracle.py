@@ -342,15 +342,56 @@ def recover_pose(E, pts1, pts2, focal, pp, mask=None):
 # ---- oracle/_ref: the reference's OWN glue sources (feature.cpp, bucket.cpp) compiled where they lie ----------
 _REF_SO = os.path.join(_HERE, "_ref", *(["san"] if _SAN else []), "libvo_refglue.so")
 _ref = None
+_REF = "/root/reference"
+_ROOT = os.path.dirname(_HERE)
+_GLUE_SOURCES = [os.path.join(_HERE, f) for f in ("Makefile", "ref_shim/ref_glue.cpp", "ref_shim/vo_cv_shim.h")] + \
+                [os.path.join(_ROOT, "tests", "host_check", "corners_ref.c")]
+_DROPIN_SO = os.path.join(_HERE, "_ref", "libvo_ref_dropin.so")
+_DROPIN_SOURCES = [os.path.join(_HERE, f) for f in ("ref_dropin/Makefile", "ref_dropin/dropin_glue.cpp", "ref_shim/vo_cv_shim.h")] + \
+                  [os.path.join(_ROOT, f) for f in ("adapters/feature_hip.cpp", "adapters/feature_hip.h", "include/vo_hip.h", "include/vo_flow.h",
+                                                    "include/vo_flow_win.h", "include/vo_flow_flags.h", "include/vo_corners.h", "include/vo_corners_mask.h")]
+
+
+def _make_by_content(so, sources, make):
+    """make, after removing `so` unless it was built from exactly these sources (and the reference's): their digest lies next to
+    it.  File times alone do not say so: a tree that was unpacked over one holding an older build brings sources older than that
+    build's libraries."""
+    import hashlib
+    d = hashlib.sha256()
+    for sub in ("src", "src/evaluate"):
+        sources = sources + [os.path.join(_REF, sub, f) for f in sorted(os.listdir(os.path.join(_REF, sub))) if f.endswith((".cpp", ".h"))]
+    for s in sources:
+        d.update(os.path.basename(s).encode() + b"\0" + open(s, "rb").read() + b"\0")
+    stamp, want = so + ".sources", d.hexdigest()
+    same = os.path.exists(so) and os.path.exists(stamp) and open(stamp).read().strip() == want
+    for f in [stamp] + ([] if same else [so]):
+        if os.path.exists(f):
+            os.remove(f)
+    subprocess.check_call(make)
+    with open(stamp, "w") as f:
+        f.write(want + "\n")
+
+
+def can_build_ref():
+    return os.path.exists(_REF + "/src/feature.cpp") and os.path.exists(_REF + "/src/visualOdometry.cpp")
 
 
 def build_ref():
     """`make -C oracle ref`: only possible where /root/reference exists (the authoring container); elsewhere the
     prebuilt oracle/_ref/libvo_refglue.so that travelled with the snapshot is used.  Returns the path or None."""
-    if os.path.exists("/root/reference/src/feature.cpp"):
+    if can_build_ref():
         build()
-        subprocess.check_call(_MAKE + ["ref"])
+        _make_by_content(_REF_SO, _GLUE_SOURCES + [os.path.join(_HERE, f) for f in sorted(os.listdir(_HERE)) if f.endswith((".c", ".h"))],
+                         _MAKE + ["ref"])
     return _REF_SO if os.path.exists(_REF_SO) else None
+
+
+def build_ref_dropin():
+    """`make -C oracle/ref_dropin`: the same reference sources and the shipped adapter over libvo_hip.so (which has to be built) ->
+    oracle/_ref/libvo_ref_dropin.so, only where /root/reference exists.  Returns the path or None."""
+    if can_build_ref():
+        _make_by_content(_DROPIN_SO, _DROPIN_SOURCES, ["make", "-s", "-C", os.path.join(_HERE, "ref_dropin")])
+    return _DROPIN_SO if os.path.exists(_DROPIN_SO) else None
 
 
 def ref_lib():
@@ -396,6 +437,48 @@ def ref_bucketing_features(rows, cols, points, ages, bucket_size, features_per_b
                                           features_per_bucket)
     assert rc == 0
     return P[:n_p.value].copy(), A[:n_a.value].copy()
+
+
+def ref_delete_unmatch_features(points0, points1, status):
+    """the reference's own deleteUnmatchFeatures (feature.cpp:20-37): (points0, points1) compacted, status at its length"""
+    p0 = np.array(points0, np.float32).reshape(-1, 2).copy()
+    p1 = np.array(points1, np.float32).reshape(-1, 2).copy()
+    st = np.array(status, np.uint8).reshape(-1).copy()
+    n = len(st)
+    assert len(p0) == n and len(p1) == n
+    m = ref_lib().ref_delete_unmatch_features(_vp(p0), _vp(p1), _vp(st), n)
+    assert 0 <= m <= n
+    return p0[:m].copy(), p1[:m].copy(), st
+
+
+def ref_feature_tracking(img1, img2, points1):
+    """the reference's own featureTracking (feature.cpp:64-74) over the oracle's calcOpticalFlowPyrLK: (points1, points2)
+    compacted, and status as long as the function left it"""
+    a, b = np.ascontiguousarray(img1, np.uint8), np.ascontiguousarray(img2, np.uint8)
+    h, w = a.shape
+    assert b.shape == (h, w)
+    p1 = np.array(points1, np.float32).reshape(-1, 2).copy()
+    n = len(p1)
+    p2 = np.zeros((max(n, 1), 2), np.float32)
+    st = np.zeros(max(n, 1), np.uint8)
+    ns = C.c_int(-1)
+    m = ref_lib().ref_feature_tracking(_vp(a), _vp(b), w, h, _vp(p1), n, _vp(p2), _vp(st), C.byref(ns))
+    assert 0 <= m <= n and 0 <= ns.value <= n
+    return p1[:m].copy(), p2[:m].copy(), st[:ns.value].copy()
+
+
+def ref_feature_detection_gftt(img, cap=None):
+    """the reference's own featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) over tests/host_check/corners_ref.c;
+    img may be a view whose rows are further apart than its width.  Returns (corners [min(n, cap), 2], n found)"""
+    img = np.asarray(img, np.uint8)
+    h, w = img.shape
+    if img.strides[1] != 1 or img.strides[0] < w:
+        img = np.ascontiguousarray(img)
+    cap = w * h if cap is None else cap
+    pts = np.zeros((max(cap, 1), 2), np.float32)
+    n = ref_lib().ref_feature_detection_gftt(C.c_void_p(img.ctypes.data), w, h, int(img.strides[0]), _vp(pts), cap)
+    assert n >= 0
+    return pts[:min(n, cap)].copy(), n
 
 
 def ref_append_new_features(img, points, ages, cap=200000):

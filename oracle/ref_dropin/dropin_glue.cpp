@@ -15,6 +15,8 @@
  * tests/test_gpu_parity.py runs the reference's matchingFeatures() / trackingFrame2Frame() / integrateOdometryStereo()
  * through this library on the MI355X and compares, frame after frame, with the same reference code running over the
  * CPU oracle (oracle/_ref).  No reference source is copied or modified.
+ * The adapter_* exports at the end call the shipped adapter's entry points one by one on the caller's buffers
+ * (tests/adapter_cases.py, tests/test_gpu_adapter.py).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -296,6 +298,100 @@ extern "C" int adapter_detect_bucket(const uint8_t *img, int w, int h, float *pt
     } catch (const std::exception &ex) {
         fprintf(stderr, "dropin_glue: %s\n", ex.what());
         return -2;
+    }
+}
+
+/* ---- the adapter's other entry points, each on a cv::Mat built over the CALLER's buffer with the caller's row step (bytes).
+ * An exception comes back as -2 with its what() in adapter_last_error(); -1: the result does not fit the caller's array. */
+static std::string g_adapter_error;
+extern "C" const char *adapter_last_error(void) { return g_adapter_error.c_str(); }
+static int adapter_failed(const std::exception &ex)
+{
+    g_adapter_error = ex.what();
+    return -2;
+}
+
+/* featureTracking_hip.  points1 [n*2] in/out (compacted); points2 holds *n2 points on entry (the caller's stale contents) and
+ * the call's on return, array capacity cap2 points; status [cap_status] out, *n_status its length.  Returns points1's length. */
+extern "C" int adapter_feature_tracking(const uint8_t *img1, const uint8_t *img2, int w, int h, int step, float *points1, int n,
+                                        float *points2, int *n2, int cap2, uint8_t *status, int *n_status, int cap_status)
+{
+    try {
+        cv::Mat I1(h, w, CV_8UC1, (void *)img1, (size_t)step), I2(h, w, CV_8UC1, (void *)img2, (size_t)step);
+        std::vector<cv::Point2f> p1 = to_points(points1, n), p2 = to_points(points2, *n2);
+        std::vector<uchar> st(3, (uchar)7); /* (stale too) */
+        featureTracking_hip(I1, I2, p1, p2, st);
+        if ((int)p1.size() > n || (int)p2.size() > cap2 || (int)st.size() > cap_status)
+            return -1;
+        from_points(p1, points1, n);
+        *n2 = from_points(p2, points2, cap2);
+        *n_status = (int)st.size();
+        if (!st.empty())
+            memcpy(status, st.data(), st.size());
+        return (int)p1.size();
+    } catch (const std::exception &ex) {
+        return adapter_failed(ex);
+    }
+}
+
+/* featureDetectionGoodFeaturesToTrack_hip.  pts holds n_in points on entry (a non-empty vector is replaced, not appended to) and
+ * the first cap corners on return.  Returns the number of corners. */
+extern "C" int adapter_gftt_default(const uint8_t *img, int w, int h, int step, float *pts, int n_in, int cap)
+{
+    try {
+        cv::Mat I(h, w, CV_8UC1, (void *)img, (size_t)step);
+        std::vector<cv::Point2f> p = to_points(pts, n_in);
+        featureDetectionGoodFeaturesToTrack_hip(I, p);
+        return from_points(p, pts, cap);
+    } catch (const std::exception &ex) {
+        return adapter_failed(ex);
+    }
+}
+
+/* goodFeaturesToTrack_hip.  mask == NULL: an empty Mat; img_type / mask_type: the cv type of the two headers (CV_8UC1 = 0 is the
+ * one the adapter takes).  Returns the number of corners; pts takes the first cap. */
+extern "C" int adapter_gftt(const uint8_t *img, int w, int h, int step, int img_type, const uint8_t *mask, int mask_step, int mask_w,
+                            int mask_h, int mask_type, int max_corners, double quality, double min_distance, float *pts, int cap)
+{
+    try {
+        cv::Mat I(h, w, img_type, (void *)img, (size_t)step), M;
+        if (mask)
+            M = cv::Mat(mask_h, mask_w, mask_type, (void *)mask, (size_t)mask_step);
+        std::vector<cv::Point2f> p(2, cv::Point2f(-9.f, -9.f));
+        goodFeaturesToTrack_hip(I, p, max_corners, quality, min_distance, M);
+        return from_points(p, pts, cap);
+    } catch (const std::exception &ex) {
+        return adapter_failed(ex);
+    }
+}
+
+/* circularMatching_hip on the caller's four buffers (vo_adapter_keep_pair compares their addresses).  pts_l0 [n*2] in/out, the
+ * other four [n*2] out, ages [*n_ages] in/out.  Returns the survivor count. */
+extern "C" int adapter_circular_matching(const uint8_t *l0, const uint8_t *r0, const uint8_t *l1, const uint8_t *r1, int w, int h,
+                                         int step, float *pts_l0, int n, float *pts_r0, float *pts_r1, float *pts_l1,
+                                         float *pts_l0_ret, int *ages, int *n_ages)
+{
+    try {
+        cv::Mat L0(h, w, CV_8UC1, (void *)l0, (size_t)step), R0(h, w, CV_8UC1, (void *)r0, (size_t)step),
+            L1(h, w, CV_8UC1, (void *)l1, (size_t)step), R1(h, w, CV_8UC1, (void *)r1, (size_t)step);
+        std::vector<cv::Point2f> p_l0 = to_points(pts_l0, n), p_r0, p_l1, p_r1, p_ret;
+        FeatureSet fs;
+        fs.ages.assign(ages, ages + *n_ages);
+        circularMatching_hip(L0, R0, L1, R1, p_l0, p_r0, p_l1, p_r1, p_ret, fs);
+        const size_t m = p_l0.size();
+        if (m > (size_t)n || p_r0.size() != m || p_l1.size() != m || p_r1.size() != m || p_ret.size() != m || (int)fs.ages.size() > *n_ages)
+            return -1;
+        from_points(p_l0, pts_l0, n);
+        from_points(p_r0, pts_r0, n);
+        from_points(p_r1, pts_r1, n);
+        from_points(p_l1, pts_l1, n);
+        from_points(p_ret, pts_l0_ret, n);
+        for (size_t i = 0; i < fs.ages.size(); i++)
+            ages[i] = fs.ages[i];
+        *n_ages = (int)fs.ages.size();
+        return (int)m;
+    } catch (const std::exception &ex) {
+        return adapter_failed(ex);
     }
 }
 

@@ -20,6 +20,10 @@
 #include "evaluate_odometry.h" /* src/evaluate: calcSequenceErrors and friends (no OpenCV in there) */
 #include "vo_oracle.h"
 
+/* tests/host_check/corners_ref.c, compiled as C by the Makefile */
+extern "C" int cr_detect(const uint8_t *img, int w, int h, int stride, int max_corners, double quality_level, double min_distance,
+                         float *pts, int cap, int *n_cand, int trap);
+
 namespace cv {
 
 void KeyPoint::convert(const std::vector<KeyPoint> &keypoints, std::vector<Point2f> &points2f, const std::vector<int> &)
@@ -55,10 +59,33 @@ void FAST(Mat image, std::vector<KeyPoint> &keypoints, int threshold, bool nonma
         keypoints[i].pt = Point2f(pts[2 * i], pts[2 * i + 1]);
 }
 
-void goodFeaturesToTrack(Mat, std::vector<Point2f> &, int, double, double, Mat, int, bool, double)
+/* the one call the reference makes (feature.cpp:61): an 8-bit image, no mask, blockSize 3, no Harris -> cr_detect, the
+ * restatement of cv::goodFeaturesToTrack the device detector is held to (tests/host_check/corners_ref.c) */
+void goodFeaturesToTrack(Mat image, std::vector<Point2f> &corners, int maxCorners, double qualityLevel, double minDistance,
+                         Mat mask, int blockSize, bool useHarrisDetector, double)
 {
-    fprintf(stderr, "vo_cv_shim: goodFeaturesToTrack is not on the path and not provided\n");
-    abort();
+    if (image.type() != CV_8UC1 || image.empty() || !mask.empty() || blockSize != 3 || useHarrisDetector) {
+        fprintf(stderr, "vo_cv_shim: goodFeaturesToTrack called in a way the reference never does\n");
+        abort();
+    }
+    const std::vector<uchar> img = continuous(image);
+    const int mc = maxCorners > 0 ? maxCorners : 0; /* (upstream: maxCorners <= 0 means no limit) */
+    int cap = mc > 0 ? mc : 1 << 13, n;
+    std::vector<float> pts;
+    for (;;) {
+        pts.resize((size_t)2 * cap);
+        n = cr_detect(img.data(), image.cols, image.rows, image.cols, mc, qualityLevel, minDistance, pts.data(), cap, 0, 0);
+        if (n < 0) {
+            fprintf(stderr, "vo_cv_shim: goodFeaturesToTrack: qualityLevel > 0 && minDistance >= 0 (OpenCV asserts)\n");
+            abort();
+        }
+        if (n <= cap)
+            break;
+        cap = n;
+    }
+    corners.resize((size_t)n);
+    for (int i = 0; i < n; i++)
+        corners[i] = Point2f(pts[2 * i], pts[2 * i + 1]);
 }
 
 void calcOpticalFlowPyrLK(Mat prevImg, Mat nextImg, std::vector<Point2f> &prevPts, std::vector<Point2f> &nextPts,
@@ -308,6 +335,52 @@ int ref_append_new_features(const uint8_t *img, int w, int h, float *points, int
     *n_points = (int)fs.points.size();
     *n_ages = (int)fs.ages.size();
     return 0;
+}
+
+/* deleteUnmatchFeatures(points0, points1, status) (feature.cpp:20-37).  points0 / points1 [n*2] and status [n] in/out: the
+ * points come back compacted, status keeps its length.  Returns the survivor count. */
+int ref_delete_unmatch_features(float *points0, float *points1, uint8_t *status, int n)
+{
+    std::vector<cv::Point2f> p0 = to_points(points0, n), p1 = to_points(points1, n);
+    std::vector<uchar> st(status, status + n);
+    deleteUnmatchFeatures(p0, p1, st);
+    from_points(p0, points0, n);
+    from_points(p1, points1, n);
+    if ((int)st.size() != n || p0.size() != p1.size())
+        return -1;
+    if (n > 0) /* (an empty vector's data() may be null) */
+        memcpy(status, st.data(), (size_t)n);
+    return (int)p0.size();
+}
+
+/* featureTracking(img_1, img_2, points1, points2, status) (feature.cpp:64-74).  points1 [n*2] in/out (compacted), points2 [n*2]
+ * and status [n] out; *n_status: the length status came back with.  Returns the survivor count, -1 when the two point vectors
+ * come back with different lengths. */
+int ref_feature_tracking(const uint8_t *img1, const uint8_t *img2, int w, int h, float *points1, int n, float *points2,
+                         uint8_t *status, int *n_status)
+{
+    Quiet q;
+    cv::Mat I1(h, w, CV_8UC1, (void *)img1, (size_t)w), I2(h, w, CV_8UC1, (void *)img2, (size_t)w);
+    std::vector<cv::Point2f> p1 = to_points(points1, n), p2;
+    std::vector<uchar> st;
+    featureTracking(I1, I2, p1, p2, st);
+    from_points(p1, points1, n);
+    from_points(p2, points2, n);
+    *n_status = (int)st.size();
+    if (!st.empty() && n > 0)
+        memcpy(status, st.data(), st.size() < (size_t)n ? st.size() : (size_t)n);
+    return p1.size() == p2.size() ? (int)p1.size() : -1;
+}
+
+/* featureDetectionGoodFeaturesToTrack(image, points) (feature.cpp:49-62).  pts [cap*2] takes the first cap corners; `step`:
+ * bytes per image row (>= w).  Returns the number found. */
+int ref_feature_detection_gftt(const uint8_t *img, int w, int h, int step, float *pts, int cap)
+{
+    Quiet q;
+    cv::Mat image(h, w, CV_8UC1, (void *)img, (size_t)step);
+    std::vector<cv::Point2f> points(3, cv::Point2f(-1.f, -1.f)); /* (what the vector held before is replaced) */
+    featureDetectionGoodFeaturesToTrack(image, points);
+    return from_points(points, pts, cap);
 }
 
 /* One pass of the body of main()'s frame loop (main.cpp:144-208) through the reference's own functions:

@@ -2,10 +2,14 @@
 lie against a stand-in for the OpenCV declarations (oracle/ref_shim), with the OpenCV algorithms forwarding to the
 oracle's restatement.  These tests pin the oracle's RESTATED glue (oracle/orc_glue.c: call order of the four LK hops,
 deleteUnmatchFeaturesCircle's erase / age semantics, Bucket::add_feature, bucketingFeatures' aliased indexing and
-duplicate emission, appendNewFeatures) against the real sources on identical inputs.  OpenCV's own arithmetic is
+duplicate emission, appendNewFeatures) and the tests' own restatements (flow_cases.delete_unmatch_features; featureTracking and
+featureDetectionGoodFeaturesToTrack as checker call + restated glue) against the real sources on identical inputs.  OpenCV's own arithmetic is
 not part of what is pinned here (it is absent from the reference tree: parity of LK / FAST stays unpinned)."""
 import numpy as np
 import pytest
+
+import corners_emu as ce
+import flow_cases as fc
 
 
 @pytest.fixture(scope="module")
@@ -70,6 +74,79 @@ def test_append_new_features_equals_the_reference_source(ref, small_seq):
     assert len(fast) > 50
     assert np.array_equal(bits(p2), bits(np.vstack([carried, fast])))
     assert np.array_equal(a2, np.concatenate([ages, np.zeros(len(fast), np.int32)]))
+
+
+def _same_deletion(ref, p0, p1, st):
+    """flow_cases.delete_unmatch_features == the reference's deleteUnmatchFeatures on one input, bit for bit; returns the survivors"""
+    a0, a1, ast, keep = fc.delete_unmatch_features(p0, p1, st)
+    b0, b1, bst = ref.ref_delete_unmatch_features(p0, p1, st)
+    assert len(b0) == len(b1) == len(a0) == len(a1) == len(keep)
+    assert np.array_equal(bits(a0), bits(b0)) and np.array_equal(bits(a1), bits(b1))
+    assert ast.dtype == bst.dtype == np.uint8 and len(bst) == len(st) and np.array_equal(ast, bst)
+    return len(b0), bst
+
+
+def test_delete_unmatch_restatement_equals_the_reference_source(ref, small_seq):
+    """flow_cases.delete_unmatch_features is what every voflow_feature_tracking / vowin_feature_tracking test expects: here it
+    meets the function it restates (feature.cpp:20-37)"""
+    c = fc.case("L0-R0", small_seq, ref)
+    nxt, st, _ = c["want"]
+    left = (st == 1) & ((nxt[:, 0] < 0) | (nxt[:, 1] < 0))
+    assert len(st) == 596 and left.sum() >= 1 and (st == 0).sum() >= 20, "L0-R0: a tracked point that left the image, and lost ones"
+    m, out = _same_deletion(ref, c["pts"], nxt, st)
+    assert m == 596 - int(((st == 0) | left).sum()) and np.all(out[left] == 0)
+
+    nan, T, F = np.nan, 1, 0
+    #        0: first  1     2 3 4: a run (lost, x < 0, y < 0)        5: -0.0      6: NaN      7 (255)   8 9: a run           10     11: last
+    st = [F, T, F, T, T, T, T, 255, F, T, T, F]
+    p1 = [[-3, 5], [4, 4], [7, 7], [-1, 9], [9, -0.5], [-0.0, 6], [nan, 2], [3, 3], [nan, nan], [-2, -2], [8, 1], [5, 5]]
+    st, p1 = np.array(st, np.uint8), np.array(p1, np.float32)
+    p0 = np.arange(24, dtype=np.float32).reshape(12, 2) + 100
+    drop = (st == 0) | (p1[:, 0] < 0) | (p1[:, 1] < 0)
+    assert drop.tolist() == [1, 0, 1, 1, 1, 0, 0, 0, 1, 1, 0, 1]            # first and last dropped, runs of 3 and 2
+    assert st[3] == 1 and p1[3, 0] < 0 and p1[3, 1] >= 0 and st[4] == 1 and p1[4, 1] < 0 and p1[4, 0] >= 0   # status 1: x < 0; y < 0
+    assert st[5] == 1 and np.signbit(p1[5, 0]) and p1[5, 0] == 0 and st[6] == 1 and np.isnan(p1[6, 0])      # -0.0 and NaN: kept
+    m, out = _same_deletion(ref, p0, p1, st)
+    assert m == 12 - int(drop.sum()) == 5 and out.tolist() == [0, 1, 0, 0, 0, 1, 1, 255, 0, 0, 1, 0]
+    assert _same_deletion(ref, p0, p1, np.zeros(12, np.uint8))[0] == 0                                       # all dropped ...
+    assert _same_deletion(ref, p0, np.full((12, 2), -1, np.float32), np.ones(12, np.uint8))[0] == 0          # ... by either rule
+    assert _same_deletion(ref, p0, np.abs(np.nan_to_num(p1)), np.ones(12, np.uint8))[0] == 12                # none dropped
+    assert _same_deletion(ref, p0[:0], p1[:0], st[:0])[0] == 0                                               # n = 0
+    assert _same_deletion(ref, p0[:1], p1[:1], st[:1])[0] == 0 and _same_deletion(ref, p0[1:2], p1[1:2], st[1:2])[0] == 1
+
+
+@pytest.mark.parametrize("name", ["L0-L1", "L0-R0"])
+def test_feature_tracking_equals_the_reference_source(ref, small_seq, name):
+    """featureTracking (feature.cpp:64-74) compiled where it lies == calcOpticalFlowPyrLK(21 x 21, maxLevel 3) of the checker +
+    the restated deleteUnmatchFeatures: what featureTracking_hip is held to on the device"""
+    c = fc.case(name, small_seq, ref)
+    fc.assert_not_vacuous(name, c)
+    nxt, st, _ = c["want"]
+    w0, w1, wst, keep = fc.delete_unmatch_features(c["pts"], nxt, st)
+    assert 500 <= len(keep) < (st == 1).sum() <= 596 - 20, "lost points, and tracked points that left the image"
+    g0, g1, gst = ref.ref_feature_tracking(c["prev"], c["next"], c["pts"])
+    assert len(g0) == len(g1) == len(keep) and len(gst) == 596
+    assert np.array_equal(bits(g0), bits(w0)) and np.array_equal(bits(g1), bits(w1)) and np.array_equal(gst, wst)
+    e0, e1, est = ref.ref_feature_tracking(c["prev"], c["next"], c["pts"][:0])
+    assert len(e0) == len(e1) == len(est) == 0
+
+
+def test_feature_detection_gftt_equals_the_reference_source(ref, small_seq):
+    """featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) compiled where it lies == corners_ref.c's cr_detect at the
+    reference's literals 5000 / 0.01 / 5.0: on a frame the limit leaves alone, and on one it cuts (5 pixels apart, 480 x 160
+    cannot hold 5000 corners: the noise image is 640 x 480)"""
+    for img, binds in ((small_seq["L"][0], False), (ce.noise(640, 480, 21), True)):
+        want, n, _ = ce.ref_detect(img, 5000, 0.01, 5.0)
+        unlimited = ce.ref_detect(img, 0, 0.01, 5.0)[1]
+        assert (unlimited > 5000 and n == 5000) if binds else (100 < unlimited == n < 5000), (unlimited, n)
+        got, m = ref.ref_feature_detection_gftt(img)
+        assert m == n == len(got) and np.array_equal(bits(got), bits(want))
+        few, m = ref.ref_feature_detection_gftt(img, cap=7)
+        assert m == n and np.array_equal(bits(few), bits(want[:7]))
+    img = ce.noise(131, 67, 3)
+    want, n, _ = ce.ref_detect(img, 5000, 0.01, 5.0)
+    got, m = ref.ref_feature_detection_gftt(ce.strided(img, 131 + 29)[:, :131])     # rows 160 bytes apart, 0xEE between them
+    assert m == n > 50 and np.array_equal(bits(got), bits(want))
 
 
 def _oracle_chain_step(orc, state, l0, r0, l1, r1, P_l, P_r, K, mono=False):
