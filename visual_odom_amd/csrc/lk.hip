@@ -25,7 +25,8 @@
 //   bilinear sample from VERTICAL pixel pairs (t[k], b[k]) against the weights packed by column: each
 //   column is lifted once (8 v_perm_b32 per cell, where horizontal pairs took 14; profiles/r07_lk_vertical_pairs.md).
 //   Reductions: v_permlane32/16_swap + v_add_u32_dpp butterflies, two sums per tree (vo_dev.h
-//   wave_sum2_exact_f32), no LDS round trips.
+//   wave_sum2_exact_f32), no LDS round trips.  A level whose structure tensor says that b1, b2 fit 32 bits (lk_sums_fit,
+//   vo_lkmath.h) sums them in one tree of wrapping 32-bit adds instead (wave_sum2_f32; profiles/r11_lk_fit_sums.md).
 // Grid: blocks are numbered so that (dispatcher: block b -> XCD b % 8) all features of one frame
 // run on ONE XCD, i.e. the frame's four pyramids are pulled into one L2 only, eight frames at a time.
 // Batches of fewer than 8 frames split each frame's feature list into contiguous parts over 8/fpg XCDs.
@@ -47,6 +48,14 @@
 #include <type_traits>
 
 namespace vo {
+
+#ifdef VO_HOST_EMUL
+// (the CPU emulator only) iterations run per pyramid level with the 32-bit sums [level][1] and with the split ones [level][0]
+inline long long g_lk_fit_iterations[VO_MAX_LEVELS][2];
+#define VO_LK_COUNT_FIT(level, fit) ((void)(threadIdx.x == 0 ? ++g_lk_fit_iterations[level][(fit) ? 1 : 0] : 0))
+#else
+#define VO_LK_COUNT_FIT(level, fit) ((void)0)
+#endif
 
 constexpr int LK_WIN = 21; // the window of the chain kernels and of lk_flow_kernel; lk_flow_win_kernel<W>: odd W of 5 .. 19
 constexpr int LK_JT_W = 48, LK_JT_H = 40; // search tile (bytes x rows), LDS row stride = LK_JT_W
@@ -398,6 +407,9 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             }
             float A11, A12, A22;
             wave_sum3_exact_f32(a11, a12, a22, A11, A12, A22);
+            // can b1, b2 of this level's iterations exceed 32 bits (vo_lkmath.h)?  Wave-uniform, from the two sums as they come out
+            // of v_readlane -- scalar registers --, before the 2^-20
+            const bool fit = lk_sums_fit(A11, A22);
             A11 *= FLT_SCALE;
             A12 *= FLT_SCALE;
             A22 *= FLT_SCALE;
@@ -527,7 +539,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     }
                 }
                 float fb1, fb2;
-                wave_sum2_exact_f32(b1, b2, fb1, fb2);
+                VO_LK_COUNT_FIT(level, fit);
+                wave_sum2_f32(b1, b2, fit, fb1, fb2); // (the level's word: 10 VALU instructions where the sums fit, else 15)
                 dx = (A12s * fb2 - A22s * fb1) * D;
                 dy = (A12s * fb1 - A11s * fb2) * D;
                 nextX += dx;

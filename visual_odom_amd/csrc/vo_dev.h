@@ -214,12 +214,21 @@ __device__ __forceinline__ float wave_sum_exact_f32(int v)
 //   them (row_bcast15) and fuse high * 2^16 + low with ONE rounding = (float)(int64 sum), what the CPU
 //   path computes; two v_readlane return the results.
 // 15 VALU instructions for two sums instead of 2 x 16 with wave_sum_exact_f32.
-__device__ __forceinline__ void wave_sum2_exact_f32(int a, int b, float &fa, float &fb)
+// (head and tail are separate functions for wave_sum2_f32 below, whose two trees share the head)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_add_wrap(int v) // dpp_add modulo 2^32: for sums that are meant to wrap (wave_sum2_fit_f32)
+{
+    return (int)((uint32_t)v + (uint32_t)VO_UPDATE_DPP(0, v, CTRL, ROW_MASK, 0xf, true));
+}
+__device__ __forceinline__ int wave_sum2_quads(int a, int b)
 {
     VO_PERMLANE32_SWAP(a, b);
-    int t = a + b;
-    t = dpp_add<VO_DPP_QUAD_XOR1, 0xf>(t);
-    t = dpp_add<VO_DPP_QUAD_XOR2, 0xf>(t);
+    int t = (int)((uint32_t)a + (uint32_t)b);
+    t = dpp_add_wrap<VO_DPP_QUAD_XOR1, 0xf>(t);
+    return dpp_add_wrap<VO_DPP_QUAD_XOR2, 0xf>(t);
+}
+__device__ __forceinline__ void wave_sum2_exact_tail(int t, float &fa, float &fb)
+{
     int hi = t >> 16, lo = t & 0xffff;
     VO_PERMLANE16_SWAP(hi, lo);
     int u = hi + lo;
@@ -231,6 +240,45 @@ __device__ __forceinline__ void wave_sum2_exact_f32(int a, int b, float &fa, flo
     const float res = fmaf(up, 65536.f, uf);
     fa = __int_as_float(VO_READLANE(__float_as_int(res), 31));
     fb = __int_as_float(VO_READLANE(__float_as_int(res), 63));
+}
+__device__ __forceinline__ void wave_sum2_exact_f32(int a, int b, float &fa, float &fb)
+{
+    wave_sum2_exact_tail(wave_sum2_quads(a, b), fa, fb);
+}
+
+// The same two sums where each TOTAL is known to fit 32 bits: one tree of plain 32-bit adds, no halves.
+//   Precondition: |sum a| < 2^31 and |sum b| < 2^31 over the 64 lanes.  The lane values are arbitrary int32 and every partial sum
+//   may wrap: the adds are modulo 2^32, so the last one leaves total mod 2^32, which IS the total when it fits, and one
+//   v_cvt_f32_i32 rounds it once = (float)(int64 sum), bit for bit what wave_sum2_exact_f32 returns where both apply.  (lk.hip
+//   knows the precondition per level from the structure tensor: vo_lkmath.h, lk_sums_fit.)
+//   v_permlane32_swap(a, b); t = a + b      lanes 0-31: a[l] + a[l+32], lanes 32-63: the same of b
+//   quad xor 1, quad xor 2, row_half_mirror, row_mirror (4 DPP adds): every lane of a row holds the row's sum, rows 0 and 1 of
+//                                           a's values, rows 2 and 3 of b's
+//   row_bcast:15 into rows 1 and 3 (1 DPP add): lanes 16-31 hold a's total, lanes 48-63 b's
+//   v_cvt_f32_i32, two v_readlane.
+// 10 VALU instructions for 15.
+__device__ __forceinline__ void wave_sum2_fit_tail(int t, float &fa, float &fb)
+{
+    t = dpp_add_wrap<VO_DPP_ROW_HALF_MIRROR, 0xf>(t);
+    t = dpp_add_wrap<VO_DPP_ROW_MIRROR, 0xf>(t);
+    t = dpp_add_wrap<VO_DPP_ROW_BCAST15, 0xa>(t);
+    const float tf = (float)t;
+    fa = __int_as_float(VO_READLANE(__float_as_int(tf), 31));
+    fb = __int_as_float(VO_READLANE(__float_as_int(tf), 63));
+}
+__device__ __forceinline__ void wave_sum2_fit_f32(int a, int b, float &fa, float &fb)
+{
+    wave_sum2_fit_tail(wave_sum2_quads(a, b), fa, fb);
+}
+// wave_sum2_fit_f32 if `fit` (wave-uniform: the caller's word that the precondition holds), else wave_sum2_exact_f32: the four
+// instructions the two begin with, then a branch to one of the tails
+__device__ __forceinline__ void wave_sum2_f32(int a, int b, bool fit, float &fa, float &fb)
+{
+    const int t = wave_sum2_quads(a, b);
+    if (fit)
+        wave_sum2_fit_tail(t, fa, fb);
+    else
+        wave_sum2_exact_tail(t, fa, fb);
 }
 
 // Three exact sums (the structure tensor A11, A12, A22) in one tree: two half-swaps fold a|b and c|(unread) into two

@@ -206,6 +206,32 @@ VO_HD void bilinear7_deriv_cols(const uint32_t dt[8], const uint32_t db[8], uint
     }
 }
 
+// ---- do the iteration's two sums fit 32 bits? -------------------------------------------------------
+// b1 = sum (Jp - Ip) * Ixp and b2 = sum (Jp - Ip) * Iyp over the window can reach 2^34 in general, which is what
+// wave_sum2_exact_f32's two halves are for.  For most templates they cannot, and the level's structure tensor says so:
+//   * Jp and Ip are DESCALE(sum of p * iw, 9) of pixels p in [0, 255] under weights that sum to 2^14, three of them >= 0 and
+//     iw11 >= -1: both lie in [0, 8160] (iw11 = -1: at most (255 * (2^14 + 1) + 256) >> 9 = 8160, at least (-255 + 256) >> 9 = 0),
+//     so |Jp - Ip| <= 8160 < 2^13 whatever J holds;
+//   * Cauchy-Schwarz over the n <= 441 pixels of the window: sum |Ixp| <= sqrt(n * sum Ixp^2) = sqrt(n * A11raw);
+//   * hence |b1| <= 2^13 * 21 * sqrt(A11raw), which is < 2^31 for A11raw < (2^18 / 21)^2 = 1.558e8 (1.569e8 with 8160).
+// A11raw, A22raw: the exact integer sums of wave_sum3_exact_f32 rounded once to f32 (relative error 2^-24), BEFORE the 2^-20
+// of FLT_SCALE.  The threshold 1.5e8 leaves 3.7 % for that rounding and holds for every window of 21 x 21 and below (a smaller n
+// only lowers the bound).  Written on the bit patterns -- non-negative floats order like their bits, a negative value or a NaN
+// reads as "does not fit" -- so that on the device, where both sums sit in scalar registers, the test is s_max_u32 + s_cmp_lt_u32.
+constexpr float LK_FIT_RAW_MAX = 1.5e8f;
+constexpr uint32_t LK_FIT_RAW_MAX_BITS = 0x4D0F0D18u; // of 1.5e8f (tests/host_check/lk_fit_host.cpp holds the two together)
+VO_HD uint32_t f32_bits(float v)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &v, 4);
+    return u;
+}
+VO_HD bool lk_sums_fit(float a11_raw, float a22_raw)
+{
+    const uint32_t u = f32_bits(a11_raw), v = f32_bits(a22_raw);
+    return (u > v ? u : v) < LK_FIT_RAW_MAX_BITS;
+}
+
 // Scharr 3x3 (cv::calcSharrDeriv) of the centre pixel of a 3x3 patch, stored pre-multiplied by 4
 VO_HD uint32_t scharr4_packed(int p00, int p01, int p02, int p10, int p12, int p20, int p21, int p22)
 {
