@@ -26,7 +26,8 @@
 //   column is lifted once (8 v_perm_b32 per cell, where horizontal pairs took 14; profiles/r07_lk_vertical_pairs.md).
 //   Reductions: v_permlane32/16_swap + v_add_u32_dpp butterflies, two sums per tree (vo_dev.h
 //   wave_sum2_exact_f32), no LDS round trips.  A level whose structure tensor says that b1, b2 fit 32 bits (lk_sums_fit,
-//   vo_lkmath.h) sums them in one tree of wrapping 32-bit adds instead (wave_sum2_f32; profiles/r11_lk_fit_sums.md).
+//   vo_lkmath.h) sums them in one tree of wrapping 32-bit adds instead (wave_sum2_f32; profiles/r11_lk_fit_sums.md); the level's
+//   iteration loop exists once per kind of sum, chosen once per level (profiles/r12_lk_iteration_branches.md).
 // Grid: blocks are numbered so that (dispatcher: block b -> XCD b % 8) all features of one frame
 // run on ONE XCD, i.e. the frame's four pyramids are pulled into one L2 only, eight frames at a time.
 // Batches of fewer than 8 frames split each frame's feature list into contiguous parts over 8/fpg XCDs.
@@ -53,13 +54,16 @@ namespace vo {
 // (the CPU emulator only) iterations run per pyramid level with the 32-bit sums [level][1] and with the split ones [level][0]
 inline long long g_lk_fit_iterations[VO_MAX_LEVELS][2];
 #define VO_LK_COUNT_FIT(level, fit) ((void)(threadIdx.x == 0 ? ++g_lk_fit_iterations[level][(fit) ? 1 : 0] : 0))
+// (the same) iterations that sampled the search window with iw11 = -1, the rare case of blend7_cols (vo_lkmath.h)
+inline long long g_lk_neg_iterations;
+#define VO_LK_COUNT_NEG(neg) ((void)(threadIdx.x == 0 && (neg) ? ++g_lk_neg_iterations : 0))
 #else
 #define VO_LK_COUNT_FIT(level, fit) ((void)0)
+#define VO_LK_COUNT_NEG(neg) ((void)0)
 #endif
 
 constexpr int LK_WIN = 21; // the window of the chain kernels and of lk_flow_kernel; lk_flow_win_kernel<W>: odd W of 5 .. 19
 constexpr int LK_JT_W = 48, LK_JT_H = 40; // search tile (bytes x rows), LDS row stride = LK_JT_W
-constexpr int LK_W_BITS = 14;
 // A W x W window on the wavefront: a row is cut into SEGS 7-pixel segments, lane -> (row = lane / SEGS, segment = lane % SEGS),
 // W * SEGS lanes own pixels (63 for W = 21, at most 57 below).  A lane always reads the 8 columns of its segment, so a row of
 // the window reads COLS = 7 * SEGS + 1 columns -- W + 1 only where 7 divides W -- and the last segment of a row holds
@@ -78,42 +82,7 @@ constexpr uint32_t lk_seg_mask(int valid, int m)
     return (2 * m < valid ? 0x0000ffffu : 0u) | (2 * m + 1 < valid ? 0xffff0000u : 0u);
 }
 
-// 14-bit fixed-point bilinear weights of OpenCV's LKTrackerInvoker from the fractional parts of the
-// window corner: iw00 = cvRound((1-a)*(1-b)*2^14), iw01 = cvRound(a*(1-b)*2^14), iw10 = cvRound((1-a)*b*2^14),
-// iw11 = 2^14 - iw00 - iw01 - iw10, returned as packed int16 pairs: by row, wt = (iw00, iw01), wb = (iw10, iw11)
-// (lk_weights: the samplers over horizontal pixel pairs), or by column, wl = (iw00, iw10), wr = (iw01, iw11)
-// (lk_weights_cols: the samplers over vertical pairs, vo_lkmath.h) -- the two differ in the packing selectors' operands only.
-//   * the scale is folded in exactly (a power of two, see below);
-//   * cvRound (round half to even) = adding 1.5 * 2^23: the f32 sum has ulp 1, so the add rounds the
-//     product to the nearest-even integer and leaves it in the low mantissa bits.  The raw bit patterns
-//     are packed / summed directly (0x4B400000 has no low 16 bits), no v_rndne / v_cvt per weight.
-template <bool COLS>
-__device__ __forceinline__ void lk_weights_packed(float a, float b, uint32_t &w0, uint32_t &w1)
-{
-    const float s = (float)(1 << LK_W_BITS), magic = 12582912.f; // 1.5 * 2^23 = 0x4B400000
-    // Written on pairs, the way the packed f32 instructions take them: (a1, b1) = 1 - (a, b) is one subtraction, (a1 * b, b1 * a)
-    // one multiply of that pair with the swapped one.  The scale moves behind the product -- a power of two goes through a
-    // rounded product unchanged, fl((a1 * s) * b1) == fl(a1 * b1) * s, and where the product underflows both forms vanish in the
-    // sum -- so "* s + magic" is one fused multiply-add with an exact product: one rounding, the one the add always had.
-    typedef float F32x2 __attribute__((vector_size(8)));
-    const F32x2 p = {a, b}, q = 1.f - p, pswap = {b, a};
-    const F32x2 x = q * pswap; // (a1 * b, b1 * a)
-    const uint32_t r00 = (uint32_t)__float_as_int(fmaf(q[0] * q[1], s, magic));
-    const uint32_t r01 = (uint32_t)__float_as_int(fmaf(x[1], s, magic));
-    const uint32_t r10 = (uint32_t)__float_as_int(fmaf(x[0], s, magic));
-    // iw11 = 2^14 - (r00 + r01 + r10 - 3 * 0x4B400000)   (mod 2^32)
-    const uint32_t iw11 = ((1u << LK_W_BITS) + 3u * 0x4B400000u) - (r00 + r01 + r10);
-    w0 = perm_b32(COLS ? r10 : r01, r00, VO_SEL_LO16);
-    w1 = perm_b32(iw11, COLS ? r01 : r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
-}
-__device__ __forceinline__ void lk_weights(float a, float b, uint32_t &wt, uint32_t &wb)
-{
-    lk_weights_packed<false>(a, b, wt, wb);
-}
-__device__ __forceinline__ void lk_weights_cols(float a, float b, uint32_t &wl, uint32_t &wr)
-{
-    lk_weights_packed<true>(a, b, wl, wr);
-}
+// (the 14-bit fixed-point bilinear weights, lk_weights / lk_weights_cols: vo_lkmath.h)
 
 // ---- the search tile: LK_JT_H rows of LK_JT_W bytes of J in LDS, origin (jx0, jy0) -------------------------------------
 // The helpers take and return the origin BY VALUE: a local whose address goes into a call stays in memory until the call is
@@ -479,16 +448,15 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // that (like the columns below: no moves per level to zero what the first cell overwrites)
             float fnx, fny, frx, fry;
 #ifndef VO_HOST_EMUL
-            asm volatile("" : "=v"(fnx), "=v"(fny), "=v"(frx), "=v"(fry));
+            asm volatile("" : "=v"(fnx), "=v"(fny));
 #else
             fnx = fny = frx = fry = 0.f;
 #endif
             // the cell's columns (two window rows per lane) as vertical pixel pairs: eight scalars, not an array -- an array carried
             // round the loop becomes one 8-register tuple, copied at every cell entry -- and set by nothing before the first cell
+            // (the device's "set by nothing" stands at the top of each version of the loop, below)
             uint32_t J0, J1, J2, J3, J4, J5, J6, J7;
-#ifndef VO_HOST_EMUL
-            asm volatile("" : "=v"(J0), "=v"(J1), "=v"(J2), "=v"(J3), "=v"(J4), "=v"(J5), "=v"(J6), "=v"(J7));
-#else
+#ifdef VO_HOST_EMUL
             J0 = J1 = J2 = J3 = J4 = J5 = J6 = J7 = 0;
 #endif
             int inx = 0, iny = 0;
@@ -523,13 +491,19 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
             // re-enters the same cell.  As raw bits, [0, 1) is "below 0x3f800000, unsigned" (negative values have the
             // sign bit set), so one unsigned max + one compare replace two floors, two compares and two selects per
             // iteration; the two differences of that test are the next iteration's weight inputs.
-            auto iterate = [&](const float px, const float py, float &dx, float &dy, const int osc) -> int {
+            // `fitc` (std::true_type / std::false_type): the level's word on its sums, as a type -- the loop below exists once per value
+            auto iterate = [&](auto fitc, const float px, const float py, float &dx, float &dy, const int osc) -> int {
+                constexpr bool FIT = decltype(fitc)::value;
                 lk_weights_cols(frx, fry, wl, wr);
                 int b1, b2;
                 {
                     const uint32_t Jc[8] = {J0, J1, J2, J3, J4, J5, J6, J7};
                     uint32_t Jp[4];
-                    blend7_cols(Jc, wl, wr, Jp);
+                    // iw11 = -1 (the sign of wr, the same in every lane) through a scalar: a branch of the wave, not a region
+                    // that rewrites the execution mask around a case that almost never occurs
+                    const bool neg = uni((int)wr) < 0;
+                    VO_LK_COUNT_NEG(neg);
+                    blend7_cols(Jc, wl, wr, neg, Jp);
                     b1 = sdot2_first(Jp[0], Ixp[0], nc1); // seeds: minus the lane's sum I * Ix, sum I * Iy
                     b2 = sdot2_first(Jp[0], Iyp[0], nc2);
 #pragma unroll
@@ -539,8 +513,8 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     }
                 }
                 float fb1, fb2;
-                VO_LK_COUNT_FIT(level, fit);
-                wave_sum2_f32(b1, b2, fit, fb1, fb2); // (the level's word: 10 VALU instructions where the sums fit, else 15)
+                VO_LK_COUNT_FIT(level, FIT);
+                wave_sum2_f32<FIT>(b1, b2, fb1, fb2); // (10 VALU instructions where the sums fit, else 15)
                 dx = (A12s * fb2 - A22s * fb1) * D;
                 dy = (A12s * fb1 - A11s * fb2) * D;
                 nextX += dx;
@@ -578,17 +552,41 @@ __device__ __forceinline__ void lk_circular_body(const PyrImage *__restrict__ im
                     st = 0;
                 run = false;
             }
-            if (run)
+            // The loop, once for each kind of sum and chosen once per level: `fit` is the same for every iteration of the level, and
+            // as a value tested inside the iteration it cost two scalar branches and a mask in a scalar pair in each of them
+            // (profiles/r12_lk_iteration_branches.md).  Returns how the loop was left.
+            auto solve = [&](auto fitc) -> int {
+                // The region is compiled with a path from the first loop into the second, so what enters the second loop lives
+                // through the first.  The corner and its floors would: four registers the chain kernels do not have.  They are formed
+                // again per version instead, from `out`, which the loops leave alone -- the same operations on the same values as in
+                // front of the loop, with the constant through a scalar the compiler does not see through, or it takes the results
+                // it has.  (A scalar: an opaque vector register counts as a value per lane, and `st` and the hop's start point, which
+                // depend on the corner, then move from scalar registers into vector ones.)
+                int hw = __float_as_int(halfWin);
+#ifndef VO_HOST_EMUL
+                asm volatile("" : "+s"(hw));
+                // what the first cell overwrites, undefined per version: defined once in front of both, the two loops get a set of
+                // registers each and a copy of every one at their entry
+                asm volatile("" : "=v"(frx), "=v"(fry));
+                asm volatile("" : "=v"(J0), "=v"(J1), "=v"(J2), "=v"(J3), "=v"(J4), "=v"(J5), "=v"(J6), "=v"(J7));
+#endif
+                nextX = outX - __int_as_float(hw);
+                nextY = outY - __int_as_float(hw);
+                fnx = floorf(nextX);
+                fny = floorf(nextY);
                 for (;;) {
                     if (cell)
                         enter_cell();
-                    if ((left = iterate(dBx, dBy, dAx, dAy, 2)) != 0)
-                        break;
+                    if (const int l = iterate(fitc, dBx, dBy, dAx, dAy, 2))
+                        return l;
                     if (cell)
                         enter_cell();
-                    if ((left = iterate(dAx, dAy, dBx, dBy, 3)) != 0)
-                        break;
+                    if (const int l = iterate(fitc, dAx, dAy, dBx, dBy, 3))
+                        return l;
                 }
+            };
+            if (run)
+                left = fit ? solve(std::true_type{}) : solve(std::false_type{});
             if (left == 4 && level == 0) // the corner left the image behind an iteration
                 st = 0;
             // out = next + halfWin, read only here; the rounding order of the half step is (next + halfWin) - d * 0.5

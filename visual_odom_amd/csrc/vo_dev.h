@@ -270,8 +270,19 @@ __device__ __forceinline__ void wave_sum2_fit_f32(int a, int b, float &fa, float
 {
     wave_sum2_fit_tail(wave_sum2_quads(a, b), fa, fb);
 }
-// wave_sum2_fit_f32 if `fit` (wave-uniform: the caller's word that the precondition holds), else wave_sum2_exact_f32: the four
-// instructions the two begin with, then a branch to one of the tails
+// wave_sum2_fit_f32 if FIT (the caller's word that the precondition holds), else wave_sum2_exact_f32, chosen where the code is
+// compiled: the four instructions the two begin with and ONE of the tails, no branch.  lk.hip's iteration loop exists once per
+// value (profiles/r12_lk_iteration_branches.md).
+template <bool FIT>
+__device__ __forceinline__ void wave_sum2_f32(int a, int b, float &fa, float &fb)
+{
+    const int t = wave_sum2_quads(a, b);
+    if constexpr (FIT)
+        wave_sum2_fit_tail(t, fa, fb);
+    else
+        wave_sum2_exact_tail(t, fa, fb);
+}
+// The same with `fit` as a wave-uniform value: the shared head, then a branch to one of the tails
 __device__ __forceinline__ void wave_sum2_f32(int a, int b, bool fit, float &fa, float &fb)
 {
     const int t = wave_sum2_quads(a, b);

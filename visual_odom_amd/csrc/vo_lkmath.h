@@ -27,7 +27,16 @@
 
 #include "vo_isa.h" // the instruction wrappers (device: the CDNA4 instruction; host: its definition) and VO_HD
 
+#include <math.h>
+
 namespace vo {
+
+VO_HD uint32_t f32_bits(float v)
+{
+    uint32_t u;
+    __builtin_memcpy(&u, &v, 4);
+    return u;
+}
 
 // ---- selectors ------------------------------------------------------------------------------------
 // bytes k and k+1 of the 8 loaded bytes into the high byte of the two u16 lanes (256*p[k], 256*p[k+1])
@@ -43,6 +52,58 @@ VO_HD uint32_t pack_w(int w_lo, int w_hi)
 #else
     return (uint32_t)(w_lo & 0xffff) | ((uint32_t)w_hi << 16);
 #endif
+}
+
+// ---- the bilinear weights ------------------------------------------------------------------------
+// 14-bit fixed-point bilinear weights of OpenCV's LKTrackerInvoker from the fractional parts of the
+// window corner: iw00 = cvRound((1-a)*(1-b)*2^14), iw01 = cvRound(a*(1-b)*2^14), iw10 = cvRound((1-a)*b*2^14),
+// iw11 = 2^14 - iw00 - iw01 - iw10, returned as packed int16 pairs: by row, wt = (iw00, iw01), wb = (iw10, iw11)
+// (lk_weights: the samplers over horizontal pixel pairs), or by column, wl = (iw00, iw10), wr = (iw01, iw11)
+// (lk_weights_cols: the samplers over vertical pairs below) -- the two differ in the packing selectors' operands only.
+//   * the scale is folded in exactly (a power of two, see below);
+//   * cvRound (round half to even) = adding 1.5 * 2^23: the f32 sum has ulp 1, so the add rounds the
+//     product to the nearest-even integer and leaves it in the low mantissa bits.  The raw bit patterns
+//     are packed / summed directly (0x4B400000 has no low 16 bits), no v_rndne / v_cvt per weight.
+constexpr int LK_W_BITS = 14;
+// x * s + m on both lanes with ONE rounding each: v_pk_fma_f32
+typedef float F32x2 __attribute__((vector_size(8)));
+VO_HD F32x2 pk_fma_f32(F32x2 x, float s, float m)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const F32x2 sv = {s, s}, mv = {m, m};
+    return __builtin_elementwise_fma(x, sv, mv);
+#else
+    const F32x2 r = {fmaf(x[0], s, m), fmaf(x[1], s, m)};
+    return r;
+#endif
+}
+template <bool COLS>
+VO_HD void lk_weights_packed(float a, float b, uint32_t &w0, uint32_t &w1)
+{
+    const float s = (float)(1 << LK_W_BITS), magic = 12582912.f; // 1.5 * 2^23 = 0x4B400000
+    // Written on pairs, the way the packed f32 instructions take them: (a1, b1) = 1 - (a, b) is one subtraction, (a * b1, b * a1)
+    // one multiply of the pair with the swapped one, and that pair goes into the packed scale-and-round AS IT IS -- (iw01, iw10) --
+    // beside a plain multiply for a1 * b1.  (Pairing a1 * b1 with one of the two put a register copy between the multiplies and
+    // the fused multiply-add, profiles/r12_lk_iteration_branches.md; the three products, their operands and their roundings are
+    // what they were.)  The scale moves behind the product -- a power of two goes through a
+    // rounded product unchanged, fl((a1 * s) * b1) == fl(a1 * b1) * s, and where the product underflows both forms vanish in the
+    // sum -- so "* s + magic" is one fused multiply-add with an exact product: one rounding, the one the add always had.
+    const F32x2 p = {a, b}, q = 1.f - p, qswap = {q[1], q[0]};
+    const F32x2 r = pk_fma_f32(p * qswap, s, magic); // of (a * b1, b * a1)
+    const uint32_t r00 = f32_bits(fmaf(q[0] * q[1], s, magic));
+    const uint32_t r01 = f32_bits(r[0]), r10 = f32_bits(r[1]);
+    // iw11 = 2^14 - (r00 + r01 + r10 - 3 * 0x4B400000)   (mod 2^32)
+    const uint32_t iw11 = ((1u << LK_W_BITS) + 3u * 0x4B400000u) - (r00 + r01 + r10);
+    w0 = perm_b32(COLS ? r10 : r01, r00, VO_SEL_LO16);
+    w1 = perm_b32(iw11, COLS ? r01 : r10, VO_SEL_LO16); // signed lanes: iw11 may be -1
+}
+VO_HD void lk_weights(float a, float b, uint32_t &wt, uint32_t &wb)
+{
+    lk_weights_packed<false>(a, b, wt, wb);
+}
+VO_HD void lk_weights_cols(float a, float b, uint32_t &wl, uint32_t &wr)
+{
+    lk_weights_packed<true>(a, b, wl, wr);
 }
 
 // ---- one 7-pixel row segment ----------------------------------------------------------------------
@@ -129,7 +190,7 @@ VO_HD void lift8_cols(uint32_t t_lo, uint32_t t_hi, uint32_t b_lo, uint32_t b_hi
 // zeroes the weight and subtracts |iw11| * 256*b[k+1], the high lane of column k + 1.
 VO_HD void blend7_cols(const uint32_t col[8], uint32_t wl, uint32_t wr, uint32_t out[4])
 {
-    uint32_t acc[8];
+    uint32_t acc[7];
     if (!(wr & 0x80000000u)) {
 #pragma unroll
         for (int k = 0; k < 7; k++)
@@ -147,10 +208,46 @@ VO_HD void blend7_cols(const uint32_t col[8], uint32_t wl, uint32_t wr, uint32_t
             acc[k] = udot2(c, wr0, udot2(col[k], wl, 1u << 16)) - kneg * (c >> 16);
         }
     }
-    acc[7] = 0;
 #pragma unroll
-    for (int m = 0; m < 4; m++)
+    for (int m = 0; m < 3; m++)
         out[m] = pk_lshr1_u16(perm_b32(acc[2 * m + 1], acc[2 * m], VO_SEL_HI16));
+    // (val[6], 0): the high half of acc[6], shifted once more, is the whole word shifted right by 17 -- one instruction for two, and
+    // no selector beside a zero, which the compiler keeps in a vector register of its own for the whole kernel
+    out[3] = acc[6] >> 17;
+}
+
+// The same for a caller that knows the sign of iw11 as a wave-uniform value (`neg`; lk.hip's iteration reads it off the packed
+// weight through v_readfirstlane_b32): one scalar compare-and-branch, where the test of `wr` -- a value per lane -- is compiled as
+// a divergent region that saves, rewrites and restores the execution mask in every call although all lanes agree.  The first
+// links of the seven chains do not depend on the case and stand in front of the branch; the rare case is kept out of line.
+VO_HD void blend7_cols(const uint32_t col[8], uint32_t wl, uint32_t wr, bool neg, uint32_t out[4])
+{
+    uint32_t acc[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++)
+        acc[k] = udot2(col[k], wl, 1u << 16);
+    if (__builtin_expect(neg, 0)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" ::: "memory"); // keep the rare case out of the common path
+#endif
+        const uint32_t wr0 = wr & 0xffffu, kneg = (uint32_t)(-(int32_t)((int16_t)(wr >> 16)));
+#pragma unroll
+        for (int k = 0; k < 7; k++) {
+            uint32_t c = col[k + 1];
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" : "+v"(c)); // (as above: the shift stays in the rare case)
+#endif
+            acc[k] = udot2(c, wr0, acc[k]) - kneg * (c >> 16);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 7; k++)
+            acc[k] = udot2(col[k + 1], wr, acc[k]);
+    }
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+        out[m] = pk_lshr1_u16(perm_b32(acc[2 * m + 1], acc[2 * m], VO_SEL_HI16));
+    out[3] = acc[6] >> 17; // (val[6], 0): the high half of acc[6], shifted once more, is the whole word shifted -- no selector
 }
 
 VO_HD void bilinear7_u8_cols(uint32_t t_lo, uint32_t t_hi, uint32_t b_lo, uint32_t b_hi, uint32_t wl, uint32_t wr,
@@ -220,12 +317,6 @@ VO_HD void bilinear7_deriv_cols(const uint32_t dt[8], const uint32_t db[8], uint
 // reads as "does not fit" -- so that on the device, where both sums sit in scalar registers, the test is s_max_u32 + s_cmp_lt_u32.
 constexpr float LK_FIT_RAW_MAX = 1.5e8f;
 constexpr uint32_t LK_FIT_RAW_MAX_BITS = 0x4D0F0D18u; // of 1.5e8f (tests/host_check/lk_fit_host.cpp holds the two together)
-VO_HD uint32_t f32_bits(float v)
-{
-    uint32_t u;
-    __builtin_memcpy(&u, &v, 4);
-    return u;
-}
 VO_HD bool lk_sums_fit(float a11_raw, float a22_raw)
 {
     const uint32_t u = f32_bits(a11_raw), v = f32_bits(a22_raw);
