@@ -21,6 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import corners_emu as ce  # noqa: E402
 import corners_mask_cases as cm  # noqa: E402
+from corners_scale import tiles  # noqa: E402  (the 3 x 3 plateau pattern, shared with the detector's scale cases)
 import flow_cases as fc  # noqa: E402
 import flow_win_cases as wc  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
@@ -54,16 +55,6 @@ def padded(imgs, pad_x=37, pad_y=9, fill=200):
     oy, ox = pad_y // 2, pad_x // 3
     big[:, oy:oy + h, ox:ox + w] = np.stack(imgs)
     return [big[i, oy:oy + h, ox:ox + w] for i in range(len(imgs))]
-
-
-def tiles(w, h, cols=None):
-    """a 3 x 3 tile repeated over the first `cols` columns (default: all), flat beyond: the 3 x 3 box sums of a pattern of period 3
-    are the same at every pixel, so the quality map is one exact plateau there and every interior pixel of it is a candidate"""
-    tile = np.random.default_rng(1).integers(0, 256, (3, 3), dtype=np.uint8)
-    img = np.full((h, w), 128, np.uint8)
-    cols = w if cols is None else cols
-    img[:, :cols] = np.tile(tile, (h // 3 + 1, w // 3 + 1))[:h, :cols]
-    return img
 
 
 def _img(a):
