@@ -151,6 +151,36 @@ void goodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points, in
     points.swap(out);
 }
 
+void goodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points, int maxCorners, double qualityLevel, double minDistance, cv::Mat mask,
+                             int blockSize, bool useHarrisDetector, double k)
+{
+    if (image.type() != CV_8UC1)
+        throw std::runtime_error("goodFeaturesToTrack_hip: an 8-bit gray image");
+    if (!mask.empty() && (mask.type() != CV_8UC1 || mask.rows != image.rows || mask.cols != image.cols)) // (upstream's CV_Assert)
+        throw std::runtime_error("goodFeaturesToTrack_hip: the mask is CV_8UC1 of the image's size, or empty");
+    if (blockSize != 3 && blockSize != 5)
+        throw std::runtime_error("goodFeaturesToTrack_hip: blockSize 3 and 5 are built (include/vo_corners_response.h)");
+    vo_ctx* c = ctx_for(image.cols, image.rows, 1);
+    vocorn_params prm;
+    prm.max_corners = maxCorners > 0 ? maxCorners : 0; // (upstream: maxCorners <= 0 means no limit)
+    prm.quality_level = qualityLevel;
+    prm.min_distance = minDistance;
+    voresp_params rsp;
+    rsp.block_size = blockSize;
+    rsp.use_harris = useHarrisDetector ? 1 : 0;
+    rsp.k = k; // (a k that is not finite: VO_ERR_ARG, thrown by check)
+    std::vector<cv::Point2f> out((size_t)(prm.max_corners > 0 ? prm.max_corners : 8192));
+    const uchar* m = mask.empty() ? nullptr : mask.data;
+    int n = 0;
+    check(c, voresp_detect(c, image.data, image.cols, image.rows, (int)image.step, m, m ? (int)mask.step : 0, &prm, &rsp, &out[0].x, (int)out.size(), &n));
+    if ((size_t)n > out.size()) { // no limit was given and more were found than the first buffer holds: nothing is truncated
+        out.resize((size_t)n);
+        check(c, voresp_detect(c, image.data, image.cols, image.rows, (int)image.step, m, m ? (int)mask.step : 0, &prm, &rsp, &out[0].x, n, &n));
+    }
+    out.resize((size_t)n);
+    points.swap(out);
+}
+
 void triangulate_hip(cv::Mat& Pl, cv::Mat& Pr, std::vector<cv::Point2f>& pl, std::vector<cv::Point2f>& pr, cv::Mat& points3D_t0)
 {
     if (Pl.type() != CV_32F || Pr.type() != CV_32F || Pl.rows != 3 || Pl.cols != 4 || Pr.rows != 3 || Pr.cols != 4)

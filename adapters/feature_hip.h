@@ -30,6 +30,7 @@
 #include "vo_flow.h"          // ... and its two-image tracker
 #include "vo_corners.h"       // ... and its Shi-Tomasi detector
 #include "vo_corners_mask.h"  // ... with goodFeaturesToTrack's mask argument
+#include "vo_corners_response.h" // ... and its blockSize, useHarrisDetector and k
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -65,6 +66,12 @@ void featureDetectionGoodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Poin
 // include/vo_corners_mask.h: mask is empty (no mask) or CV_8UC1 of the image's size, non-zero = allowed -- what a KLT front end
 // passes to top its point set up away from the points it still tracks.  maxCorners <= 0: no limit.
 void goodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points, int maxCorners, double qualityLevel, double minDistance, cv::Mat mask);
+
+// ... with upstream's full argument list: cv::goodFeaturesToTrack(image, points, maxCorners, qualityLevel, minDistance, mask, blockSize,
+// useHarrisDetector, k) through voresp_detect of include/vo_corners_response.h.  Built: blockSize 3 or 5 (gradientSize stays 3), the
+// minimum eigenvalue or the Harris response, any finite k; anything else throws std::runtime_error.
+void goodFeaturesToTrack_hip(cv::Mat image, std::vector<cv::Point2f>& points, int maxCorners, double qualityLevel, double minDistance, cv::Mat mask,
+                             int blockSize, bool useHarrisDetector, double k);
 
 // OPT-IN, default off: the caller promises that the t0 pair of every circularMatching_hip call IS the t1 pair of the call
 // before it -- the reference's loop hands its frames over exactly so (main.cpp:157-158: imageLeft_t0 = imageLeft_t1 shares

@@ -41,8 +41,8 @@
  * The device memory for the masks (one mask of max_w x max_h bytes and one point list per image of the table) is allocated by the
  * first vocmask_* call; a context that never makes one allocates and launches what it always did.
  *
- * OUT OF SCOPE: the Harris response, blockSize / gradientSize other than 3, cv::circle-exact discs, and any wiring into
- * vo_detect_bucket, vo_seq_* or the frame loop.
+ * OUT OF SCOPE: cv::circle-exact discs, and any wiring into vo_detect_bucket, vo_seq_* or the frame loop.  blockSize 5 and the
+ * Harris response are in the seventh header, vo_corners_response.h, whose calls run under these masks.
  */
 #ifndef VO_CORNERS_MASK_H
 #define VO_CORNERS_MASK_H

@@ -1,0 +1,69 @@
+/*
+ * vo_corners_response.h -- the Shi-Tomasi detector of vo_corners.h and vo_corners_mask.h with the last three arguments of
+ * cv::goodFeaturesToTrack: blockSize, useHarrisDetector and k (featureDetectionGoodFeaturesToTrack spells them out in its own call,
+ * feature.cpp:53-61).  The seventh header beside vo_hip.h.
+ *
+ *   voresp_map        cv::cornerMinEigenVal(img, out, block_size, 3)  or  cv::cornerHarris(img, out, block_size, 3, k): the f32
+ *                     response map of the whole image, border pixels included;
+ *   voresp_detect     cv::goodFeaturesToTrack(img, pts, max_corners, quality_level, min_distance, mask, block_size, use_harris, k);
+ *   voresp_batch_run  the detector over a range of the batch image table under whatever vocmask_batch_set_mask / _set_kept left;
+ *                     results come through vocorn_batch_get.
+ * Results are those of OpenCV 4.5 bit for bit as tests/host_check/corners_response_ref.c restates it (argued from upstream, not
+ * measured against a linked OpenCV: tools/opencv_crosscheck.py does that where there is one).  With the default response parameters
+ * (3, 0, 0.04) every call IS its vocorn_* / vocmask_* counterpart: the same function, the same kernels, the same bytes.
+ *
+ * Everything not said here -- the context, input formats, strides, image sizes, the kept image (img == NULL), PARAMETERS, the
+ * MIN_DISTANCE RANGE, the CAPACITY rule and VO_ERR_OVERFLOW, THE IMAGE TABLE, VO_ERR_STATE inside vo_seq_*, masks -- is
+ * vo_corners.h's and vo_corners_mask.h's, word for word.  A NULL response record means voresp_default_params.
+ *
+ * WHAT IS BUILT.  block_size 3 or 5; use_harris 0 or 1; k any finite double (it is read only when use_harris is 1, and checked
+ * always).  Anything else is VO_ERR_ARG, and vo_last_error says what is built.
+ *
+ * WHY ONLY 3 AND 5.  boxFilter's row pass, RowSum<float, double>, has explicit branches for ksize == 3 and ksize == 5 that add the
+ * casts left to right.  Every other size takes the branch that keeps a RUNNING f64 sum along the row.  The f64 sums of this filter
+ * are not exact (visual_odom_amd/csrc/corners.hip's header comment explains why), so the order is part of the result; a running sum
+ * in x would add a serial dependency along rows on top of ColumnSum's serial dependency down columns.  That is a different kernel,
+ * not a template argument.  gradientSize stays 3.
+ *
+ * THE HARRIS RESPONSE is calcHarris's scalar text: (float)(a * c - b * b - k * (a + c) * (a + c)) with a, b, c the f32 box sums and k
+ * a double -- a * c, b * b and their difference in f32, k * (a + c) * (a + c) in f64 left to right, the subtraction in f64, one cast.
+ * Upstream's vector loop computes the same expression in f32 with (float)k and differs from it in the last bits on some pixels;
+ * DESIGN 6 records it as a known divergence.  A Harris map is negative on edges and may be negative everywhere: the threshold
+ * (float)(max x quality_level) then lies ABOVE the maximum for quality_level < 1 (no corners) and below it for quality_level > 1.
+ * Threshold, dilate, sort and suppression are literal about sign, as upstream.
+ *
+ * OUT OF SCOPE: block sizes that take RowSum's generic branch, gradientSize other than 3, cv::circle-exact discs, and any wiring
+ * into vo_detect_bucket, vo_seq_* or the frame loop.
+ */
+#ifndef VO_CORNERS_RESPONSE_H
+#define VO_CORNERS_RESPONSE_H
+
+#include "vo_corners_mask.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct voresp_params {
+    int block_size; /* 3 or 5 */
+    int use_harris; /* 0: minimum eigenvalue, 1: Harris */
+    double k;       /* Harris's free parameter */
+} voresp_params;
+
+/* 3, 0, 0.04: cv::goodFeaturesToTrack's own defaults */
+void voresp_default_params(voresp_params *p);
+
+/* The response map of img: out is h rows of w floats, out_stride_floats (>= w) floats apart.  img as in vocorn_detect. */
+int voresp_map(vo_ctx *ctx, const uint8_t *img, int w, int h, int stride, const voresp_params *resp, float *out, int out_stride_floats);
+
+/* vocmask_detect with the response `resp`.  mask == NULL: no mask (mask_stride is not looked at). */
+int voresp_detect(vo_ctx *ctx, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride, const vocorn_params *params,
+                  const voresp_params *resp, float *pts_out, int cap, int *n_out);
+
+/* vocmask_batch_run with the response `resp`: an image without a mask runs unmasked.  Results come through vocorn_batch_get. */
+int voresp_batch_run(vo_ctx *ctx, const vocorn_params *params, const voresp_params *resp, int first_image, int n_images);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* VO_CORNERS_RESPONSE_H */

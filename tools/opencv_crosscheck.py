@@ -11,7 +11,8 @@ message when cv2 is missing.
 
 Calls diffed (the reference's call sites): cv2.pyrDown (inside buildOpticalFlowPyramid), cv2.calcOpticalFlowPyrLK as
 feature.cpp:136-139 calls it (win 21, maxLevel 3, 30 / 0.01, minEig 1e-3), cv2.FAST(20, nonmax), cv2.cornerMinEigenVal(3, 3) + cv2.goodFeaturesToTrack as feature.cpp:53-55
-calls it (against tests/host_check/corners_ref.c), cv2.triangulatePoints +
+calls it (against tests/host_check/corners_ref.c), cv2.cornerMinEigenVal(5, 3), cv2.cornerHarris(3 | 5, 3, 0.04) and cv2.goodFeaturesToTrack
+with them (against tests/host_check/corners_response_ref.c), cv2.triangulatePoints +
 convertPointsFromHomogeneous (main.cpp:170-171), cv2.solvePnPRansac + Rodrigues (visualOdometry.cpp:176,188; also with exactly 4 points = the P3P switch) and
 cv2.findEssentialMat + recoverPose (visualOdometry.cpp:152-153).  Expected against x86 OpenCV: pyramids and FAST
 bit-exact, LK positions within ~1e-3 px with identical status (OpenCV accumulates the 2x2 system in f32 SIMD lanes, the
@@ -91,6 +92,30 @@ def main():
             report("goodFeaturesToTrack(5000, 0.01, %g) %s corners + order" % (md, name), 0.0 if same else 1.0, 0, "cv2 %d / ref %d" % (len(c_cv), len(c_my)))
             if name == "crop" and md == 5.0:
                 golden["corn_crop"], golden["corn_eig"], golden["corn_pts"] = img, eig_cv, c_cv
+    # ---- blockSize 5 and the Harris response (include/vo_corners_response.h): cv2.cornerMinEigenVal(5, 3), cv2.cornerHarris(3 | 5, 3,
+    # 0.04) and cv2.goodFeaturesToTrack with them, against tests/host_check/corners_response_ref.c.  Expected for the Harris maps: the
+    # scalar text of calcHarris (form 0) is the specification, but a vectorised build runs its f32 loop (form 1) for all but the tail
+    # columns -- the row says which form THIS cv2 matches in more pixels, and the corner lists may then differ where qualities nearly tie.
+    import corners_response_cases as cr
+    for name, img in (("full", L[0]), ("crop", np.ascontiguousarray(L[0][140:236, 400:720]))):
+        for block, harris in cr.RESPONSES:
+            if harris:
+                m_cv = cv2.cornerHarris(img, block, 3, 0.04)
+                what = "cornerHarris(%d, 3, 0.04)" % block
+            else:
+                m_cv = cv2.cornerMinEigenVal(img, block, ksize=3)
+                what = "cornerMinEigenVal(%d, 3)" % block
+            diff = {f: int((m_cv.view(np.uint32) != cr.ref_map(img, block, harris, 0.04, form=f).view(np.uint32)).sum()) for f in ((0, 1) if harris else (0,))}
+            m_my = cr.ref_map(img, block, harris, 0.04)
+            report("%s %s" % (what, name), float(np.abs(m_cv - m_my).max()), 0,
+                   ", ".join("form %d: %d of %d values differ in their bits" % (f, n, m_my.size) for f, n in diff.items()))
+            for md in (5.0, 0.0):
+                c_cv = cv2.goodFeaturesToTrack(img, 5000, 0.01, md, None, None, block, bool(harris), 0.04)
+                c_cv = np.zeros((0, 2), np.float32) if c_cv is None else c_cv.reshape(-1, 2)
+                c_my = cr.ref_detect(img, None, 5000, 0.01, md, block, harris, 0.04)[0]
+                same = c_cv.shape == c_my.shape and np.array_equal(c_cv, c_my)
+                report("goodFeaturesToTrack(5000, 0.01, %g, blockSize %d, harris %d) %s corners + order" % (md, block, harris, name),
+                       0.0 if same else 1.0, 0, "cv2 %d / ref %d" % (len(c_cv), len(c_my)))
     # ---- the four LK hops
     lk = dict(winSize=(21, 21), maxLevel=3, criteria=(cv2.TERM_CRITERIA_COUNT + cv2.TERM_CRITERIA_EPS, 30, 0.01), flags=0,
               minEigThreshold=0.001)

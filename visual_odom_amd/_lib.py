@@ -50,6 +50,8 @@ FLAG_EXPORTS = ("voflag_track", "voflag_feature_tracking", "voflag_batch_set_gue
 CORN_EXPORTS = ("vocorn_default_params", "vocorn_detect", "vocorn_min_eigen_map", "vocorn_batch_run", "vocorn_batch_get")
 # include/vo_corners_mask.h: the same detector with goodFeaturesToTrack's mask argument, the sixth header
 CMASK_EXPORTS = ("vocmask_detect", "vocmask_disc_mask", "vocmask_replenish", "vocmask_batch_set_mask", "vocmask_batch_set_kept", "vocmask_batch_run")
+# include/vo_corners_response.h: the same detector with goodFeaturesToTrack's blockSize, useHarrisDetector and k, the seventh header
+RESP_EXPORTS = ("voresp_default_params", "voresp_map", "voresp_detect", "voresp_batch_run")
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -114,6 +116,11 @@ class VoCornParams(C.Structure):
     _fields_ = [("max_corners", C.c_int), ("quality_level", C.c_double), ("min_distance", C.c_double)]
 
 
+class VoRespParams(C.Structure):
+    """voresp_params (include/vo_corners_response.h)"""
+    _fields_ = [("block_size", C.c_int), ("use_harris", C.c_int), ("k", C.c_double)]
+
+
 class VoError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libvo_hip error %d: %s" % (code, msg))
@@ -175,6 +182,13 @@ def load():
     lib.vocmask_batch_set_kept.argtypes = [vp, i, vp, i, i]
     lib.vocmask_batch_run.argtypes = [vp, C.POINTER(VoCornParams), i, i]
     for name in CMASK_EXPORTS:
+        getattr(lib, name).restype = C.c_int
+    lib.voresp_default_params.argtypes = [C.POINTER(VoRespParams)]
+    lib.voresp_default_params.restype = None
+    lib.voresp_map.argtypes = [vp, vp, i, i, i, C.POINTER(VoRespParams), vp, i]
+    lib.voresp_detect.argtypes = [vp, vp, i, i, i, vp, i, C.POINTER(VoCornParams), C.POINTER(VoRespParams), vp, i, vp]
+    lib.voresp_batch_run.argtypes = [vp, C.POINTER(VoCornParams), C.POINTER(VoRespParams), i, i]
+    for name in RESP_EXPORTS[1:]:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -589,12 +603,20 @@ class Context:
             m = np.ascontiguousarray(m, np.uint8)
         return m, int(m.strides[0])
 
-    def good_features_to_track(self, img, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None, mask=None):
+    def good_features_to_track(self, img, max_corners=5000, quality_level=0.01, min_distance=5.0, cap=None, mask=None, block_size=3,
+                               use_harris=False, k=0.04):
         """featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) = cv::goodFeaturesToTrack(img, max_corners, quality_level,
-        min_distance, mask): corners best first, (n, 2) float32.  cap: rows to fetch (default: all that were found).  mask: (h, w)
-        uint8, non-zero = allowed (vocmask_detect, include/vo_corners_mask.h); None = no mask (vocorn_detect)"""
+        min_distance, mask, block_size, use_harris, k): corners best first, (n, 2) float32.  cap: rows to fetch (default: all that
+        were found).  mask: (h, w) uint8, non-zero = allowed (vocmask_detect, include/vo_corners_mask.h); None = no mask
+        (vocorn_detect).  block_size 3 or 5, use_harris, k: as given they are the calls above; anything else goes through
+        voresp_detect (include/vo_corners_response.h)"""
         img, w, h, stride = self._corn_image(img)
         prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        if (block_size, bool(use_harris), k) != (3, False, 0.04):
+            rsp = VoRespParams(int(block_size), int(bool(use_harris)), float(k))
+            m, ms = (None, 0) if mask is None else self._mask(mask, w, h)
+            return self._corn_fetch_all(lambda pts, c, n: self.lib.voresp_detect(self.h, _pn(img), w, h, stride, _pn(m), ms, C.byref(prm), C.byref(rsp),
+                                                                                  pts, c, n), cap)
         if mask is None:
             return self._corn_fetch_all(lambda pts, c, n: self.lib.vocorn_detect(self.h, _pn(img), w, h, stride, C.byref(prm), pts, c, n), cap)
         m, ms = self._mask(mask, w, h)
@@ -631,10 +653,16 @@ class Context:
         k = _f32(kept, (-1, 2))
         self._chk(self.lib.vocmask_batch_set_kept(self.h, int(image_idx), _pn(k if len(k) else None), len(k), int(radius)))
 
-    def corners_batch_run(self, first_image, n_images, max_corners=5000, quality_level=0.01, min_distance=5.0, masked=False):
+    def corners_batch_run(self, first_image, n_images, max_corners=5000, quality_level=0.01, min_distance=5.0, masked=False, block_size=3,
+                          use_harris=False, k=0.04):
         """the detector over images first_image .. first_image + n_images - 1 of the batch image table, enqueued.  masked: under the
-        masks set so far (vocmask_batch_run; an image without one runs unmasked)"""
+        masks set so far (vocmask_batch_run; an image without one runs unmasked).  block_size, use_harris, k other than the defaults:
+        voresp_batch_run, which always runs under the masks set so far"""
         prm = VoCornParams(int(max_corners), float(quality_level), float(min_distance))
+        if (block_size, bool(use_harris), k) != (3, False, 0.04):
+            rsp = VoRespParams(int(block_size), int(bool(use_harris)), float(k))
+            self._chk(self.lib.voresp_batch_run(self.h, C.byref(prm), C.byref(rsp), int(first_image), int(n_images)))
+            return
         run = self.lib.vocmask_batch_run if masked else self.lib.vocorn_batch_run
         self._chk(run(self.h, C.byref(prm), int(first_image), int(n_images)))
 
@@ -651,6 +679,14 @@ class Context:
         eig = np.zeros((h, w), np.float32)
         self._chk(self.lib.vocorn_min_eigen_map(self.h, _pn(img), w, h, stride, _p(eig), w))
         return eig
+
+    def corner_response_map(self, img, block_size=3, use_harris=False, k=0.04):
+        """cv::cornerMinEigenVal(img, block_size, 3) or cv::cornerHarris(img, block_size, 3, k) (voresp_map): (h, w) float32"""
+        img, w, h, stride = self._corn_image(img)
+        out = np.zeros((h, w), np.float32)
+        rsp = VoRespParams(int(block_size), int(bool(use_harris)), float(k))
+        self._chk(self.lib.voresp_map(self.h, _pn(img), w, h, stride, C.byref(rsp), _p(out), w))
+        return out
 
     def detect_bucket(self, img, pts, ages, **detect_kw):
         """appendNewFeatures (if fewer than redetect_below points) + bucketingFeatures

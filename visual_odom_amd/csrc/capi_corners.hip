@@ -4,11 +4,12 @@
 // have the context's corner-list capacity (vo_ctx::fcap), in buffers of their own: the FAST lists (d_feat, d_fages) are float2 + age
 // rows that a detect / bucket run of the batch API may still own, and the sort needs 64-bit keys at a power-of-two length.
 #include "capi_internal.h"
-#include "../../include/vo_corners.h"
+#include "../../include/vo_corners_response.h"
 #include "vo_corners_dev.h"
 
 // (namespace vo_capi: capi_corners_mask.hip -- vocmask_*, the same detector under a mask -- shares the argument checks, the image
-// set-up, the buffers and the fetch; they are declared in capi_internal.h)
+// set-up, the buffers and the fetch, and capi_corners_response.hip -- voresp_*, the detector with blockSize / useHarrisDetector / k --
+// the calls themselves; they are declared in capi_internal.h)
 namespace vo_capi {
 
 int ensure_corn(vo_ctx *c, int slots)
@@ -43,7 +44,7 @@ int ensure_corn(vo_ctx *c, int slots)
     return VO_OK;
 }
 
-CornArgs corn_args(vo_ctx *c, const vocorn_params &p)
+CornArgs corn_args(vo_ctx *c, const vocorn_params &p, const voresp_params *resp)
 {
     vo_ctx::Corn &k = c->corn;
     const size_t S = (size_t)k.slots;
@@ -66,6 +67,11 @@ CornArgs corn_args(vo_ctx *c, const vocorn_params &p)
     // dx * dx + dy * dy < minDistance * minDistance (a double); integer offsets: d2 < ceil(minDistance^2)
     a.cell = p.min_distance >= 1 ? (int)lrint(p.min_distance) : 1;
     a.lim = p.min_distance >= 1 ? (int)ceil(p.min_distance * p.min_distance) : 0;
+    if (resp) {
+        a.block_size = resp->block_size;
+        a.use_harris = resp->use_harris;
+        a.harris_k = resp->k;
+    }
     return a;
 }
 
@@ -115,7 +121,52 @@ int corn_fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *
     return VO_OK;
 }
 
-int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked)
+int corn_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const vocorn_params *params, const voresp_params *resp,
+                float *pts_out, int cap, int *n_out)
+{
+    if (!n_out || cap < 0 || (cap > 0 && !pts_out))
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": null output, or cap < 0").c_str());
+    vocorn_params p;
+    int rc = corn_check_params(c, who, params, &p);
+    if (rc != VO_OK)
+        return rc;
+    int image = 0;
+    rc = corn_sync_image(c, who, img, w, h, stride, &image);
+    if (rc != VO_OK)
+        return rc;
+    rc = ensure_corn(c, 1);
+    if (rc != VO_OK)
+        return rc;
+    c->corn.run_n = 0; // (slot 0 no longer holds a batch run's image)
+    VO_HIP_TRY(c, launch_corners(c->d_imgs, image, 1, w, h, corn_args(c, p, resp), c->sel->stream));
+    return corn_fetch(c, who, 0, pts_out, cap, n_out);
+}
+
+int corn_map(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const voresp_params *resp, float *out, int out_stride_floats)
+{
+    if (!out || out_stride_floats < w)
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": null output, or a row stride smaller than the width").c_str());
+    int image = 0;
+    int rc = corn_sync_image(c, who, img, w, h, stride, &image);
+    if (rc != VO_OK)
+        return rc;
+    rc = ensure_corn(c, 1);
+    if (rc != VO_OK)
+        return rc;
+    vo_ctx::Corn &k = c->corn;
+    k.run_n = 0; // (slot 0's map no longer belongs to a batch run)
+    if (resp)
+        launch_corner_map(c->d_imgs, image, w, h, k.d_maps, c->sel->stream, resp->block_size, resp->use_harris, resp->k);
+    else
+        launch_corner_map(c->d_imgs, image, w, h, k.d_maps, c->sel->stream);
+    VO_HIP_TRY(c, hipGetLastError());
+    VO_HIP_TRY(c, hipMemcpy2DAsync(out, sizeof(float) * (size_t)out_stride_floats, k.d_maps, sizeof(float) * (size_t)w, sizeof(float) * (size_t)w, (size_t)h,
+                                   hipMemcpyDeviceToHost, c->sel->stream));
+    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
+    return VO_OK;
+}
+
+int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked, const voresp_params *resp)
 {
     const std::string name(who);
     vocorn_params p;
@@ -134,7 +185,7 @@ int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int 
     VO_HIP_TRY(c, hipSetDevice(c->device));
     vo_ctx::Corn &k = c->corn;
     k.run_n = 0;
-    CornArgs a = corn_args(c, p);
+    CornArgs a = corn_args(c, p, resp);
     if (masked && c->cmask.any) { // (no image has a mask: the unmasked kernels)
         a.masks = c->cmask.d_table + first_image;
         a.mask_pitch = c->w;
@@ -163,45 +214,14 @@ int vocorn_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const
 {
     if (!c)
         return VO_ERR_ARG;
-    if (!n_out || cap < 0 || (cap > 0 && !pts_out))
-        return fail(c, VO_ERR_ARG, "vocorn_detect: null output, or cap < 0");
-    vocorn_params p;
-    int rc = corn_check_params(c, "vocorn_detect", params, &p);
-    if (rc != VO_OK)
-        return rc;
-    int image = 0;
-    rc = corn_sync_image(c, "vocorn_detect", img, w, h, stride, &image);
-    if (rc != VO_OK)
-        return rc;
-    rc = ensure_corn(c, 1);
-    if (rc != VO_OK)
-        return rc;
-    c->corn.run_n = 0; // (slot 0 no longer holds a batch run's image)
-    VO_HIP_TRY(c, launch_corners(c->d_imgs, image, 1, w, h, corn_args(c, p), c->sel->stream));
-    return corn_fetch(c, "vocorn_detect", 0, pts_out, cap, n_out);
+    return corn_detect(c, "vocorn_detect", img, w, h, stride, params, nullptr, pts_out, cap, n_out);
 }
 
 int vocorn_min_eigen_map(vo_ctx *c, const uint8_t *img, int w, int h, int stride, float *eig_out, int eig_stride_floats)
 {
     if (!c)
         return VO_ERR_ARG;
-    if (!eig_out || eig_stride_floats < w)
-        return fail(c, VO_ERR_ARG, "vocorn_min_eigen_map: null output, or a row stride smaller than the width");
-    int image = 0;
-    int rc = corn_sync_image(c, "vocorn_min_eigen_map", img, w, h, stride, &image);
-    if (rc != VO_OK)
-        return rc;
-    rc = ensure_corn(c, 1);
-    if (rc != VO_OK)
-        return rc;
-    vo_ctx::Corn &k = c->corn;
-    k.run_n = 0; // (slot 0's map no longer belongs to a batch run)
-    launch_corner_map(c->d_imgs, image, w, h, k.d_maps, c->sel->stream);
-    VO_HIP_TRY(c, hipGetLastError());
-    VO_HIP_TRY(c, hipMemcpy2DAsync(eig_out, sizeof(float) * (size_t)eig_stride_floats, k.d_maps, sizeof(float) * (size_t)w, sizeof(float) * (size_t)w,
-                                   (size_t)h, hipMemcpyDeviceToHost, c->sel->stream));
-    VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
-    return VO_OK;
+    return corn_map(c, "vocorn_min_eigen_map", img, w, h, stride, nullptr, eig_out, eig_stride_floats);
 }
 
 int vocorn_batch_run(vo_ctx *c, const vocorn_params *params, int first_image, int n_images)

@@ -5,7 +5,7 @@
 // what it always did); a run reads the plane of image i through d_table[i], null for an image without a mask.  The synchronous calls
 // use a plane, a point list and a table entry of their own behind those of the images.  Everything runs on the tracking stream.
 #include "capi_internal.h"
-#include "../../include/vo_corners_mask.h"
+#include "../../include/vo_corners_response.h"
 #include "vo_corners_dev.h"
 
 namespace {
@@ -84,13 +84,14 @@ int batch_checks(vo_ctx *c, const char *who, int image_idx)
 }
 
 // the detector on image `image` of the table under the synchronous calls' own plane, and its results
-int detect_under_own_mask(vo_ctx *c, const char *who, int image, int w, int h, const vocorn_params &p, float *pts_out, int cap, int *n_out)
+int detect_under_own_mask(vo_ctx *c, const char *who, int image, int w, int h, const vocorn_params &p, const voresp_params *resp, float *pts_out, int cap,
+                          int *n_out)
 {
     int rc = ensure_corn(c, 1);
     if (rc != VO_OK)
         return rc;
     c->corn.run_n = 0; // (slot 0 no longer holds a batch run's image)
-    CornArgs a = corn_args(c, p);
+    CornArgs a = corn_args(c, p, resp);
     a.masks = c->cmask.d_table + c->max_images;
     a.mask_pitch = w;
     VO_HIP_TRY(c, launch_corners(c->d_imgs, image, 1, w, h, a, c->sel->stream));
@@ -99,25 +100,21 @@ int detect_under_own_mask(vo_ctx *c, const char *who, int image, int w, int h, c
 
 } // namespace
 
-extern "C" {
-
-int vocmask_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride, const vocorn_params *params,
-                   float *pts_out, int cap, int *n_out)
+int vo_capi::cmask_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride,
+                          const vocorn_params *params, const voresp_params *resp, float *pts_out, int cap, int *n_out)
 {
-    if (!c)
-        return VO_ERR_ARG;
     if (!mask)
-        return vocorn_detect(c, img, w, h, stride, params, pts_out, cap, n_out);
+        return corn_detect(c, who, img, w, h, stride, params, resp, pts_out, cap, n_out);
     if (!n_out || cap < 0 || (cap > 0 && !pts_out))
-        return fail(c, VO_ERR_ARG, "vocmask_detect: null output, or cap < 0");
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": null output, or cap < 0").c_str());
     if (mask_stride < w)
-        return fail(c, VO_ERR_ARG, "vocmask_detect: mask stride smaller than the width");
+        return fail(c, VO_ERR_ARG, (std::string(who) + ": mask stride smaller than the width").c_str());
     vocorn_params p;
-    int rc = corn_check_params(c, "vocmask_detect", params, &p);
+    int rc = corn_check_params(c, who, params, &p);
     if (rc != VO_OK)
         return rc;
     int image = 0;
-    rc = corn_sync_image(c, "vocmask_detect", img, w, h, stride, &image);
+    rc = corn_sync_image(c, who, img, w, h, stride, &image);
     if (rc != VO_OK)
         return rc;
     rc = ensure_cmask(c);
@@ -125,7 +122,19 @@ int vocmask_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, cons
         return rc;
     uint8_t *plane = c->cmask.d_masks + (size_t)c->max_images * plane_bytes(c);
     VO_HIP_TRY(c, hipMemcpy2DAsync(plane, (size_t)w, mask, (size_t)mask_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice, c->sel->stream));
-    return detect_under_own_mask(c, "vocmask_detect", image, w, h, p, pts_out, cap, n_out); // (its fetch waits for the stream)
+    return detect_under_own_mask(c, who, image, w, h, p, resp, pts_out, cap, n_out); // (its fetch waits for the stream)
+}
+
+extern "C" {
+
+int vocmask_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride, const vocorn_params *params,
+                   float *pts_out, int cap, int *n_out)
+{
+    if (!c)
+        return VO_ERR_ARG;
+    if (!mask) // (vocorn_detect itself)
+        return corn_detect(c, "vocorn_detect", img, w, h, stride, params, nullptr, pts_out, cap, n_out);
+    return cmask_detect(c, "vocmask_detect", img, w, h, stride, mask, mask_stride, params, nullptr, pts_out, cap, n_out);
 }
 
 int vocmask_disc_mask(vo_ctx *c, int w, int h, const float *kept_xy, int n_kept, int radius, uint8_t *mask_out, int mask_stride)
@@ -178,7 +187,7 @@ int vocmask_replenish(vo_ctx *c, const uint8_t *img, int w, int h, int stride, c
     rc = build_disc_mask(c, c->max_images, kept_xy, n_kept, radius, w, h);
     if (rc != VO_OK)
         return rc;
-    return detect_under_own_mask(c, "vocmask_replenish", image, w, h, p, pts_out, cap, n_out);
+    return detect_under_own_mask(c, "vocmask_replenish", image, w, h, p, nullptr, pts_out, cap, n_out);
 }
 
 int vocmask_batch_set_mask(vo_ctx *c, int image_idx, const uint8_t *mask, int mask_stride)

@@ -27,6 +27,7 @@ namespace vo {
 struct CornArgs; // vo_corners_dev.h
 }
 struct vocorn_params; // include/vo_corners.h
+struct voresp_params; // include/vo_corners_response.h
 
 #define VO_SEQ_INFLIGHT 8 // steps the host may run ahead of the device
 // timing events of one run: [0..3] tracking stream (3 stages), [4..7] post streams (3 stages), [8] start of DETECT on
@@ -552,13 +553,21 @@ int seq_push(vo_ctx *c, int seq, const void *left, const void *right, int stride
 int single_frame_setup(vo_ctx *c, const uint8_t *l0, const uint8_t *r0, const uint8_t *l1, const uint8_t *r1, int w, int h, int stride, const float *pts, int n, bool defer_t1 = false);
 int single_image_setup(vo_ctx *c, const uint8_t *img, int w, int h, int stride, bool plain = false);
 int flush_deferred(vo_ctx *c, hipStream_t on);
-// the Shi-Tomasi detector's host side (capi_corners.hip), shared with its masked calls (capi_corners_mask.hip)
+// the Shi-Tomasi detector's host side (capi_corners.hip), shared with its masked calls (capi_corners_mask.hip) and with the calls that
+// take a response (capi_corners_response.hip).  resp: a CHECKED record, or null for the 3 x 3 minimum eigenvalue -- the vocorn_* and
+// vocmask_* entry points are these functions with resp == null, under their own names in `who`
 int ensure_corn(vo_ctx *c, int slots);
-vo::CornArgs corn_args(vo_ctx *c, const vocorn_params &p);
+vo::CornArgs corn_args(vo_ctx *c, const vocorn_params &p, const voresp_params *resp = nullptr);
 int corn_check_params(vo_ctx *c, const char *who, const vocorn_params *in, vocorn_params *p);
 int corn_sync_image(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, int *image);
 int corn_fetch(vo_ctx *c, const char *who, int s, float *pts_out, int cap, int *n_out);
-int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked);
+int corn_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const vocorn_params *params, const voresp_params *resp,
+                float *pts_out, int cap, int *n_out);
+int corn_map(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const voresp_params *resp, float *out, int out_stride_floats);
+int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked,
+                   const voresp_params *resp = nullptr);
+int cmask_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride,
+                 const vocorn_params *params, const voresp_params *resp, float *pts_out, int cap, int *n_out); // (capi_corners_mask.hip)
 struct DeferGuard { // the deferred t1 pair never outlives the call whose host pointers it holds
     vo_ctx *c;
     ~DeferGuard() { c->defer.n = 0; }

@@ -10,6 +10,9 @@
 // and goodFeaturesToTrack's mask argument (include/vo_corners_mask.h): the map kernel's masked twin takes the maximum over the allowed
 // pixels, the candidate kernel drops the masked-out local maxima, and
 //   corn_disc_kernel     one wavefront per kept point: zeros over its disc in a mask that holds 0xFF
+// and goodFeaturesToTrack's blockSize, useHarrisDetector and k (include/vo_corners_response.h; tests/host_check/corners_response_ref.c):
+//   corn_map_resp_kernel<B, HARRIS>  the map kernel at blockSize 5 and / or with calcHarris's response, masked or not; the
+//                        candidate and select kernels take whatever map comes in, negative values included
 //
 // Why a thread per column.  boxFilter sums the f32 products in f64, and its column pass (ColumnSum<double, float>) is a RUNNING sum
 // down the whole column: SUM += row(y + 1); out = SUM; SUM -= row(y - 1).  The f64 operations are not exact in general -- a dy of
@@ -32,18 +35,29 @@
 
 namespace vo {
 
-constexpr int CM_T = 256, CM_COLS = CM_T - 2;     // map kernel: threads per workgroup; columns it owns (+ one halo column each side)
+constexpr int CM_T = 256;                         // map kernels: threads per workgroup = cov columns it computes
+constexpr int CM_COLS = CM_T - 2;                 // ... columns a workgroup owns at blockSize 3 (+ one halo column each side)
+constexpr int CM_COLS5 = CM_T - 4;                // ... at blockSize 5 (+ two)
 constexpr int CT_W = 64, CT_H = 16;               // candidate kernel: tile
 constexpr int CV_W = CT_W + 2, CV_H = CT_H + 2;   // ... and its values: + the 3 x 3 neighbours of the tile's pixels
 constexpr int CORN_SELECT_THREADS = 1024;
 
 __device__ __forceinline__ int corn_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-// The body of the two map kernels.  mask: the slot's mask (rows mask_pitch bytes apart) or null.  minMaxLoc(eig, 0, &maxVal, 0, 0,
+// The body of the map kernels.  mask: the slot's mask (rows mask_pitch bytes apart) or null.  minMaxLoc(eig, 0, &maxVal, 0, 0,
 // mask) takes the maximum over the allowed pixels only (none: max_key stays 0); the map itself is the same with and without one.
+//
+// B: blockSize, 3 or 5 -- the two sizes for which RowSum<float, double> sums the casts left to right (every other size keeps a
+// running sum along the row, which is another kernel).  R = B / 2 halo columns on each side, cov rows -R .. h - 1 + R, and the
+// B - 1 row sums that ColumnSum<double, float> still has to subtract in `ring`, oldest first: registers, shifted once per row (at
+// B = 5 that is 12 doubles; in LDS they would cost 24 KiB per workgroup and an address per access).  HARRIS: calcHarris in place of
+// calcMinEigenVal; k is read by it alone.  (3, false) is cv::cornerMinEigenVal(img, eig, 3, 3) as it always was.
+template <int B, int HARRIS>
 __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
-                                              unsigned *__restrict__ max_key, const uint8_t *__restrict__ mask, int mask_pitch)
+                                              unsigned *__restrict__ max_key, const uint8_t *__restrict__ mask, int mask_pitch, double k)
 {
+    static_assert(B == 3 || B == 5, "RowSum's left-to-right branches");
+    constexpr int R = B / 2, COLS = B == 5 ? CM_COLS5 : CM_COLS;
     __shared__ float s_cov[3][CM_T];
     __shared__ unsigned s_max;
     const int tid = threadIdx.x, slot = blockIdx.y;
@@ -53,22 +67,22 @@ __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs,
     float *__restrict__ map = maps + (size_t)slot * map_stride;
     // this thread's cov column: x of the COV image, which outside the image is the cov of the reflected position rx (boxFilter
     // reflects the cov image); its Sobel reads the source around rx, reflected in turn
-    const int x = (int)blockIdx.x * CM_COLS - 1 + tid;
-    const int rx = reflect101(corn_clamp(x, -1, w), w), xa = reflect101(rx - 1, w), xc = reflect101(rx + 1, w);
-    const bool owner = tid >= 1 && tid <= CM_COLS && x < w; // (x >= 0 then)
+    const int x = (int)blockIdx.x * COLS - R + tid;
+    const int rx = reflect101(corn_clamp(x, -R, w - 1 + R), w), xa = reflect101(rx - 1, w), xc = reflect101(rx + 1, w);
+    const bool owner = tid >= R && tid < CM_T - R && x < w; // (x >= 0 then)
     if (tid == 0)
         s_max = 0;
-    const float sf = (float)(1.0 / (255.0 * 4.0 * 3.0)), sf2 = sf * 2.f;
-    double sum[3] = {0, 0, 0}, r_prev[3] = {0, 0, 0}, r_cur[3] = {0, 0, 0}; // SUM, row(y - 1), row(y) of ColumnSum
+    const float sf = (float)(1.0 / (255.0 * 4.0 * B)), sf2 = sf * 2.f;
+    double sum[3] = {0, 0, 0}, ring[B - 1][3] = {}; // SUM, row(y - R) .. row(y + R - 1) of ColumnSum
     unsigned best = 0;
-    for (int yy = -1; yy <= h; yy++) { // cov row yy enters the column sum; the map row yy - 1 leaves it
+    for (int yy = -R; yy <= h - 1 + R; yy++) { // cov row yy enters the column sum; the map row yy - R leaves it
         const int ry = reflect101(yy, h);
         // the mask byte of the map row this iteration completes: one coalesced byte per pixel beside the 4-byte store, fetched with
         // the iteration's pixels.  It is a fourth row stream and, unlike two of the three pixel rows, never a cache hit: the masked
         // kernel takes 0.67 ms where the plain one takes 0.53 (256 images of 1241 x 376)
         uint8_t allowed = 1;
-        if (mask && owner && yy >= 1)
-            allowed = mask[(size_t)(yy - 1) * mask_pitch + x];
+        if (mask && owner && yy >= R)
+            allowed = mask[(size_t)(yy - R) * mask_pitch + x];
         float rd[3], rs[3];
         for (int j = 0; j < 3; j++) { // RowFilter<uchar, float>: s = k0 p(x-1); s += k1 p(x); s += k2 p(x+1)
             const VO_GLOBAL uint8_t *row = src + (ptrdiff_t)reflect101(ry + j - 1, h) * stride;
@@ -90,30 +104,41 @@ __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs,
         __syncthreads();
         double r[3] = {0, 0, 0};
         if (owner)
-            for (int k = 0; k < 3; k++) // RowSum<float, double>, ksize == 3
-                r[k] = ((double)s_cov[k][tid - 1] + (double)s_cov[k][tid]) + (double)s_cov[k][tid + 1];
+            for (int c = 0; c < 3; c++) { // RowSum<float, double>, the ksize == 3 and ksize == 5 branches: the casts, left to right
+                r[c] = ((double)s_cov[c][tid - R] + (double)s_cov[c][tid - R + 1]) + (double)s_cov[c][tid - R + 2];
+                if constexpr (B == 5)
+                    r[c] = (r[c] + (double)s_cov[c][tid + 1]) + (double)s_cov[c][tid + 2];
+            }
         __syncthreads();
         if (!owner)
             continue;
-        if (yy <= 0) { // SUM = 0; SUM += row(-1); SUM += row(0)
-            for (int k = 0; k < 3; k++) {
-                sum[k] += r[k];
-                r_prev[k] = r_cur[k];
-                r_cur[k] = r[k];
+        if (yy < R) { // SUM = 0; SUM += row(-R); ... SUM += row(R - 1)
+            for (int c = 0; c < 3; c++) {
+                sum[c] += r[c];
+                for (int i = 0; i < B - 2; i++)
+                    ring[i][c] = ring[i + 1][c];
+                ring[B - 2][c] = r[c];
             }
             continue;
         }
         float box[3];
-        for (int k = 0; k < 3; k++) { // s0 = SUM + row(y + 1); D = (float)s0; SUM = s0 - row(y - 1)
-            const double s0 = sum[k] + r[k];
-            box[k] = (float)s0;
-            sum[k] = s0 - r_prev[k];
-            r_prev[k] = r_cur[k];
-            r_cur[k] = r[k];
+        for (int c = 0; c < 3; c++) { // s0 = SUM + row(y + R); D = (float)s0; SUM = s0 - row(y - R)
+            const double s0 = sum[c] + r[c];
+            box[c] = (float)s0;
+            sum[c] = s0 - ring[0][c];
+            for (int i = 0; i < B - 2; i++)
+                ring[i][c] = ring[i + 1][c];
+            ring[B - 2][c] = r[c];
         }
-        const float ea = box[0] * 0.5f, eb = box[1], ec = box[2] * 0.5f; // calcMinEigenVal
-        const float e = (ea + ec) - sqrtf((ea - ec) * (ea - ec) + eb * eb);
-        map[(size_t)(yy - 1) * w + x] = e;
+        float e;
+        if constexpr (HARRIS) { // calcHarris: (float)(a * c - b * b - k * (a + c) * (a + c)), a, b, c floats and k a double
+            const float ha = box[0], hb = box[1], hc = box[2];
+            e = (float)((double)(ha * hc - hb * hb) - k * (double)(ha + hc) * (double)(ha + hc));
+        } else { // calcMinEigenVal
+            const float ea = box[0] * 0.5f, eb = box[1], ec = box[2] * 0.5f;
+            e = (ea + ec) - sqrtf((ea - ec) * (ea - ec) + eb * eb);
+        }
+        map[(size_t)(yy - R) * w + x] = e;
         const unsigned key = corn_ord(e);
         if (allowed)
             best = key > best ? key : best;
@@ -131,14 +156,24 @@ __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs,
 __global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
                                                         unsigned *__restrict__ max_key)
 {
-    corn_map_body(imgs, first, maps, map_stride, max_key, nullptr, 0);
+    corn_map_body<3, 0>(imgs, first, maps, map_stride, max_key, nullptr, 0, 0.0);
 }
 
 // ... under masks [n] (CornArgs::masks: a slot's entry may be null)
 __global__ __launch_bounds__(CM_T) void corn_map_masked_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
                                                                unsigned *__restrict__ max_key, const uint8_t *const *__restrict__ masks, int mask_pitch)
 {
-    corn_map_body(imgs, first, maps, map_stride, max_key, masks[blockIdx.y], mask_pitch);
+    corn_map_body<3, 0>(imgs, first, maps, map_stride, max_key, masks[blockIdx.y], mask_pitch, 0.0);
+}
+
+// The response maps of include/vo_corners_response.h: cornerMinEigenVal at blockSize 5, cornerHarris at 3 and 5.  masks: null, or
+// as above.  k is an argument, not an instantiation: any finite double.
+template <int B, int HARRIS>
+__global__ __launch_bounds__(CM_T) void corn_map_resp_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+                                                             unsigned *__restrict__ max_key, const uint8_t *const *__restrict__ masks, int mask_pitch,
+                                                             double k)
+{
+    corn_map_body<B, HARRIS>(imgs, first, maps, map_stride, max_key, masks ? masks[blockIdx.y] : nullptr, mask_pitch, k);
 }
 
 __global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_x, CornArgs a)
@@ -379,6 +414,27 @@ __global__ __launch_bounds__(CD_T) void corn_disc_kernel(const float2 *__restric
 }
 
 #ifndef VO_HOST_EMUL
+// the map pass of a response other than (3, min-eigen): masks may be null
+template <int B, int HARRIS>
+static void launch_resp_map(const PyrImage *d_imgs, int first, int n, int w, float *maps, size_t map_stride, unsigned *max_key,
+                            const uint8_t *const *masks, int mask_pitch, double k, hipStream_t stream)
+{
+    constexpr int COLS = CM_T - 2 * (B / 2);
+    hipLaunchKernelGGL((corn_map_resp_kernel<B, HARRIS>), dim3((w + COLS - 1) / COLS, n), dim3(CM_T), 0, stream, d_imgs, first, maps, map_stride, max_key, masks,
+                       mask_pitch, k);
+}
+
+static void launch_resp_map(int block_size, int use_harris, const PyrImage *d_imgs, int first, int n, int w, float *maps, size_t map_stride,
+                            unsigned *max_key, const uint8_t *const *masks, int mask_pitch, double k, hipStream_t stream)
+{
+    if (block_size == 5 && !use_harris)
+        launch_resp_map<5, 0>(d_imgs, first, n, w, maps, map_stride, max_key, masks, mask_pitch, k, stream);
+    else if (block_size == 5)
+        launch_resp_map<5, 1>(d_imgs, first, n, w, maps, map_stride, max_key, masks, mask_pitch, k, stream);
+    else
+        launch_resp_map<3, 1>(d_imgs, first, n, w, maps, map_stride, max_key, masks, mask_pitch, k, stream);
+}
+
 hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream)
 {
     if (n <= 0)
@@ -389,7 +445,9 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
     if (e != hipSuccess)
         return e;
     const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
-    if (a.masks)
+    if (a.block_size != 3 || a.use_harris)
+        launch_resp_map(a.block_size, a.use_harris, d_imgs, first, n, w, a.maps, a.map_stride, a.max_key, a.masks, a.mask_pitch, a.harris_k, stream);
+    else if (a.masks)
         hipLaunchKernelGGL(corn_map_masked_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key,
                            a.masks, a.mask_pitch);
     else
@@ -399,9 +457,12 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
     return hipGetLastError();
 }
 
-void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream)
+void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream, int block_size, int use_harris, double k)
 {
-    hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, 1), dim3(CM_T), 0, stream, d_imgs, image, d_map, (size_t)0, (unsigned *)nullptr);
+    if (block_size != 3 || use_harris)
+        launch_resp_map(block_size, use_harris, d_imgs, image, 1, w, d_map, (size_t)0, (unsigned *)nullptr, (const uint8_t *const *)nullptr, 0, k, stream);
+    else
+        hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, 1), dim3(CM_T), 0, stream, d_imgs, image, d_map, (size_t)0, (unsigned *)nullptr);
 }
 
 hipError_t launch_corner_disc_mask(const float2 *d_kept, int n_kept, int radius, uint8_t *d_mask, int w, int h, hipStream_t stream)

@@ -28,6 +28,11 @@ struct CornArgs {
     const uint8_t *const *masks = nullptr; // [n] the slot's mask (h rows of w bytes, mask_pitch bytes apart; non-zero: allowed), or
                                            // null for a slot without one.  A null table: no slot has one
     int mask_pitch = 0;
+    // goodFeaturesToTrack's blockSize, useHarrisDetector and k (include/vo_corners_response.h).  As initialised here: the 3 x 3
+    // minimum eigenvalue through corn_map_kernel / corn_map_masked_kernel, and the run is what it was.
+    int block_size = 3;   // 3 or 5
+    int use_harris = 0;   // 0: calcMinEigenVal, 1: calcHarris
+    double harris_k = 0.04;
 };
 
 // A float's bits as an unsigned that orders like the float (negative values included): the map maximum by atomicMax, the sort key
@@ -54,10 +59,13 @@ inline int corn_pow2(int n)
 
 #ifndef VO_HOST_EMUL
 // the whole detector over n slots: map + maximum, candidates, sort + suppression + output (three launches on `stream`; max_key and
-// ncand are zeroed first).  Returns the first HIP error of the memsets and launches.  With a.masks the map pass is the masked twin.
+// ncand are zeroed first).  Returns the first HIP error of the memsets and launches.  With a.masks the map pass is the masked twin;
+// with a.block_size / a.use_harris other than (3, 0) it is corn_map_resp_kernel<block_size, use_harris>, masked or not.
 hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream);
-// cv::cornerMinEigenVal of image `image` into map [h][w] (tight)
-void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream);
+// cv::cornerMinEigenVal(img, map, block_size, 3) or cv::cornerHarris(img, map, block_size, 3, k) of image `image` into map [h][w]
+// (tight); block_size 3 or 5
+void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream, int block_size = 3, int use_harris = 0,
+                       double k = 0.04);
 // the disc mask of include/vo_corners_mask.h into mask [h][w] (tight): 0xFF everywhere, then 0 within `radius` of every kept point
 // (a memset and, with n_kept > 0, one launch on `stream`)
 hipError_t launch_corner_disc_mask(const float2 *d_kept, int n_kept, int radius, uint8_t *d_mask, int w, int h, hipStream_t stream);
