@@ -264,3 +264,26 @@ void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats)
         feats.points[i] = cv::Point2f(pts[2 * i], pts[2 * i + 1]);
     feats.ages.assign(ages.begin(), ages.begin() + n_ages);
 }
+
+void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats, bool useGoodFeaturesToTrack)
+{
+    if (!useGoodFeaturesToTrack) {
+        detectAndBucket_hip(image, feats);
+        return;
+    }
+    // appendNewFeatures with its one detector call swapped for featureDetectionGoodFeaturesToTrack (feature.cpp:49-62, its literals
+    // 5000 / 0.01 / 5.0 / 3 / false / 0.04 are the record's defaults): the detector is context state, the adapter's context is
+    // shared by every call of this file, so it is FAST again on every way out
+    vo_ctx* c = ctx_for(image.cols, image.rows, 0);
+    vodet_params det;
+    vodet_default_params(&det);
+    det.detector = VODET_SHI_TOMASI;
+    check(c, vodet_set_params(c, &det));
+    try {
+        detectAndBucket_hip(image, feats);
+    } catch (...) {
+        (void)vodet_set_params(c, NULL);
+        throw;
+    }
+    check(c, vodet_set_params(c, NULL));
+}

@@ -31,6 +31,7 @@
 #include "vo_corners.h"       // ... and its Shi-Tomasi detector
 #include "vo_corners_mask.h"  // ... with goodFeaturesToTrack's mask argument
 #include "vo_corners_response.h" // ... and its blockSize, useHarrisDetector and k
+#include "vo_detector.h"      // ... and the frame loop's choice between FAST and that detector
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -50,6 +51,9 @@ void triangulate_hip(cv::Mat& projMatrl, cv::Mat& projMatrr, std::vector<cv::Poi
 // replaces visualOdometry.cpp:95-108: appendNewFeatures when fewer than 2000 features are carried + bucketingFeatures
 // (bucket_size = rows / 10, one feature per bucket: the reference's literals)
 void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features);
+// ... with appendNewFeatures' detector call swapped for featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) when
+// useGoodFeaturesToTrack is set: carried features, then goodFeaturesToTrack's corners in its own order (vo_detector.h)
+void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features, bool useGoodFeaturesToTrack);
 
 // same signature as featureTracking (feature.h:52): calcOpticalFlowPyrLK(img_1, img_2, ..., 21 x 21, 3, 30 / 0.01, 0, 0.001) +
 // deleteUnmatchFeatures.  points1 / points2 come back compacted, status keeps its length (0 also where a tracked point was

@@ -5,11 +5,12 @@
 // dropped and the trajectory the reference only draws (utils.cpp:19-48) is written in the KITTI pose
 // format (12 doubles per line, what loadPoses reads, evaluate_odometry.cpp:24-27).
 //
-//   vo_run <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out.txt> [features_per_bucket]
+//   vo_run [--detector fast|shi_tomasi] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out.txt> [features_per_bucket]
+//   --detector shi_tomasi: appendNewFeatures detects with goodFeaturesToTrack (include/vo_detector.h)
 //   images: <sequence_dir>/image_0/%06d.pgm (left), image_1/%06d.pgm (right)   (utils.cpp:172-190)
 //
 // build: g++ -O2 -std=c++17 vo_run.cpp -I../include -L../visual_odom_amd -lvo_hip -Wl,-rpath,... -o vo_run
-#include "vo_hip.h"
+#include "vo_detector.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -57,8 +58,15 @@ static std::string frame_path(const std::string &dir, int cam, int id)
 
 int main(int argc, char **argv)
 {
+    int detector = VODET_FAST;
+    if (argc > 2 && !strcmp(argv[1], "--detector") && (!strcmp(argv[2], "fast") || !strcmp(argv[2], "shi_tomasi"))) {
+        detector = !strcmp(argv[2], "fast") ? VODET_FAST : VODET_SHI_TOMASI;
+        argv[2] = argv[0];
+        argv += 2;
+        argc -= 2;
+    }
     if (argc < 8) {
-        fprintf(stderr, "usage: %s <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out> [features_per_bucket [mono_rotation]]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--detector fast|shi_tomasi] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out> [features_per_bucket [mono_rotation]]\n", argv[0]);
         return 1;
     }
     const std::string dir = argv[1];
@@ -80,6 +88,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "vo_create failed: no HIP device (there is no CPU fallback)\n");
         return 2;
     }
+    vodet_params det;
+    vodet_default_params(&det);
+    det.detector = detector;
+    CHECK(vodet_set_params(ctx, &det));
     vo_detect_params dp;
     vo_default_detect_params(&dp);
     if (argc > 8)

@@ -33,9 +33,11 @@
  * pair survives a call with an image of its own size), and the results of an earlier vocorn_batch_run can no longer be fetched
  * (vocorn_batch_get: VO_ERR_STATE).
  *
- * OUT OF SCOPE: gradientSize other than 3, block sizes other than 3 and 5, and any wiring into vo_detect_bucket, vo_seq_* or the
- * frame loop -- the reference's frame loop detects with FAST (visualOdometry.cpp:95-101).  The mask argument is in the sixth header,
- * vo_corners_mask.h; blockSize 5 and the Harris response (useHarrisDetector, k) in the seventh, vo_corners_response.h.
+ * OUT OF SCOPE: gradientSize other than 3, block sizes other than 3 and 5.  The mask argument is in the sixth header,
+ * vo_corners_mask.h; blockSize 5 and the Harris response (useHarrisDetector, k) in the seventh, vo_corners_response.h; the frame
+ * loop (vo_detect_bucket, VO_STAGE_DETECT, vo_seq_*) detects with FAST like the reference's (visualOdometry.cpp:95-101) unless the
+ * eighth, vo_detector.h, selects this detector for it -- the frame path then runs in the buffers of the calls here, and a
+ * vocorn_batch_get after it answers VO_ERR_STATE until the next vocorn_batch_run.
  */
 #ifndef VO_CORNERS_H
 #define VO_CORNERS_H

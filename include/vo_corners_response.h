@@ -32,8 +32,9 @@
  * (float)(max x quality_level) then lies ABOVE the maximum for quality_level < 1 (no corners) and below it for quality_level > 1.
  * Threshold, dilate, sort and suppression are literal about sign, as upstream.
  *
- * OUT OF SCOPE: block sizes that take RowSum's generic branch, gradientSize other than 3, cv::circle-exact discs, and any wiring
- * into vo_detect_bucket, vo_seq_* or the frame loop.
+ * OUT OF SCOPE: block sizes that take RowSum's generic branch, gradientSize other than 3, cv::circle-exact discs.  The frame loop
+ * (vo_detect_bucket, VO_STAGE_DETECT, vo_seq_*) takes this detector, with a response record, through the eighth header,
+ * vo_detector.h.
  */
 #ifndef VO_CORNERS_RESPONSE_H
 #define VO_CORNERS_RESPONSE_H

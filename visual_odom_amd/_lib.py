@@ -52,6 +52,9 @@ CORN_EXPORTS = ("vocorn_default_params", "vocorn_detect", "vocorn_min_eigen_map"
 CMASK_EXPORTS = ("vocmask_detect", "vocmask_disc_mask", "vocmask_replenish", "vocmask_batch_set_mask", "vocmask_batch_set_kept", "vocmask_batch_run")
 # include/vo_corners_response.h: the same detector with goodFeaturesToTrack's blockSize, useHarrisDetector and k, the seventh header
 RESP_EXPORTS = ("voresp_default_params", "voresp_map", "voresp_detect", "voresp_batch_run")
+# include/vo_detector.h: which detector the frame loop appends new features with, the eighth header
+DET_EXPORTS = ("vodet_default_params", "vodet_set_params", "vodet_get_params")
+DETECTORS = {"fast": 0, "shi_tomasi": 1}  # VODET_FAST, VODET_SHI_TOMASI
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -119,6 +122,11 @@ class VoCornParams(C.Structure):
 class VoRespParams(C.Structure):
     """voresp_params (include/vo_corners_response.h)"""
     _fields_ = [("block_size", C.c_int), ("use_harris", C.c_int), ("k", C.c_double)]
+
+
+class VoDetParams(C.Structure):
+    """vodet_params (include/vo_detector.h)"""
+    _fields_ = [("detector", C.c_int), ("corners", VoCornParams), ("response", VoRespParams)]
 
 
 class VoError(RuntimeError):
@@ -189,6 +197,12 @@ def load():
     lib.voresp_detect.argtypes = [vp, vp, i, i, i, vp, i, C.POINTER(VoCornParams), C.POINTER(VoRespParams), vp, i, vp]
     lib.voresp_batch_run.argtypes = [vp, C.POINTER(VoCornParams), C.POINTER(VoRespParams), i, i]
     for name in RESP_EXPORTS[1:]:
+        getattr(lib, name).restype = C.c_int
+    lib.vodet_default_params.argtypes = [C.POINTER(VoDetParams)]
+    lib.vodet_default_params.restype = None
+    lib.vodet_set_params.argtypes = [vp, C.POINTER(VoDetParams)]
+    lib.vodet_get_params.argtypes = [vp, C.POINTER(VoDetParams)]
+    for name in DET_EXPORTS[1:]:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -687,6 +701,25 @@ class Context:
         rsp = VoRespParams(int(block_size), int(bool(use_harris)), float(k))
         self._chk(self.lib.voresp_map(self.h, _pn(img), w, h, stride, C.byref(rsp), _p(out), w))
         return out
+
+    def set_detector(self, detector="fast", max_corners=5000, quality_level=0.01, min_distance=5.0, block_size=3, use_harris=False, k=0.04):
+        """which detector the frame loop appends new features with (vodet_set_params, include/vo_detector.h): "fast" or "shi_tomasi",
+        and goodFeaturesToTrack's arguments for the latter.  Context state: detect_bucket, VO_STAGE_DETECT and the seq_* loop follow
+        it; set it before seq_configure."""
+        if detector not in DETECTORS:
+            raise ValueError("detector: one of %s" % ", ".join(sorted(DETECTORS)))
+        prm = VoDetParams(DETECTORS[detector], VoCornParams(int(max_corners), float(quality_level), float(min_distance)),
+                          VoRespParams(int(block_size), int(bool(use_harris)), float(k)))
+        self._chk(self.lib.vodet_set_params(self.h, C.byref(prm)))
+
+    def get_detector(self):
+        """the record in force (vodet_get_params), as the keyword arguments of set_detector"""
+        prm = VoDetParams()
+        self._chk(self.lib.vodet_get_params(self.h, C.byref(prm)))
+        names = {v: n for n, v in DETECTORS.items()}
+        return dict(detector=names[prm.detector], max_corners=prm.corners.max_corners, quality_level=prm.corners.quality_level,
+                    min_distance=prm.corners.min_distance, block_size=prm.response.block_size, use_harris=bool(prm.response.use_harris),
+                    k=prm.response.k)
 
     def detect_bucket(self, img, pts, ages, **detect_kw):
         """appendNewFeatures (if fewer than redetect_below points) + bucketingFeatures

@@ -7,6 +7,9 @@
 #include "../../include/vo_corners_response.h"
 #include "vo_corners_dev.h"
 
+// The frame loop under VODET_SHI_TOMASI (capi_detector.hip) runs in these buffers too, on the tracking stream or -- the lock-step
+// loop's look-ahead -- on the ingest stream, and clears run_n: its results never come out through vocorn_batch_get.
+//
 // (namespace vo_capi: capi_corners_mask.hip -- vocmask_*, the same detector under a mask -- shares the argument checks, the image
 // set-up, the buffers and the fetch, and capi_corners_response.hip -- voresp_*, the detector with blockSize / useHarrisDetector / k --
 // the calls themselves; they are declared in capi_internal.h)

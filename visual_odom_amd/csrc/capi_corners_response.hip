@@ -8,10 +8,10 @@
 
 #include <math.h>
 
-namespace {
+namespace vo_capi {
 
 // *r: the record to run with.  The defaults are the run the other two headers make.
-int check_resp(vo_ctx *c, const char *who, const voresp_params *in, voresp_params *r)
+int corn_check_resp(vo_ctx *c, const char *who, const voresp_params *in, voresp_params *r)
 {
     if (in)
         *r = *in;
@@ -23,7 +23,7 @@ int check_resp(vo_ctx *c, const char *who, const voresp_params *in, voresp_param
     return VO_OK;
 }
 
-} // namespace
+} // namespace vo_capi
 
 extern "C" {
 
@@ -41,7 +41,7 @@ int voresp_map(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const vo
     if (!c)
         return VO_ERR_ARG;
     voresp_params r;
-    int rc = check_resp(c, "voresp_map", resp, &r);
+    int rc = corn_check_resp(c, "voresp_map", resp, &r);
     if (rc != VO_OK)
         return rc;
     return corn_map(c, "voresp_map", img, w, h, stride, &r, out, out_stride_floats);
@@ -53,7 +53,7 @@ int voresp_detect(vo_ctx *c, const uint8_t *img, int w, int h, int stride, const
     if (!c)
         return VO_ERR_ARG;
     voresp_params r;
-    int rc = check_resp(c, "voresp_detect", resp, &r);
+    int rc = corn_check_resp(c, "voresp_detect", resp, &r);
     if (rc != VO_OK)
         return rc;
     return cmask_detect(c, "voresp_detect", img, w, h, stride, mask, mask_stride, params, &r, pts_out, cap, n_out);
@@ -64,7 +64,7 @@ int voresp_batch_run(vo_ctx *c, const vocorn_params *params, const voresp_params
     if (!c)
         return VO_ERR_ARG;
     voresp_params r;
-    int rc = check_resp(c, "voresp_batch_run", resp, &r);
+    int rc = corn_check_resp(c, "voresp_batch_run", resp, &r);
     if (rc != VO_OK)
         return rc;
     return corn_batch_run(c, "voresp_batch_run", params, first_image, n_images, /*masked*/ true, &r);

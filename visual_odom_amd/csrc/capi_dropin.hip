@@ -331,6 +331,11 @@ int vo_detect_bucket(vo_ctx *c, const uint8_t *img, int w, int h, int stride, co
     VO_HIP_TRY(c, hipStreamSynchronize(c->sel->stream));
     const FeaturesOutLayout L{(size_t)c->cap};
     const int k = peek<int>(c->h_gather + L.count), ovf = peek<int>(c->h_gather + L.overflow);
+    // (include/vo_detector.h) under Shi-Tomasi the corner list is the select pass's and holds at most the capacity: bit 0 can only
+    // mean that the CANDIDATES did not fit, and then no corner was selected at all -- nothing is written
+    if (shi_tomasi(c) && (ovf & 1))
+        return fail(c, VO_ERR_OVERFLOW, "vo_detect_bucket: more goodFeaturesToTrack candidates than the context's corner-list capacity "
+                                        "(max(4 x max_pts, 16384, max_w x max_h / 16)): nothing was written");
     if (k > cap)
         return fail(c, VO_ERR_ARG, "vo_detect_bucket: bucketed set larger than the caller's capacity");
     const int kc = k < c->cap ? k : c->cap;

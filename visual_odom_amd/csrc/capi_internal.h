@@ -1,10 +1,10 @@
 // capi_internal.h -- what the translation units of the C ABI share: the context record, the stream set, small helpers and the
 // internal functions one unit calls in another.  capi.hip: context, allocation, batch API and getters; capi_run.hip: the stage
 // launcher (run_stages); capi_sched.hip: the schedule probe and its export / import; capi_seq.hip: the lock-step sequence
-// loop; capi_dropin.hip: the synchronous drop-in calls.  Round 4 split capi.hip (2 800 lines in one unit)
+// loop; capi_dropin.hip: the synchronous drop-in calls; capi_detector.hip: the frame loop's detector.  Round 4 split capi.hip (2 800 lines in one unit)
 // without changing behaviour.  Nothing declared here is exported: internal functions live in namespace vo_capi.
 #pragma once
-#include "../../include/vo_hip.h"
+#include "../../include/vo_detector.h" // (brings vo_hip.h and the three corner headers)
 #include "vo_kernels.h"
 #include "vo_dev_hooks.h"
 #include "vo_integrate.h"
@@ -26,8 +26,6 @@ using namespace vo;
 namespace vo {
 struct CornArgs; // vo_corners_dev.h
 }
-struct vocorn_params; // include/vo_corners.h
-struct voresp_params; // include/vo_corners_response.h
 
 #define VO_SEQ_INFLIGHT 8 // steps the host may run ahead of the device
 // timing events of one run: [0..3] tracking stream (3 stages), [4..7] post streams (3 stages), [8] start of DETECT on
@@ -349,6 +347,8 @@ struct vo_ctx {
         int run_first = 0, run_n = 0; // image range of the latest vocorn_batch_run (run_n = 0: none since the table was configured)
         int cfg[3] = {0, 0, 0};      // n_images, w, h of the table it ran on
     } corn;
+    // ---- the frame loop's detector (vodet_*, include/vo_detector.h, capi_detector.hip): a CHECKED record ----
+    vodet_params det = {VODET_FAST, {5000, 0.01, 5.0}, {3, 0, 0.04}};
     // ---- the detector's masks (vocmask_*, include/vo_corners_mask.h, capi_corners_mask.hip): allocated by the first such call ----
     struct CornMask {
         bool ready = false;
@@ -566,6 +566,12 @@ int corn_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, in
 int corn_map(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const voresp_params *resp, float *out, int out_stride_floats);
 int corn_batch_run(vo_ctx *c, const char *who, const vocorn_params *params, int first_image, int n_images, bool masked,
                    const voresp_params *resp = nullptr);
+int corn_check_resp(vo_ctx *c, const char *who, const voresp_params *in, voresp_params *r); // (capi_corners_response.hip)
+// the frame loop under VODET_SHI_TOMASI (capi_detector.hip): the candidate buffers for `frames` frames (may drain the context: never
+// inside a lock-step step), and the detector over the frames of `quads` into corners [frames][fcap] / n_out [frames] on `stream`
+inline bool shi_tomasi(const vo_ctx *c) { return c->det.detector == VODET_SHI_TOMASI; }
+int det_ensure(vo_ctx *c, int frames);
+int det_launch(vo_ctx *c, const vo::Quad *quads, const int *d_detect, int frames, float2 *corners, int *n_out, hipStream_t stream);
 int cmask_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride,
                  const vocorn_params *params, const voresp_params *resp, float *pts_out, int cap, int *n_out); // (capi_corners_mask.hip)
 struct DeferGuard { // the deferred t1 pair never outlives the call whose host pointers it holds

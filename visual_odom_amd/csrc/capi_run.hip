@@ -98,6 +98,12 @@ int run_detect(vo_ctx *c, const Run &R)
         int rcr = refuse_detect_shape(c, "vo_batch_run", "VO_STAGE_DETECT");
         if (rcr != VO_OK)
             return rcr;
+        const bool shi = shi_tomasi(c); // include/vo_detector.h: goodFeaturesToTrack in appendNewFeatures' one detector call
+        if (shi && !sq.on) { // (the lock-step loop took its slots in vo_seq_configure)
+            rcr = det_ensure(c, B);
+            if (rcr != VO_OK)
+                return rcr;
+        }
         // appendNewFeatures only when fewer than redetect_below features were carried in (visualOdometry.cpp:95)
         if (R.timed)
             VO_HIP_TRY(c, hipEventRecord(R.evs[stage_events(DET).start], trk));
@@ -133,13 +139,24 @@ int run_detect(vo_ctx *c, const Run &R)
             launch_bucket(c->d_feat, sq.d_corners + (size_t)rp * sq.S * c->fcap, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap,
                           c->w, c->h, bs, fpb, c->d_pts_det[wset], c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active,
                           c->d_overflow, B, trk);
+        } else if (shi) {
+            // the corners in goodFeaturesToTrack's own order into the detector's list, their count -- 0 for a frame that does not
+            // detect again, by the select pass itself -- into d_nnew, and the bucketing in its split form: no copy behind the
+            // carried features.  A candidate list beyond fcap arrives as fcap + 1 corners and leaves as the overflow flag.
+            int rcd = det_launch(c, c->quads_cur, c->d_detect, B, c->corn.d_pts, c->d_nnew, trk);
+            if (rcd != VO_OK)
+                return rcd;
+            launch_bucket(c->d_feat, c->corn.d_pts, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap, c->w, c->h, bs, fpb, c->d_pts_det[wset],
+                          c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active, c->d_overflow, B, trk);
         } else {
             launch_detect_bucket(c->d_imgs, c->quads_cur, c->d_detect, B, c->w, c->h, t, c->dprm.fast_nonmax,
                                  c->d_nmsmask, c->d_rowcnt, c->d_rowoff, c->d_ntracked, c->d_nnew, c->fcap, c->d_feat, c->d_fages, bs, fpb,
                                  c->d_pts_det[wset], c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active,
                                  c->d_overflow, trk);
         }
-        if (sq.on && !R.prep) // (seq_enqueue_inputs: the NEXT step's PCIe ingest waits for this)
+        // (seq_enqueue_inputs: the NEXT step's PCIe ingest waits for this; under Shi-Tomasi so does this step's look-ahead pass,
+        // seq_lookahead, which runs in the candidate buffers an inline detection has just used)
+        if (sq.on && (!R.prep || (shi && !ahead)))
             VO_HIP_TRY(c, sq.detect.record(trk));
         c->pts_sel = wset;
         // the bucketed count is only known on the device; every later grid is sized by its bound

@@ -64,7 +64,8 @@ TuneKey tune_key(const vo_ctx *c, int stages)
     // (the synchronous drop-in call is keyed on the image shape only: a live sequence whose feature count drifts across a
     // bucket boundary must not pay a probe -- ~20 frame times -- in the middle of real-time use)
     key.k[6] = (c->sync_call && !c->seq.on) ? 0 : pts_bucket(pts);
-    key.k[7] = (c->prm.mono_rotation ? 1 : 0) | ((stages & VO_STAGE_DETECT) ? 2 : 0) | (c->sync_call && !c->seq.on ? 16 : 0);
+    // (bit 5: the frame loop's detector -- a schedule probed under FAST is neither reused nor overwritten by a Shi-Tomasi context)
+    key.k[7] = (c->prm.mono_rotation ? 1 : 0) | ((stages & VO_STAGE_DETECT) ? 2 : 0) | (c->sync_call && !c->seq.on ? 16 : 0) | (shi_tomasi(c) ? 32 : 0);
     return key;
 }
 
@@ -241,9 +242,19 @@ int seq_lookahead(vo_ctx *c, int r)
     vo_ctx::Seq &q = c->seq;
     int t = c->dprm.fast_threshold;
     t = t < 0 ? 0 : t > 255 ? 255 : t;
-    launch_fast_corners(c->d_imgs, q.d_quads + (size_t)r * q.S, nullptr, q.S, c->w, c->h, t, c->dprm.fast_nonmax,
-                        c->d_nmsmask, c->d_rowcnt, c->d_rowoff, nullptr, q.d_ncorn + (size_t)r * q.S, c->fcap,
-                        q.d_corners + (size_t)r * q.S * c->fcap, ingest_stream(c));
+    if (shi_tomasi(c)) {
+        // (include/vo_detector.h) goodFeaturesToTrack of every pair's left image into the ring slot's corner list, every frame
+        // (which sequence detects again is known one step later: seq_prepare_kernel).  The candidate buffers are the ones an inline
+        // detection of the step just enqueued may still use on the tracking stream: behind it.
+        VO_HIP_TRY(c, q.detect.wait(ingest_stream(c)));
+        int rc = det_launch(c, q.d_quads + (size_t)r * q.S, nullptr, q.S, q.d_corners + (size_t)r * q.S * c->fcap, q.d_ncorn + (size_t)r * q.S,
+                            ingest_stream(c));
+        if (rc != VO_OK)
+            return rc;
+    } else
+        launch_fast_corners(c->d_imgs, q.d_quads + (size_t)r * q.S, nullptr, q.S, c->w, c->h, t, c->dprm.fast_nonmax,
+                            c->d_nmsmask, c->d_rowcnt, c->d_rowoff, nullptr, q.d_ncorn + (size_t)r * q.S, c->fcap,
+                            q.d_corners + (size_t)r * q.S * c->fcap, ingest_stream(c));
     VO_HIP_TRY(c, q.fast[r].record(ingest_stream(c)));
     q.have_corners[r] = true;
     VO_HIP_TRY(c, hipGetLastError());

@@ -13,6 +13,11 @@
 // and goodFeaturesToTrack's blockSize, useHarrisDetector and k (include/vo_corners_response.h; tests/host_check/corners_response_ref.c):
 //   corn_map_resp_kernel<B, HARRIS>  the map kernel at blockSize 5 and / or with calcHarris's response, masked or not; the
 //                        candidate and select kernels take whatever map comes in, negative values included
+// and the FRAMES form of the three passes for the frame loop (include/vo_detector.h):
+//   corn_map_frames_kernel<B, HARRIS>, corn_cand_frames_kernel, corn_select_frames_kernel
+//                        slot = frame, image = quads[frame].l0; a frame whose detect flag is 0 leaves all three at once and reports
+//                        no corner; a candidate list beyond lcap is reported as lcap + 1 corners, the count bucket_kernel's split
+//                        form turns into the frame's overflow flag.  The bodies are the ones above.
 //
 // Why a thread per column.  boxFilter sums the f32 products in f64, and its column pass (ColumnSum<double, float>) is a RUNNING sum
 // down the whole column: SUM += row(y + 1); out = SUM; SUM -= row(y - 1).  The f64 operations are not exact in general -- a dy of
@@ -53,7 +58,7 @@ __device__ __forceinline__ int corn_clamp(int v, int lo, int hi) { return v < lo
 // B = 5 that is 12 doubles; in LDS they would cost 24 KiB per workgroup and an address per access).  HARRIS: calcHarris in place of
 // calcMinEigenVal; k is read by it alone.  (3, false) is cv::cornerMinEigenVal(img, eig, 3, 3) as it always was.
 template <int B, int HARRIS>
-__device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
+__device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs, int image, float *__restrict__ maps, size_t map_stride,
                                               unsigned *__restrict__ max_key, const uint8_t *__restrict__ mask, int mask_pitch, double k)
 {
     static_assert(B == 3 || B == 5, "RowSum's left-to-right branches");
@@ -61,7 +66,7 @@ __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs,
     __shared__ float s_cov[3][CM_T];
     __shared__ unsigned s_max;
     const int tid = threadIdx.x, slot = blockIdx.y;
-    const PyrImage &im = imgs[first + slot];
+    const PyrImage &im = imgs[image];
     const int w = im.w[0], h = im.h[0], stride = im.stride[0];
     const VO_GLOBAL uint8_t *__restrict__ src = (const VO_GLOBAL uint8_t *)im.lvl[0];
     float *__restrict__ map = maps + (size_t)slot * map_stride;
@@ -156,14 +161,14 @@ __device__ __forceinline__ void corn_map_body(const PyrImage *__restrict__ imgs,
 __global__ __launch_bounds__(CM_T) void corn_map_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
                                                         unsigned *__restrict__ max_key)
 {
-    corn_map_body<3, 0>(imgs, first, maps, map_stride, max_key, nullptr, 0, 0.0);
+    corn_map_body<3, 0>(imgs, first + (int)blockIdx.y, maps, map_stride, max_key, nullptr, 0, 0.0);
 }
 
 // ... under masks [n] (CornArgs::masks: a slot's entry may be null)
 __global__ __launch_bounds__(CM_T) void corn_map_masked_kernel(const PyrImage *__restrict__ imgs, int first, float *__restrict__ maps, size_t map_stride,
                                                                unsigned *__restrict__ max_key, const uint8_t *const *__restrict__ masks, int mask_pitch)
 {
-    corn_map_body<3, 0>(imgs, first, maps, map_stride, max_key, masks[blockIdx.y], mask_pitch, 0.0);
+    corn_map_body<3, 0>(imgs, first + (int)blockIdx.y, maps, map_stride, max_key, masks[blockIdx.y], mask_pitch, 0.0);
 }
 
 // The response maps of include/vo_corners_response.h: cornerMinEigenVal at blockSize 5, cornerHarris at 3 and 5.  masks: null, or
@@ -173,10 +178,22 @@ __global__ __launch_bounds__(CM_T) void corn_map_resp_kernel(const PyrImage *__r
                                                              unsigned *__restrict__ max_key, const uint8_t *const *__restrict__ masks, int mask_pitch,
                                                              double k)
 {
-    corn_map_body<B, HARRIS>(imgs, first, maps, map_stride, max_key, masks ? masks[blockIdx.y] : nullptr, mask_pitch, k);
+    corn_map_body<B, HARRIS>(imgs, first + (int)blockIdx.y, maps, map_stride, max_key, masks ? masks[blockIdx.y] : nullptr, mask_pitch, k);
 }
 
-__global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_x, CornArgs a)
+// The frames form (include/vo_detector.h): slot = frame, its image the left t0 image of the frame's quadruple -- what FAST reads in
+// the same call.  detect: null (every frame), or the frames' flags as seq_prepare_kernel / the host wrote them; a frame that does
+// not detect again costs the launch of its workgroups and nothing else.  (3, 0) is corn_map_kernel's body.
+template <int B, int HARRIS>
+__global__ __launch_bounds__(CM_T) void corn_map_frames_kernel(const PyrImage *__restrict__ imgs, const Quad *__restrict__ quads, const int *__restrict__ detect,
+                                                               float *__restrict__ maps, size_t map_stride, unsigned *__restrict__ max_key, double k)
+{
+    if (detect && !detect[blockIdx.y]) // (uniform)
+        return;
+    corn_map_body<B, HARRIS>(imgs, quads[blockIdx.y].l0, maps, map_stride, max_key, nullptr, 0, k);
+}
+
+__device__ __forceinline__ void corn_cand_body(int w, int h, int tiles_x, const CornArgs &a)
 {
     __shared__ float s_val[CV_H * CV_W];
     __shared__ unsigned long long s_list[CT_W * CT_H];
@@ -223,6 +240,16 @@ __global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_
             keys[s_base + i] = s_list[i];
 }
 
+__global__ __launch_bounds__(256) void corn_cand_kernel(int w, int h, int tiles_x, CornArgs a) { corn_cand_body(w, h, tiles_x, a); }
+
+// ... of the frames form: detect as in corn_map_frames_kernel
+__global__ __launch_bounds__(256) void corn_cand_frames_kernel(int w, int h, int tiles_x, CornArgs a, const int *__restrict__ detect)
+{
+    if (detect && !detect[blockIdx.y]) // (uniform)
+        return;
+    corn_cand_body(w, h, tiles_x, a);
+}
+
 // bitonic sort of keys[0 .. n), n a power of two, by the whole workgroup (every key is distinct)
 __device__ void corn_sort(unsigned long long *keys, int n, bool descending)
 {
@@ -254,7 +281,9 @@ __device__ void corn_sort(unsigned long long *keys, int n, bool descending)
 //   cells       found through a second sorted list (cell, rank): the three cell rows around a candidate are three contiguous
 //               ranges of it, each by one binary search.  O(candidates) memory whatever the cell size.
 //   maxCorners  the loop stops at maxCorners accepted = the first maxCorners accepted in rank order.
-__global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornArgs a, int w, int h)
+//   overflow    what nout reports for a candidate list beyond lcap: -1 in the detector's own calls (the host answers
+//               VO_ERR_OVERFLOW), lcap + 1 in the frames form
+__device__ __forceinline__ void corn_select_body(const CornArgs &a, int w, int h, int overflow)
 {
     __shared__ int s_part[CORN_SELECT_THREADS];
     __shared__ int s_flag[3];
@@ -262,7 +291,7 @@ __global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornAr
     const int n = a.ncand[slot];
     if (n > a.lcap) { // (uniform) nothing is silently truncated: the host reports VO_ERR_OVERFLOW
         if (tid == 0) {
-            a.nout[slot] = -1;
+            a.nout[slot] = overflow;
             if (a.rounds)
                 a.rounds[slot] = 0;
         }
@@ -385,6 +414,25 @@ __global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornAr
     }
 }
 
+__global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_kernel(CornArgs a, int w, int h) { corn_select_body(a, w, h, -1); }
+
+// ... of the frames form: a.pts / a.nout are the frame loop's corner list and count ([frames][lcap] and [frames], the layout of
+// bucket_kernel's split form).  A frame that does not detect again appends nothing: nout = 0.  A candidate list beyond lcap comes out
+// as lcap + 1 corners: no list holds that many, so seq_prepare_kernel hands the count on as it is and bucket_kernel's `n_new > cap`
+// sets bit 0 of the frame's overflow flag -- the way a FAST list that did not fit is reported.
+__global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_frames_kernel(CornArgs a, int w, int h, const int *__restrict__ detect)
+{
+    if (detect && !detect[blockIdx.x]) { // (uniform)
+        if (threadIdx.x == 0) {
+            a.nout[blockIdx.x] = 0;
+            if (a.rounds)
+                a.rounds[blockIdx.x] = 0;
+        }
+        return;
+    }
+    corn_select_body(a, w, h, a.lcap + 1);
+}
+
 // The disc mask of include/vo_corners_mask.h over a mask that holds 0xFF: one wavefront per kept point writes zeros over the part of
 // its disc that lies inside the image.  Centre (cvRound(x), cvRound(y)), round-half-to-even; a point with a NaN, infinite or
 // |coordinate| >= 2^30 is skipped; pixel (px, py) is cleared iff (px - cx)^2 + (py - cy)^2 <= radius^2 in integers (inside the clipped
@@ -454,6 +502,37 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
         hipLaunchKernelGGL(corn_map_kernel, dim3((w + CM_COLS - 1) / CM_COLS, n), dim3(CM_T), 0, stream, d_imgs, first, a.maps, a.map_stride, a.max_key);
     hipLaunchKernelGGL(corn_cand_kernel,dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a);
     hipLaunchKernelGGL(corn_select_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h);
+    return hipGetLastError();
+}
+
+template <int B, int HARRIS>
+static void launch_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, hipStream_t stream)
+{
+    constexpr int COLS = CM_T - 2 * (B / 2);
+    hipLaunchKernelGGL((corn_map_frames_kernel<B, HARRIS>), dim3((w + COLS - 1) / COLS, n), dim3(CM_T), 0, stream, d_imgs, d_quads, d_detect, a.maps,
+                       a.map_stride, a.max_key, a.harris_k);
+}
+
+hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, int h, const CornArgs &a, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    hipError_t e = hipMemsetAsync(a.max_key, 0, sizeof(unsigned) * (size_t)n, stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.ncand, 0, sizeof(int) * (size_t)n, stream);
+    if (e != hipSuccess)
+        return e;
+    const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
+    if (a.block_size == 5 && !a.use_harris)
+        launch_frames_map<5, 0>(d_imgs, d_quads, d_detect, n, w, a, stream);
+    else if (a.block_size == 5)
+        launch_frames_map<5, 1>(d_imgs, d_quads, d_detect, n, w, a, stream);
+    else if (a.use_harris)
+        launch_frames_map<3, 1>(d_imgs, d_quads, d_detect, n, w, a, stream);
+    else
+        launch_frames_map<3, 0>(d_imgs, d_quads, d_detect, n, w, a, stream);
+    hipLaunchKernelGGL(corn_cand_frames_kernel, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a, d_detect);
+    hipLaunchKernelGGL(corn_select_frames_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h, d_detect);
     return hipGetLastError();
 }
 

@@ -11,7 +11,7 @@ namespace vo {
 struct CornArgs {
     unsigned *max_key;         // [n] ordered bits (corn_ord) of the quality map's maximum; 0 before the run
     int *ncand;                // [n] candidates that passed the threshold (may exceed lcap: nothing beyond it is stored); 0 before
-    int *nout;                 // [n] corners found, -1: the candidate list overflowed
+    int *nout;                 // [n] corners found, -1: the candidate list overflowed (frames form: lcap + 1)
     int *rounds;               // [n] rounds the suppression took, or null (the library does not ask; the emulator harness does)
     float *maps;               // [n][map_stride] the quality maps, rows tight (w floats)
     size_t map_stride;
@@ -62,6 +62,12 @@ inline int corn_pow2(int n)
 // ncand are zeroed first).  Returns the first HIP error of the memsets and launches.  With a.masks the map pass is the masked twin;
 // with a.block_size / a.use_harris other than (3, 0) it is corn_map_resp_kernel<block_size, use_harris>, masked or not.
 hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h, const CornArgs &a, hipStream_t stream);
+// The same three passes in the FRAMES form (the frame loop, include/vo_detector.h): slot = frame, image = d_quads[frame].l0, and
+// d_detect (null: every frame) the frames' "detect again" flags on the device.  a.pts / a.nout point at the loop's own corner list
+// [n][a.lcap] and count [n] (bucket_kernel's split form reads them); a frame that does not detect gets nout = 0, a candidate list
+// beyond a.lcap nout = a.lcap + 1 (which bucket_kernel reports as the frame's list overflow).  a.masks is not read.
+hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, int h, const CornArgs &a,
+                                 hipStream_t stream);
 // cv::cornerMinEigenVal(img, map, block_size, 3) or cv::cornerHarris(img, map, block_size, 3, k) of image `image` into map [h][w]
 // (tight); block_size 3 or 5
 void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream, int block_size = 3, int use_harris = 0,
