@@ -265,7 +265,7 @@ void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats)
     feats.ages.assign(ages.begin(), ages.begin() + n_ages);
 }
 
-void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats, bool useGoodFeaturesToTrack)
+void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats, bool useGoodFeaturesToTrack, int topupRadius)
 {
     if (!useGoodFeaturesToTrack) {
         detectAndBucket_hip(image, feats);
@@ -273,17 +273,23 @@ void detectAndBucket_hip(cv::Mat& image, FeatureSet& feats, bool useGoodFeatures
     }
     // appendNewFeatures with its one detector call swapped for featureDetectionGoodFeaturesToTrack (feature.cpp:49-62, its literals
     // 5000 / 0.01 / 5.0 / 3 / false / 0.04 are the record's defaults): the detector is context state, the adapter's context is
-    // shared by every call of this file, so it is FAST again on every way out
+    // shared by every call of this file, so it is FAST again on every way out -- and the top-up (vo_topup.h) off again
     vo_ctx* c = ctx_for(image.cols, image.rows, 0);
     vodet_params det;
     vodet_default_params(&det);
     det.detector = VODET_SHI_TOMASI;
     check(c, vodet_set_params(c, &det));
     try {
+        if (topupRadius >= 0) {
+            votop_params top = {VOTOP_CARRIED, topupRadius};
+            check(c, votop_set_params(c, &top));
+        }
         detectAndBucket_hip(image, feats);
     } catch (...) {
         (void)vodet_set_params(c, NULL);
+        (void)votop_set_params(c, NULL);
         throw;
     }
     check(c, vodet_set_params(c, NULL));
+    check(c, votop_set_params(c, NULL));
 }

@@ -32,6 +32,7 @@
 #include "vo_corners_mask.h"  // ... with goodFeaturesToTrack's mask argument
 #include "vo_corners_response.h" // ... and its blockSize, useHarrisDetector and k
 #include "vo_detector.h"      // ... and the frame loop's choice between FAST and that detector
+#include "vo_topup.h"         // ... and that detector's top-up under a mask of the carried points
 
 // same signature as circularMatching (feature.h:61-65)
 void circularMatching_hip(cv::Mat img_l_0, cv::Mat img_r_0, cv::Mat img_l_1, cv::Mat img_r_1,
@@ -52,8 +53,9 @@ void triangulate_hip(cv::Mat& projMatrl, cv::Mat& projMatrr, std::vector<cv::Poi
 // (bucket_size = rows / 10, one feature per bucket: the reference's literals)
 void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features);
 // ... with appendNewFeatures' detector call swapped for featureDetectionGoodFeaturesToTrack (feature.cpp:49-62) when
-// useGoodFeaturesToTrack is set: carried features, then goodFeaturesToTrack's corners in its own order (vo_detector.h)
-void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features, bool useGoodFeaturesToTrack);
+// useGoodFeaturesToTrack is set: carried features, then goodFeaturesToTrack's corners in its own order (vo_detector.h).
+// topupRadius >= 0: that call under the disc mask, radius topupRadius, of current_features.points (vo_topup.h); -1: no mask
+void detectAndBucket_hip(cv::Mat& image, FeatureSet& current_features, bool useGoodFeaturesToTrack, int topupRadius = -1);
 
 // same signature as featureTracking (feature.h:52): calcOpticalFlowPyrLK(img_1, img_2, ..., 21 x 21, 3, 30 / 0.01, 0, 0.001) +
 // deleteUnmatchFeatures.  points1 / points2 come back compacted, status keeps its length (0 also where a tracked point was

@@ -8,7 +8,7 @@
 // simply stops, like the reference's loop ends when imread fails.
 #pragma once
 
-#include "vo_detector.h"
+#include "vo_topup.h"
 #include "vo_io.h"
 
 #include <algorithm>
@@ -36,9 +36,10 @@ struct WorkerResult {
 // device_convert: the decoded RGB rows go to the library as they are (vo_params.input_format = VO_FMT_RGB8, the colour
 // conversion runs in the ingest kernel) instead of being folded to gray by the decoder threads
 // detector: VODET_FAST, or VODET_SHI_TOMASI -- appendNewFeatures with featureDetectionGoodFeaturesToTrack and its literals
-// (include/vo_detector.h)
+// (include/vo_detector.h); topup_radius >= 0: that call under the disc mask of the points each frame carries in (include/vo_topup.h)
 inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs, const Calib &cal, int max_frames,
-                               int features_per_bucket, int decode_threads, bool device_convert = false, int detector = VODET_FAST)
+                               int features_per_bucket, int decode_threads, bool device_convert = false, int detector = VODET_FAST,
+                               int topup_radius = -1)
 {
     WorkerResult out;
     out.device = device;
@@ -87,6 +88,11 @@ inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs,
     det.detector = detector;
     if ((rc = vodet_set_params(ctx, &det)) < 0) // before vo_seq_configure too: inside the loop it is VO_ERR_STATE
         return fail("vodet_set_params", rc);
+    if (topup_radius >= 0) {
+        const votop_params top = {VOTOP_CARRIED, topup_radius};
+        if ((rc = votop_set_params(ctx, &top)) < 0) // before vo_seq_configure as well: the loop takes its mask planes there
+            return fail("votop_set_params", rc);
+    }
     if ((rc = vo_seq_configure(ctx, S, w, h, /*ring*/ 3, max_frames + 1)) < 0)
         return fail("vo_seq_configure", rc);
     if ((rc = vo_batch_set_projection(ctx, P_l, P_r)) < 0)

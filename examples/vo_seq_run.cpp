@@ -5,11 +5,12 @@
 // on one GPU (examples/vo_seq_host.h); examples/vo_multi_gpu.cpp runs one such worker per GPU (BASELINE "config 5").
 // Sequences may have different lengths: a sequence whose images run out simply stops.
 //
-//   vo_seq_run [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> <out_prefix>
+//   vo_seq_run [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> <out_prefix>
 //              <sequence_dir> [<sequence_dir> ...]
 //   images:  <sequence_dir>/image_0/%06d.png (left), image_1/%06d.png (right), or .pgm         (utils.cpp:172-190)
 //            --device-convert 1: an RGB PNG is handed over as RGB and the library converts it on the GPU (VO_FMT_RGB8)
 //            --detector shi_tomasi: appendNewFeatures detects with goodFeaturesToTrack (include/vo_detector.h)
+//            --topup-radius R: ... under the disc mask, radius R, of the points each frame carries in (include/vo_topup.h)
 //   output:  <out_prefix>_<s>.txt, KITTI pose format (12 doubles per line, evaluate_odometry.cpp:24-27);
 //            stderr: end-to-end frames/s from the files (read + decode + upload + compute) and the time the loop spent
 //            waiting for the decoders
@@ -22,7 +23,7 @@
 
 int main(int argc, char **argv)
 {
-    int device = 0, decode_threads = 4, a = 1, detector = VODET_FAST;
+    int device = 0, decode_threads = 4, a = 1, detector = VODET_FAST, topup_radius = -1;
     bool device_convert = false;
     while (a + 1 < argc && !strncmp(argv[a], "--", 2)) {
         if (!strcmp(argv[a], "--device"))
@@ -33,12 +34,14 @@ int main(int argc, char **argv)
             device_convert = atoi(argv[a + 1]) != 0;
         else if (!strcmp(argv[a], "--detector") && (!strcmp(argv[a + 1], "fast") || !strcmp(argv[a + 1], "shi_tomasi")))
             detector = !strcmp(argv[a + 1], "fast") ? VODET_FAST : VODET_SHI_TOMASI;
+        else if (!strcmp(argv[a], "--topup-radius"))
+            topup_radius = atoi(argv[a + 1]);
         else
             break;
         a += 2;
     }
     if (argc - a < 8) {
-        fprintf(stderr, "usage: %s [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> "
+        fprintf(stderr, "usage: %s [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> "
                         "<out_prefix> <sequence_dir> ...\n", argv[0]);
         return 1;
     }
@@ -50,7 +53,7 @@ int main(int argc, char **argv)
     const int max_frames = atoi(argv[a + 4]), per_bucket = atoi(argv[a + 5]);
     const std::string prefix = argv[a + 6];
     std::vector<std::string> dirs(argv + a + 7, argv + argc);
-    vohost::WorkerResult r = vohost::run_worker(device, dirs, cal, max_frames, per_bucket, decode_threads, device_convert, detector);
+    vohost::WorkerResult r = vohost::run_worker(device, dirs, cal, max_frames, per_bucket, decode_threads, device_convert, detector, topup_radius);
     if (r.rc) {
         fprintf(stderr, "%s\n", r.error.c_str());
         return r.rc;

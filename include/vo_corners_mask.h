@@ -41,9 +41,9 @@
  * The device memory for the masks (one mask of max_w x max_h bytes and one point list per image of the table) is allocated by the
  * first vocmask_* call; a context that never makes one allocates and launches what it always did.
  *
- * OUT OF SCOPE: cv::circle-exact discs, and masks in the frame loop: vo_detector.h, the eighth header, puts this detector into
- * vo_detect_bucket, VO_STAGE_DETECT and vo_seq_* WITHOUT a mask (the look-ahead of the lock-step loop detects before the step's
- * carried set exists).  blockSize 5 and the Harris response are in the seventh header, vo_corners_response.h, whose calls run
+ * OUT OF SCOPE: cv::circle-exact discs.  IN THE FRAME LOOP: vo_detector.h, the eighth header, puts this detector into
+ * vo_detect_bucket, VO_STAGE_DETECT and vo_seq_*, and vo_topup.h, the ninth, runs it there under the disc mask of the points each
+ * frame carries in.  blockSize 5 and the Harris response are in the seventh header, vo_corners_response.h, whose calls run
  * under these masks.
  */
 #ifndef VO_CORNERS_MASK_H

@@ -34,8 +34,10 @@
  * SCHEDULES.  A Shi-Tomasi context neither reuses nor overwrites the schedules probed under FAST (the detector is part of the
  * probe's key), and the lock-step probe times the detector the loop will run.
  *
- * OUT OF SCOPE: masks in the frame loop (top-up away from the carried points: the look-ahead detects before the step's carried set
- * exists), a latency form of the map pass for one or a few images, and what vo_corners_response.h leaves out.
+ * THE TOP-UP AWAY FROM THE CARRIED POINTS -- the same call under the disc mask of the points a frame carries in -- is vo_topup.h, the
+ * ninth header; without it the call takes noArray().
+ *
+ * OUT OF SCOPE: a latency form of the map pass for one or a few images, and what vo_corners_response.h leaves out.
  */
 #ifndef VO_DETECTOR_H
 #define VO_DETECTOR_H

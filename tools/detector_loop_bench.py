@@ -12,8 +12,11 @@ THE COMPARISON WITH THE PARENT COMMIT.  `--tree DIR` measures the visual_odom_am
 checkout; a tree without vodet_* runs the FAST legs only.  Build both, alternate them in one session -- parent, this, parent, this,
 `--detectors fast` -- and hold every median of this commit against the parent's largest repeat (DESIGN 3.14's rule).
 
-    python tools/detector_loop_bench.py [--tree DIR] [--detectors fast,shi_tomasi] [--legs sync,seq256,seq64,seq8] [--runs 10] [--repeats 5]
-                                        [--json out.json] [--md profiles/detector_loop.md]
+`--topup-radius R` adds a third column where the tree has votop_* (include/vo_topup.h): shi_tomasi with the top-up under the disc mask,
+radius R, of the carried points -- named shi_tomasi+top in the tables.  The Shi-Tomasi legs beside it run with the top-up off.
+
+    python tools/detector_loop_bench.py [--tree DIR] [--detectors fast,shi_tomasi] [--topup-radius R] [--legs sync,seq256,seq64,seq8]
+                                        [--runs 10] [--repeats 5] [--json out.json] [--md profiles/detector_loop.md]
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--detectors", default="fast,shi_tomasi")
+    ap.add_argument("--topup-radius", type=int, default=None)
     ap.add_argument("--legs", default="sync,seq256,seq64,seq8")
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
@@ -53,6 +57,9 @@ def main():
     assert os.path.abspath(_lib.__file__).startswith(os.path.abspath(args.tree)), "the package of --tree is the one measured"
     has_det = hasattr(_lib, "DET_EXPORTS")
     detectors = [d for d in args.detectors.split(",") if d == "fast" or (d == "shi_tomasi" and has_det)]
+    if args.topup_radius is not None and has_det and hasattr(_lib, "TOPUP_EXPORTS"):
+        detectors.append("shi_tomasi+top")
+    top_kw = lambda det: dict(topup_radius=args.topup_radius) if det.endswith("+top") else {}
     world = synth.StereoWorld(seed=20260925)
     lefts, rights, _, _ = world.render_sequence(Q + 1)
     P_l, P_r = world.proj_matrices()
@@ -63,7 +70,7 @@ def main():
     out = dict(tree=os.path.abspath(args.tree), w=W, h=H, runs=args.runs, repeats=args.repeats, legs={})
 
     def sync_leg(det):
-        vo = odometry.StereoOdometry(P_l, P_r, max_w=W, max_h=H, **(dict(detector=det) if has_det else {}))
+        vo = odometry.StereoOdometry(P_l, P_r, max_w=W, max_h=H, **(dict(detector=det.split("+")[0], **top_kw(det)) if has_det else {}))
         try:
             k = 0
             for _ in range(2 * args.runs):   # warm-up: the schedule of the synchronous calls settles in their first frames
@@ -87,7 +94,9 @@ def main():
         try:
             ctx.batch_set_detect_params(features_per_bucket=1)
             if has_det:
-                ctx.set_detector(det)
+                ctx.set_detector(det.split("+")[0])
+            if det.endswith("+top"):
+                ctx.set_topup(radius=args.topup_radius)
             ctx.seq_configure(S, W, H, 3, (args.repeats + 3) * args.runs + 600)
             ctx.batch_set_projection(P_l, P_r)
             tables = [ctx.seq_pair_table(range(S), [ptrs[tri(k + s, Q)][0] for s in range(S)], [ptrs[tri(k + s, Q)][1] for s in range(S)])
@@ -136,7 +145,7 @@ def main():
         for det in detectors:
             r = sync_leg(det) if leg == "sync" else seq_leg(det, int(leg[3:]))
             out["legs"]["%s/%s" % (leg, det)] = r
-            print("%-8s %-10s %8.3f ms (min %.3f, max %.3f over %d repeats of %d)%s  bucketed %s" %
+            print("%-8s %-14s %8.3f ms (min %.3f, max %.3f over %d repeats of %d)%s  bucketed %s" %
                   (leg, det, r["median_ms"], r["min_ms"], r["max_ms"], r["n"], args.runs, "  schedule " + r["schedule"] if "schedule" in r else "",
                    r["n_bucketed"]), flush=True)
     if args.json:

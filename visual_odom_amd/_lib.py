@@ -55,6 +55,9 @@ RESP_EXPORTS = ("voresp_default_params", "voresp_map", "voresp_detect", "voresp_
 # include/vo_detector.h: which detector the frame loop appends new features with, the eighth header
 DET_EXPORTS = ("vodet_default_params", "vodet_set_params", "vodet_get_params")
 DETECTORS = {"fast": 0, "shi_tomasi": 1}  # VODET_FAST, VODET_SHI_TOMASI
+# include/vo_topup.h: the frame loop's top-up under a mask of the carried points, the ninth header
+TOPUP_EXPORTS = ("votop_default_params", "votop_set_params", "votop_get_params", "votop_get_mask")
+TOPUP_MODES = {"off": 0, "carried": 1}  # VOTOP_OFF, VOTOP_CARRIED
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -127,6 +130,11 @@ class VoRespParams(C.Structure):
 class VoDetParams(C.Structure):
     """vodet_params (include/vo_detector.h)"""
     _fields_ = [("detector", C.c_int), ("corners", VoCornParams), ("response", VoRespParams)]
+
+
+class VoTopParams(C.Structure):
+    """votop_params (include/vo_topup.h)"""
+    _fields_ = [("mode", C.c_int), ("radius", C.c_int)]
 
 
 class VoError(RuntimeError):
@@ -203,6 +211,13 @@ def load():
     lib.vodet_set_params.argtypes = [vp, C.POINTER(VoDetParams)]
     lib.vodet_get_params.argtypes = [vp, C.POINTER(VoDetParams)]
     for name in DET_EXPORTS[1:]:
+        getattr(lib, name).restype = C.c_int
+    lib.votop_default_params.argtypes = [C.POINTER(VoTopParams)]
+    lib.votop_default_params.restype = None
+    lib.votop_set_params.argtypes = [vp, C.POINTER(VoTopParams)]
+    lib.votop_get_params.argtypes = [vp, C.POINTER(VoTopParams)]
+    lib.votop_get_mask.argtypes = [vp, i, vp, i]
+    for name in TOPUP_EXPORTS[1:]:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
@@ -720,6 +735,27 @@ class Context:
         return dict(detector=names[prm.detector], max_corners=prm.corners.max_corners, quality_level=prm.corners.quality_level,
                     min_distance=prm.corners.min_distance, block_size=prm.response.block_size, use_harris=bool(prm.response.use_harris),
                     k=prm.response.k)
+
+    def set_topup(self, radius=5, mode="carried"):
+        """the frame loop's top-up under a mask of the carried points (votop_set_params, include/vo_topup.h): under the Shi-Tomasi
+        detector, new corners only further than `radius` from every point a frame carries in.  mode "off": as without.  Context
+        state: detect_bucket, VO_STAGE_DETECT and the seq_* loop follow it; set it before seq_configure."""
+        if mode not in TOPUP_MODES:
+            raise ValueError("mode: one of %s" % ", ".join(sorted(TOPUP_MODES)))
+        prm = VoTopParams(TOPUP_MODES[mode], int(radius))
+        self._chk(self.lib.votop_set_params(self.h, C.byref(prm)))
+
+    def get_topup(self):
+        """the record in force (votop_get_params), as the keyword arguments of set_topup"""
+        prm = VoTopParams()
+        self._chk(self.lib.votop_get_params(self.h, C.byref(prm)))
+        return dict(radius=prm.radius, mode={v: n for n, v in TOPUP_MODES.items()}[prm.mode])
+
+    def topup_mask(self, frame, w, h):
+        """the (h, w) mask plane the last detect_bucket (frame 0) or VO_STAGE_DETECT built for `frame` (votop_get_mask)"""
+        out = np.zeros((h, w), np.uint8)
+        self._chk(self.lib.votop_get_mask(self.h, int(frame), _p(out), w))
+        return out
 
     def detect_bucket(self, img, pts, ages, **detect_kw):
         """appendNewFeatures (if fewer than redetect_below points) + bucketingFeatures

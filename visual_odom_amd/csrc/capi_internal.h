@@ -4,7 +4,7 @@
 // loop; capi_dropin.hip: the synchronous drop-in calls; capi_detector.hip: the frame loop's detector.  Round 4 split capi.hip (2 800 lines in one unit)
 // without changing behaviour.  Nothing declared here is exported: internal functions live in namespace vo_capi.
 #pragma once
-#include "../../include/vo_detector.h" // (brings vo_hip.h and the three corner headers)
+#include "../../include/vo_topup.h" // (brings vo_detector.h, vo_hip.h and the three corner headers)
 #include "vo_kernels.h"
 #include "vo_dev_hooks.h"
 #include "vo_integrate.h"
@@ -349,6 +349,17 @@ struct vo_ctx {
     } corn;
     // ---- the frame loop's detector (vodet_*, include/vo_detector.h, capi_detector.hip): a CHECKED record ----
     vodet_params det = {VODET_FAST, {5000, 0.01, 5.0}, {3, 0, 0.04}};
+    // ---- the frame loop's top-up under a mask of the carried points (votop_*, include/vo_topup.h, capi_topup.hip): a CHECKED record,
+    // and one plane per frame with the table the kernels read them through -- from `own`, grown where the candidate buffers grow ----
+    struct TopUp {
+        votop_params prm = {VOTOP_OFF, 5};
+        int slots = 0;                     // frames the planes below serve
+        size_t plane_stride = 0;           // bytes from one plane to the next (max_w x max_h, rounded up to 16)
+        uint8_t *d_planes = nullptr;       // [slots][plane_stride] rows tight (w bytes)
+        const uint8_t **d_table = nullptr; // [slots] d_planes + f * plane_stride
+        int ran = 0;                       // frames of the latest masked detection outside the lock-step loop (0: none)
+        int cfg[3] = {0, 0, 0};            // n_images, w, h of the table it ran on
+    } top;
     // ---- the detector's masks (vocmask_*, include/vo_corners_mask.h, capi_corners_mask.hip): allocated by the first such call ----
     struct CornMask {
         bool ready = false;
@@ -401,6 +412,9 @@ struct vo_ctx {
         hipEvent_t ev_pyr = nullptr;      // pyramids of the pending step built (prep stream)
         Signal fast[VO_SEQ_MAX_RING];     // corners of ring slot r ready (prep stream)
         bool have_corners[VO_SEQ_MAX_RING] = {}; // d_corners of ring slot r belongs to the pair now in that slot
+        // (include/vo_topup.h) with the top-up on the look-ahead leaves the response MAPS of ring slot r here instead of corners, and
+        // the step finishes the detection under the carried points' mask.  One set per ring slot: see DESIGN 3.16
+        float *d_topmaps = nullptr;       // [ring][S][max_w * max_h], or null
         SeqIngest *h_ing = nullptr, *d_ing = nullptr; // [VO_SEQ_INFLIGHT][S] pairs pushed for a step (pinned / device)
         int n_ing = 0, n_active = 0;    // pairs pushed for / sequences active in the pending step
         // rectification at ingest (vo_params.rectify, else all null): the step's i-th pushed pair is ingested into raw planes
@@ -570,8 +584,15 @@ int corn_check_resp(vo_ctx *c, const char *who, const voresp_params *in, voresp_
 // the frame loop under VODET_SHI_TOMASI (capi_detector.hip): the candidate buffers for `frames` frames (may drain the context: never
 // inside a lock-step step), and the detector over the frames of `quads` into corners [frames][fcap] / n_out [frames] on `stream`
 inline bool shi_tomasi(const vo_ctx *c) { return c->det.detector == VODET_SHI_TOMASI; }
+// the top-up under a mask of the carried points acts (include/vo_topup.h): det_ensure then takes the planes too, det_launch runs the
+// masked route, and the lock-step loop's look-ahead is det_lookahead_maps (the map pass alone, into ring slot r's maps) with
+// det_launch(..., maps = that slot's) finishing it in the step
+inline bool topup_on(const vo_ctx *c) { return shi_tomasi(c) && c->top.prm.mode == VOTOP_CARRIED; }
 int det_ensure(vo_ctx *c, int frames);
-int det_launch(vo_ctx *c, const vo::Quad *quads, const int *d_detect, int frames, float2 *corners, int *n_out, hipStream_t stream);
+int top_ensure(vo_ctx *c, int frames); // (capi_topup.hip) the planes and their table for `frames` frames; may drain the context
+int det_launch(vo_ctx *c, const vo::Quad *quads, const int *d_detect, int frames, float2 *corners, int *n_out, hipStream_t stream,
+               const float *ahead_maps = nullptr);
+int det_lookahead_maps(vo_ctx *c, const vo::Quad *quads, int frames, float *maps, hipStream_t stream);
 int cmask_detect(vo_ctx *c, const char *who, const uint8_t *img, int w, int h, int stride, const uint8_t *mask, int mask_stride,
                  const vocorn_params *params, const voresp_params *resp, float *pts_out, int cap, int *n_out); // (capi_corners_mask.hip)
 struct DeferGuard { // the deferred t1 pair never outlives the call whose host pointers it holds

@@ -118,7 +118,7 @@ int run_detect(vo_ctx *c, const Run &R)
                 if (r2 == rp || !ahead)
                     VO_HIP_TRY(c, sq.fast[r2].wait(trk));
             launch_seq_prepare(R.seq_active, c->d_ntracked, c->dprm.redetect_below, c->d_detect,
-                               ahead ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, trk);
+                               ahead && !topup_on(c) ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, trk);
             c->detect_uploaded = false;
         } else {
             bool changed = false;
@@ -135,7 +135,17 @@ int run_detect(vo_ctx *c, const Run &R)
         }
         int t = c->dprm.fast_threshold;
         t = t < 0 ? 0 : t > 255 ? 255 : t;
-        if (ahead) {
+        const bool top = topup_on(c); // include/vo_topup.h: the detector's call under the disc mask of the carried points
+        if (ahead && top) {
+            // the look-ahead left the response maps of ring slot rp (seq_lookahead); seq_prepare_kernel above wrote the flags and,
+            // given no counts, left d_nnew alone: discs, masked maximum, candidates and select run here under the flags, into the
+            // detector's own list and d_nnew -- the inline route's buffers -- and the bucketing takes its split form
+            int rcd = det_launch(c, c->quads_cur, c->d_detect, B, c->corn.d_pts, c->d_nnew, trk, sq.d_topmaps + (size_t)rp * sq.S * c->max_w * c->max_h);
+            if (rcd != VO_OK)
+                return rcd;
+            launch_bucket(c->d_feat, c->corn.d_pts, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap, c->w, c->h, bs, fpb, c->d_pts_det[wset],
+                          c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active, c->d_overflow, B, trk);
+        } else if (ahead) {
             launch_bucket(c->d_feat, sq.d_corners + (size_t)rp * sq.S * c->fcap, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap,
                           c->w, c->h, bs, fpb, c->d_pts_det[wset], c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active,
                           c->d_overflow, B, trk);
@@ -155,8 +165,9 @@ int run_detect(vo_ctx *c, const Run &R)
                                  c->d_overflow, trk);
         }
         // (seq_enqueue_inputs: the NEXT step's PCIe ingest waits for this; under Shi-Tomasi so does this step's look-ahead pass,
-        // seq_lookahead, which runs in the candidate buffers an inline detection has just used)
-        if (sq.on && (!R.prep || (shi && !ahead)))
+        // seq_lookahead, which runs in the candidate buffers an inline detection has just used -- and, with the top-up on, behind
+        // the masked passes of a step that ran on look-ahead maps too: they use those buffers on this stream)
+        if (sq.on && (!R.prep || (shi && (!ahead || top))))
             VO_HIP_TRY(c, sq.detect.record(trk));
         c->pts_sel = wset;
         // the bucketed count is only known on the device; every later grid is sized by its bound

@@ -64,8 +64,10 @@ TuneKey tune_key(const vo_ctx *c, int stages)
     // (the synchronous drop-in call is keyed on the image shape only: a live sequence whose feature count drifts across a
     // bucket boundary must not pay a probe -- ~20 frame times -- in the middle of real-time use)
     key.k[6] = (c->sync_call && !c->seq.on) ? 0 : pts_bucket(pts);
-    // (bit 5: the frame loop's detector -- a schedule probed under FAST is neither reused nor overwritten by a Shi-Tomasi context)
-    key.k[7] = (c->prm.mono_rotation ? 1 : 0) | ((stages & VO_STAGE_DETECT) ? 2 : 0) | (c->sync_call && !c->seq.on ? 16 : 0) | (shi_tomasi(c) ? 32 : 0);
+    // (bit 5: the frame loop's detector -- a schedule probed under FAST is neither reused nor overwritten by a Shi-Tomasi context;
+    // bit 6: its top-up under a mask of the carried points, include/vo_topup.h, likewise)
+    key.k[7] = (c->prm.mono_rotation ? 1 : 0) | ((stages & VO_STAGE_DETECT) ? 2 : 0) | (c->sync_call && !c->seq.on ? 16 : 0) | (shi_tomasi(c) ? 32 : 0) |
+               (topup_on(c) ? 64 : 0);
     return key;
 }
 
@@ -242,7 +244,14 @@ int seq_lookahead(vo_ctx *c, int r)
     vo_ctx::Seq &q = c->seq;
     int t = c->dprm.fast_threshold;
     t = t < 0 ? 0 : t > 255 ? 255 : t;
-    if (shi_tomasi(c)) {
+    if (topup_on(c)) {
+        // (include/vo_topup.h) the mask needs the carried set, which exists one step later; the response map does not: the map pass
+        // alone, for every pair's left image, into ring slot r's maps.  The step's DETECT part finishes the call (run_detect)
+        VO_HIP_TRY(c, q.detect.wait(ingest_stream(c)));
+        int rc = det_lookahead_maps(c, q.d_quads + (size_t)r * q.S, q.S, q.d_topmaps + (size_t)r * q.S * c->max_w * c->max_h, ingest_stream(c));
+        if (rc != VO_OK)
+            return rc;
+    } else if (shi_tomasi(c)) {
         // (include/vo_detector.h) goodFeaturesToTrack of every pair's left image into the ring slot's corner list, every frame
         // (which sequence detects again is known one step later: seq_prepare_kernel).  The candidate buffers are the ones an inline
         // detection of the step just enqueued may still use on the tracking stream: behind it.

@@ -74,7 +74,8 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
     if (rc != VO_OK)
         return rc;
     seq_free(c);
-    if (shi_tomasi(c)) { // (include/vo_detector.h) the detector's candidate buffers, one slot per sequence: here, never inside a step
+    if (shi_tomasi(c)) { // (include/vo_detector.h) the detector's candidate buffers -- with the top-up of include/vo_topup.h on, the mask
+                         // planes too --, one slot per sequence: here, never inside a step
         rc = det_ensure(c, n_seq);
         if (rc != VO_OK)
             return rc;
@@ -118,6 +119,8 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
     Owner &o = q.own;
     ok = ok && o.device(&q.d_corners, (size_t)ring * S * c->fcap);
     ok = ok && o.device(&q.d_ncorn, (size_t)ring * S, /*zero*/ true);
+    if (topup_on(c)) // (include/vo_topup.h) the look-ahead's response maps, one set per ring slot
+        ok = ok && o.device(&q.d_topmaps, (size_t)ring * S * c->max_w * c->max_h);
     ok = ok && o.event(&q.ev_pyr);
     for (Signal &g : q.fast)
         ok = ok && o.signal(&g);

@@ -18,6 +18,11 @@
 //                        slot = frame, image = quads[frame].l0; a frame whose detect flag is 0 leaves all three at once and reports
 //                        no corner; a candidate list beyond lcap is reported as lcap + 1 corners, the count bucket_kernel's split
 //                        form turns into the frame's overflow flag.  The bodies are the ones above.
+// and the frame loop's top-up under a mask of the carried points (include/vo_topup.h): the map pass above with a null
+// max_key, then
+//   corn_disc_frames_kernel  corn_disc_kernel's body over the frames' carried lists, the counts read on the device
+//   corn_max_frames_kernel   minMaxLoc's masked maximum of the stored map: a flat reduction over w h floats and w h mask bytes
+// and the candidate and select kernels of the frames form, the first with a.masks set.
 //
 // Why a thread per column.  boxFilter sums the f32 products in f64, and its column pass (ColumnSum<double, float>) is a RUNNING sum
 // down the whole column: SUM += row(y + 1); out = SUM; SUM -= row(y - 1).  The f64 operations are not exact in general -- a dy of
@@ -439,10 +444,11 @@ __global__ __launch_bounds__(CORN_SELECT_THREADS) void corn_select_frames_kernel
 // box both offsets are at most radius <= 256, and cx +- radius stays far inside int).  Every writer stores the same byte, so
 // overlapping discs need no atomics and the result does not depend on order.
 constexpr int CD_T = 256, CD_WAVES = CD_T / 64;
-__global__ __launch_bounds__(CD_T) void corn_disc_kernel(const float2 *__restrict__ kept, int n_kept, int radius, uint8_t *__restrict__ mask, int w, int h,
-                                                         int pitch)
+// kept point p by the calling wavefront (p is uniform per wavefront)
+__device__ __forceinline__ void corn_disc_body(const float2 *__restrict__ kept, int n_kept, int p, int radius, uint8_t *__restrict__ mask, int w, int h,
+                                               int pitch)
 {
-    const int lane = (int)threadIdx.x % 64, p = (int)blockIdx.x * CD_WAVES + (int)threadIdx.x / 64;
+    const int lane = (int)threadIdx.x % 64;
     if (p >= n_kept) // (uniform per wavefront)
         return;
     const float2 k = kept[p];
@@ -458,6 +464,114 @@ __global__ __launch_bounds__(CD_T) void corn_disc_kernel(const float2 *__restric
         const int px = x0 + i % bw, py = y0 + i / bw, dx = px - cx, dy = py - cy;
         if (dx * dx + dy * dy <= r2)
             mask[(size_t)py * pitch + px] = 0;
+    }
+}
+
+__global__ __launch_bounds__(CD_T) void corn_disc_kernel(const float2 *__restrict__ kept, int n_kept, int radius, uint8_t *__restrict__ mask, int w, int h,
+                                                         int pitch)
+{
+    corn_disc_body(kept, n_kept, (int)blockIdx.x * CD_WAVES + (int)threadIdx.x / 64, radius, mask, w, h, pitch);
+}
+
+// The frames form (include/vo_topup.h): the kept list of frame f is the carried set at entry, feat + f * fcap, its count n_tracked[f]
+// read here -- in the lock-step loop only the device knows it.  planes[f]: the frame's mask, rows w bytes apart, which a fill on the
+// same stream has set to 0xFF.  The grid's x covers the largest carried set that still detects again (redetect_below - 1 points, at
+// most fcap); the loop makes a smaller grid right too (grid_x: gridDim.x, as an argument like seq_ingest_kernel's).
+__global__ __launch_bounds__(CD_T) void corn_disc_frames_kernel(const float2 *__restrict__ feat, int fcap, const int *__restrict__ n_tracked,
+                                                                const int *__restrict__ detect, int radius, uint8_t *const *__restrict__ planes, int w,
+                                                                int h, int grid_x /* = the grid's x */)
+{
+    const int f = blockIdx.y;
+    if (detect && !detect[f]) // (uniform)
+        return;
+    int n = n_tracked[f];
+    n = n < fcap ? n : fcap;
+    uint8_t *__restrict__ mask = planes[f];
+    for (int p = (int)blockIdx.x * CD_WAVES + (int)threadIdx.x / 64; p < n; p += grid_x * CD_WAVES)
+        corn_disc_body(feat + (size_t)f * fcap, n, p, radius, mask, w, h, w);
+}
+
+// minMaxLoc(eig, 0, &maxVal, 0, 0, mask) of the frames form, on the map the map pass stored: max_key[f] = the largest corn_ord(value)
+// over the pixels whose mask byte is non-zero, border rows and columns included, 0 when none is allowed -- the bits corn_map_body
+// leaves under the same mask (an integer maximum: exact, so its order is free).
+//
+// A streaming reduction.  Map rows are tight and the planes have pitch w, so a frame is one flat run of n = w h floats beside n bytes.
+// A lane takes four floats by one 16-byte load and their four mask bytes by one 4-byte load, CX_UNROLL such groups a pass with all
+// loads issued before the first compare.  The run's start need not be 16-byte aligned (map_stride = max_w max_h floats, any w h):
+// the floats in front of the first aligned address and those behind the last whole group go one to a lane of the first workgroup.
+// The mask word is then at whatever alignment the plane has beside the map's (an align-1 dword, which global memory takes).
+// The wavefront's maximum is taken in registers (DPP: two quad permutes, two mirrors, two row broadcasts; 0 is neutral), the four
+// wavefronts meet in LDS once, and one atomicMax per workgroup reaches memory.  No value is kept across frames.
+constexpr int CX_T = 256, CX_UNROLL = 4, CX_PER_WG = CX_T * CX_UNROLL * 4; // floats a workgroup takes per pass
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned dpp_umax(unsigned v)
+{
+    const unsigned o = (unsigned)VO_UPDATE_DPP(0, (int)v, CTRL, ROW_MASK, 0xf, true);
+    return o > v ? o : v;
+}
+
+__global__ __launch_bounds__(CX_T) void corn_max_frames_kernel(const float *__restrict__ maps, size_t map_stride, const uint8_t *const *__restrict__ planes,
+                                                               int n, const int *__restrict__ detect, unsigned *__restrict__ max_key, int grid_x /* = the grid's x */)
+{
+    __shared__ unsigned s_wave[CX_T / 64];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    if (detect && !detect[f]) // (uniform)
+        return;
+    const float *__restrict__ map = maps + (size_t)f * map_stride;
+    const uint8_t *__restrict__ mask = planes[f];
+    int head = (int)((16u - (unsigned)((uintptr_t)map & 15u)) & 15u) / 4; // floats in front of the first 16-byte boundary
+    head = head < n ? head : n;
+    const int groups = (n - head) / 4, tail0 = head + groups * 4; // whole groups; the first float behind them
+    unsigned best = 0;
+    if (blockIdx.x == 0) { // head and tail: at most 3 + 3 single elements
+        const int i = tid < head ? tid : tail0 + (tid - head);
+        if (i < n && mask[i]) {
+            const unsigned key = corn_ord(map[i]);
+            best = key;
+        }
+    }
+    const uint4 *__restrict__ m4 = reinterpret_cast<const uint4 *>(map + head);
+    const uint8_t *__restrict__ k1 = mask + head;
+    for (int g0 = (int)blockIdx.x * (CX_T * CX_UNROLL); g0 < groups; g0 += grid_x * (CX_T * CX_UNROLL)) {
+        uint4 v[CX_UNROLL];
+        uint32_t k[CX_UNROLL];
+        for (int u = 0; u < CX_UNROLL; u++) {
+            const int g = g0 + u * CX_T + tid;
+            if (g < groups) {
+                v[u] = m4[g];
+                k[u] = reinterpret_cast<const U32A1 *>(k1 + (size_t)g * 4)->a;
+            } else {
+                v[u] = make_uint4(0, 0, 0, 0);
+                k[u] = 0;
+            }
+        }
+        for (int u = 0; u < CX_UNROLL; u++) {
+            if (!k[u])
+                continue;
+            const uint32_t q[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+            for (int j = 0; j < 4; j++)
+                if ((k[u] >> (8 * j)) & 0xffu) {
+                    const unsigned key = (q[j] & 0x80000000u) ? ~q[j] : (q[j] | 0x80000000u); // corn_ord on the bits
+                    best = key > best ? key : best;
+                }
+        }
+    }
+    best = dpp_umax<VO_DPP_QUAD_XOR1, 0xf>(best);
+    best = dpp_umax<VO_DPP_QUAD_XOR2, 0xf>(best);
+    best = dpp_umax<VO_DPP_ROW_HALF_MIRROR, 0xf>(best);
+    best = dpp_umax<VO_DPP_ROW_MIRROR, 0xf>(best);
+    best = dpp_umax<VO_DPP_ROW_BCAST15, 0xa>(best);
+    best = dpp_umax<VO_DPP_ROW_BCAST31, 0xc>(best); // lane 63 holds the wavefront's maximum
+    if (tid % 64 == 63)
+        s_wave[tid / 64] = best;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned m = s_wave[0];
+        for (int i = 1; i < CX_T / 64; i++)
+            m = s_wave[i] > m ? s_wave[i] : m;
+        if (m)
+            atomicMax(&max_key[f], m);
     }
 }
 
@@ -506,11 +620,26 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
 }
 
 template <int B, int HARRIS>
-static void launch_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, hipStream_t stream)
+static void launch_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, unsigned *max_key,
+                              hipStream_t stream)
 {
     constexpr int COLS = CM_T - 2 * (B / 2);
     hipLaunchKernelGGL((corn_map_frames_kernel<B, HARRIS>), dim3((w + COLS - 1) / COLS, n), dim3(CM_T), 0, stream, d_imgs, d_quads, d_detect, a.maps,
-                       a.map_stride, a.max_key, a.harris_k);
+                       a.map_stride, max_key, a.harris_k);
+}
+
+// max_key: a.max_key, or null for the map alone (the top-up's split: corn_max_frames_kernel takes the maximum under the mask)
+static void launch_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, unsigned *max_key,
+                              hipStream_t stream)
+{
+    if (a.block_size == 5 && !a.use_harris)
+        launch_frames_map<5, 0>(d_imgs, d_quads, d_detect, n, w, a, max_key, stream);
+    else if (a.block_size == 5)
+        launch_frames_map<5, 1>(d_imgs, d_quads, d_detect, n, w, a, max_key, stream);
+    else if (a.use_harris)
+        launch_frames_map<3, 1>(d_imgs, d_quads, d_detect, n, w, a, max_key, stream);
+    else
+        launch_frames_map<3, 0>(d_imgs, d_quads, d_detect, n, w, a, max_key, stream);
 }
 
 hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, int h, const CornArgs &a, hipStream_t stream)
@@ -523,14 +652,40 @@ hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, co
     if (e != hipSuccess)
         return e;
     const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
-    if (a.block_size == 5 && !a.use_harris)
-        launch_frames_map<5, 0>(d_imgs, d_quads, d_detect, n, w, a, stream);
-    else if (a.block_size == 5)
-        launch_frames_map<5, 1>(d_imgs, d_quads, d_detect, n, w, a, stream);
-    else if (a.use_harris)
-        launch_frames_map<3, 1>(d_imgs, d_quads, d_detect, n, w, a, stream);
-    else
-        launch_frames_map<3, 0>(d_imgs, d_quads, d_detect, n, w, a, stream);
+    launch_frames_map(d_imgs, d_quads, d_detect, n, w, a, a.max_key, stream);
+    hipLaunchKernelGGL(corn_cand_frames_kernel, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a, d_detect);
+    hipLaunchKernelGGL(corn_select_frames_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h, d_detect);
+    return hipGetLastError();
+}
+
+hipError_t launch_corners_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    launch_frames_map(d_imgs, d_quads, d_detect, n, w, a, nullptr, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_corners_frames_masked(const int *d_detect, int n, int w, int h, const CornArgs &a, const CornTopArgs &t, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    hipError_t e = hipMemsetAsync(a.max_key, 0, sizeof(unsigned) * (size_t)n, stream);
+    if (e == hipSuccess)
+        e = hipMemsetAsync(a.ncand, 0, sizeof(int) * (size_t)n, stream);
+    if (e == hipSuccess) // the planes' w h bytes each (plane_stride apart)
+        e = hipMemset2DAsync(t.plane0, t.plane_stride, 0xFF, (size_t)w * h, (size_t)n, stream);
+    if (e != hipSuccess)
+        return e;
+    int kept = t.max_kept < t.fcap ? t.max_kept : t.fcap;
+    kept = kept > 0 ? kept : 1;
+    const int disc_x = (kept + CD_WAVES - 1) / CD_WAVES;
+    hipLaunchKernelGGL(corn_disc_frames_kernel, dim3(disc_x, n), dim3(CD_T), 0, stream, t.feat, t.fcap, t.n_tracked, d_detect, t.radius, t.planes, w, h, disc_x);
+    const int cells = w * h;
+    int wgs = (cells + CX_PER_WG - 1) / CX_PER_WG;
+    wgs = wgs < 1 ? 1 : wgs > 1024 ? 1024 : wgs;
+    hipLaunchKernelGGL(corn_max_frames_kernel, dim3(wgs, n), dim3(CX_T), 0, stream, a.maps, a.map_stride, a.masks, cells, d_detect, a.max_key, wgs);
+    const int tiles_x = (w + CT_W - 1) / CT_W, tiles_y = (h + CT_H - 1) / CT_H;
     hipLaunchKernelGGL(corn_cand_frames_kernel, dim3(tiles_x * tiles_y, n), dim3(256), 0, stream, w, h, tiles_x, a, d_detect);
     hipLaunchKernelGGL(corn_select_frames_kernel, dim3(n), dim3(CORN_SELECT_THREADS), 0, stream, a, w, h, d_detect);
     return hipGetLastError();

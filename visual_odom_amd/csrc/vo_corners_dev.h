@@ -57,6 +57,18 @@ inline int corn_pow2(int n)
     return p;
 }
 
+// what the top-up's masked route takes beside CornArgs (include/vo_topup.h; launch_corners_frames_masked below)
+struct CornTopArgs {
+    const float2 *feat;     // [n][fcap] the frames' feature lists: the carried points first
+    int fcap;
+    const int *n_tracked;   // [n] carried points per frame, on the device
+    int radius;
+    uint8_t *const *planes; // [n] device table of the planes (what a.masks reads)
+    uint8_t *plane0;        // plane 0; plane f lies plane_stride bytes further on, rows w bytes apart
+    size_t plane_stride;
+    int max_kept;           // the largest carried set that still detects again (sizes the disc grid)
+};
+
 #ifndef VO_HOST_EMUL
 // the whole detector over n slots: map + maximum, candidates, sort + suppression + output (three launches on `stream`; max_key and
 // ncand are zeroed first).  Returns the first HIP error of the memsets and launches.  With a.masks the map pass is the masked twin;
@@ -68,6 +80,14 @@ hipError_t launch_corners(const PyrImage *d_imgs, int first, int n, int w, int h
 // beyond a.lcap nout = a.lcap + 1 (which bucket_kernel reports as the frame's list overflow).  a.masks is not read.
 hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, int h, const CornArgs &a,
                                  hipStream_t stream);
+// The frame loop's top-up under a mask of the carried points (include/vo_topup.h) is the frames form in two parts, so that the
+// lock-step loop's look-ahead can run the first before the step's carried sets exist:
+//   launch_corners_frames_map     the map pass alone into a.maps (no maximum: max_key is not written)
+//   launch_corners_frames_masked  0xFF over the n planes, the discs of every detecting frame's carried points (corn_disc_frames_kernel),
+//                                 the maximum of the stored map under the plane (corn_max_frames_kernel), then the candidate pass under
+//                                 a.masks (= the plane table, a.mask_pitch = w) and the select pass; max_key and ncand are zeroed first
+hipError_t launch_corners_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, hipStream_t stream);
+hipError_t launch_corners_frames_masked(const int *d_detect, int n, int w, int h, const CornArgs &a, const CornTopArgs &t, hipStream_t stream);
 // cv::cornerMinEigenVal(img, map, block_size, 3) or cv::cornerHarris(img, map, block_size, 3, k) of image `image` into map [h][w]
 // (tight); block_size 3 or 5
 void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream, int block_size = 3, int use_harris = 0,

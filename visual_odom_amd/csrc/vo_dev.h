@@ -101,6 +101,9 @@ struct Quad {
 // Two and four dwords moved as ONE 8- or 16-byte access at less than their natural alignment (the A<n> of the name: what the
 // address is known to be a multiple of).  Rows of pixels start anywhere; the hardware takes unaligned vector accesses to
 // global memory and to LDS, and the packed struct is how the compiler is told that it may emit one.
+struct __attribute__((packed, aligned(1))) U32A1 { // (one dword: four mask bytes beside an aligned 16-byte load, corners.hip)
+    uint32_t a;
+};
 struct __attribute__((packed, aligned(1))) U32x2A1 {
     uint32_t a, b;
 };
