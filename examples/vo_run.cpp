@@ -5,13 +5,15 @@
 // dropped and the trajectory the reference only draws (utils.cpp:19-48) is written in the KITTI pose
 // format (12 doubles per line, what loadPoses reads, evaluate_odometry.cpp:24-27).
 //
-//   vo_run [--detector fast|shi_tomasi] [--topup-radius R] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out.txt> [features_per_bucket]
+//   vo_run [--detector fast|shi_tomasi] [--topup-radius R] [--fast-topup-radius R] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out.txt> [features_per_bucket]
 //   --detector shi_tomasi: appendNewFeatures detects with goodFeaturesToTrack (include/vo_detector.h)
 //   --topup-radius R: ... under the disc mask, radius R, of the points the frame carries in (include/vo_topup.h)
+//   --fast-topup-radius R: the same for the FAST detector -- cv::FAST's mask argument (include/vo_fast_mask.h); the options in this order
 //   images: <sequence_dir>/image_0/%06d.pgm (left), image_1/%06d.pgm (right)   (utils.cpp:172-190)
 //
 // build: g++ -O2 -std=c++17 vo_run.cpp -I../include -L../visual_odom_amd -lvo_hip -Wl,-rpath,... -o vo_run
 #include "vo_topup.h"
+#include "vo_fast_mask.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -73,8 +75,15 @@ int main(int argc, char **argv)
         argv += 2;
         argc -= 2;
     }
+    int fast_topup_radius = -1;
+    if (argc > 2 && !strcmp(argv[1], "--fast-topup-radius")) {
+        fast_topup_radius = atoi(argv[2]);
+        argv[2] = argv[0];
+        argv += 2;
+        argc -= 2;
+    }
     if (argc < 8) {
-        fprintf(stderr, "usage: %s [--detector fast|shi_tomasi] [--topup-radius R] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out> [features_per_bucket [mono_rotation]]\n", argv[0]);
+        fprintf(stderr, "usage: %s [--detector fast|shi_tomasi] [--topup-radius R] [--fast-topup-radius R] <sequence_dir> <fx> <cx> <cy> <bf> <n_frames> <poses_out> [features_per_bucket [mono_rotation]]\n", argv[0]);
         return 1;
     }
     const std::string dir = argv[1];
@@ -103,6 +112,10 @@ int main(int argc, char **argv)
     if (topup_radius >= 0) {
         votop_params top = {VOTOP_CARRIED, topup_radius};
         CHECK(votop_set_params(ctx, &top));
+    }
+    if (fast_topup_radius >= 0) {
+        vofm_params fm = {VOFM_CARRIED, fast_topup_radius};
+        CHECK(vofm_set_params(ctx, &fm));
     }
     vo_detect_params dp;
     vo_default_detect_params(&dp);

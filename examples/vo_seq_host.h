@@ -9,6 +9,7 @@
 #pragma once
 
 #include "vo_topup.h"
+#include "vo_fast_mask.h"
 #include "vo_io.h"
 
 #include <algorithm>
@@ -37,9 +38,10 @@ struct WorkerResult {
 // conversion runs in the ingest kernel) instead of being folded to gray by the decoder threads
 // detector: VODET_FAST, or VODET_SHI_TOMASI -- appendNewFeatures with featureDetectionGoodFeaturesToTrack and its literals
 // (include/vo_detector.h); topup_radius >= 0: that call under the disc mask of the points each frame carries in (include/vo_topup.h)
+// fast_topup_radius >= 0: cv::FAST's call under that mask instead (include/vo_fast_mask.h)
 inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs, const Calib &cal, int max_frames,
                                int features_per_bucket, int decode_threads, bool device_convert = false, int detector = VODET_FAST,
-                               int topup_radius = -1)
+                               int topup_radius = -1, int fast_topup_radius = -1)
 {
     WorkerResult out;
     out.device = device;
@@ -92,6 +94,11 @@ inline WorkerResult run_worker(int device, const std::vector<std::string> &dirs,
         const votop_params top = {VOTOP_CARRIED, topup_radius};
         if ((rc = votop_set_params(ctx, &top)) < 0) // before vo_seq_configure as well: the loop takes its mask planes there
             return fail("votop_set_params", rc);
+    }
+    if (fast_topup_radius >= 0) {
+        const vofm_params fm = {VOFM_CARRIED, fast_topup_radius};
+        if ((rc = vofm_set_params(ctx, &fm)) < 0)
+            return fail("vofm_set_params", rc);
     }
     if ((rc = vo_seq_configure(ctx, S, w, h, /*ring*/ 3, max_frames + 1)) < 0)
         return fail("vo_seq_configure", rc);

@@ -5,12 +5,13 @@
 // on one GPU (examples/vo_seq_host.h); examples/vo_multi_gpu.cpp runs one such worker per GPU (BASELINE "config 5").
 // Sequences may have different lengths: a sequence whose images run out simply stops.
 //
-//   vo_seq_run [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> <out_prefix>
+//   vo_seq_run [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] [--fast-topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> <out_prefix>
 //              <sequence_dir> [<sequence_dir> ...]
 //   images:  <sequence_dir>/image_0/%06d.png (left), image_1/%06d.png (right), or .pgm         (utils.cpp:172-190)
 //            --device-convert 1: an RGB PNG is handed over as RGB and the library converts it on the GPU (VO_FMT_RGB8)
 //            --detector shi_tomasi: appendNewFeatures detects with goodFeaturesToTrack (include/vo_detector.h)
 //            --topup-radius R: ... under the disc mask, radius R, of the points each frame carries in (include/vo_topup.h)
+//            --fast-topup-radius R: the same for the FAST detector -- cv::FAST's mask argument (include/vo_fast_mask.h)
 //   output:  <out_prefix>_<s>.txt, KITTI pose format (12 doubles per line, evaluate_odometry.cpp:24-27);
 //            stderr: end-to-end frames/s from the files (read + decode + upload + compute) and the time the loop spent
 //            waiting for the decoders
@@ -23,7 +24,7 @@
 
 int main(int argc, char **argv)
 {
-    int device = 0, decode_threads = 4, a = 1, detector = VODET_FAST, topup_radius = -1;
+    int device = 0, decode_threads = 4, a = 1, detector = VODET_FAST, topup_radius = -1, fast_topup_radius = -1;
     bool device_convert = false;
     while (a + 1 < argc && !strncmp(argv[a], "--", 2)) {
         if (!strcmp(argv[a], "--device"))
@@ -36,12 +37,14 @@ int main(int argc, char **argv)
             detector = !strcmp(argv[a + 1], "fast") ? VODET_FAST : VODET_SHI_TOMASI;
         else if (!strcmp(argv[a], "--topup-radius"))
             topup_radius = atoi(argv[a + 1]);
+        else if (!strcmp(argv[a], "--fast-topup-radius"))
+            fast_topup_radius = atoi(argv[a + 1]);
         else
             break;
         a += 2;
     }
     if (argc - a < 8) {
-        fprintf(stderr, "usage: %s [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> "
+        fprintf(stderr, "usage: %s [--device D] [--decode-threads T] [--device-convert 1] [--detector fast|shi_tomasi] [--topup-radius R] [--fast-topup-radius R] <fx> <cx> <cy> <bf> <max_frames> <features_per_bucket> "
                         "<out_prefix> <sequence_dir> ...\n", argv[0]);
         return 1;
     }
@@ -53,7 +56,7 @@ int main(int argc, char **argv)
     const int max_frames = atoi(argv[a + 4]), per_bucket = atoi(argv[a + 5]);
     const std::string prefix = argv[a + 6];
     std::vector<std::string> dirs(argv + a + 7, argv + argc);
-    vohost::WorkerResult r = vohost::run_worker(device, dirs, cal, max_frames, per_bucket, decode_threads, device_convert, detector, topup_radius);
+    vohost::WorkerResult r = vohost::run_worker(device, dirs, cal, max_frames, per_bucket, decode_threads, device_convert, detector, topup_radius, fast_topup_radius);
     if (r.rc) {
         fprintf(stderr, "%s\n", r.error.c_str());
         return r.rc;

@@ -44,7 +44,8 @@
  * OUT OF SCOPE: cv::circle-exact discs.  IN THE FRAME LOOP: vo_detector.h, the eighth header, puts this detector into
  * vo_detect_bucket, VO_STAGE_DETECT and vo_seq_*, and vo_topup.h, the ninth, runs it there under the disc mask of the points each
  * frame carries in.  blockSize 5 and the Harris response are in the seventh header, vo_corners_response.h, whose calls run
- * under these masks.
+ * under these masks.  cv::FAST's own mask argument -- detect on the unmasked image, then drop what the mask forbids: the opposite
+ * reading -- takes masks in this header's format and this header's disc mask, as a call and in the frame loop: vo_fast_mask.h, the tenth.
  */
 #ifndef VO_CORNERS_MASK_H
 #define VO_CORNERS_MASK_H

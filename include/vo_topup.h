@@ -33,8 +33,9 @@
  * SCHEDULES.  The mode is part of the probe's key, like the detector: schedules probed without the top-up are neither reused nor
  * overwritten, and the lock-step probe times what the loop will run.
  *
- * OUT OF SCOPE: a per-frame corner budget (target - n_carried), cv::circle-exact discs, a mask for cv::FAST, and a latency form of the
- * map pass for one or a few images.
+ * OUT OF SCOPE: a per-frame corner budget (target - n_carried), cv::circle-exact discs, and a latency form of the map pass for one or a
+ * few images.  (The fourth item this list held, a mask for cv::FAST, is vo_fast_mask.h, the tenth header: vofm_set_params does for
+ * VODET_FAST what this record does for VODET_SHI_TOMASI; each record has no effect under the other detector.)
  */
 #ifndef VO_TOPUP_H
 #define VO_TOPUP_H

@@ -15,7 +15,10 @@ checkout; a tree without vodet_* runs the FAST legs only.  Build both, alternate
 `--topup-radius R` adds a third column where the tree has votop_* (include/vo_topup.h): shi_tomasi with the top-up under the disc mask,
 radius R, of the carried points -- named shi_tomasi+top in the tables.  The Shi-Tomasi legs beside it run with the top-up off.
 
-    python tools/detector_loop_bench.py [--tree DIR] [--detectors fast,shi_tomasi] [--topup-radius R] [--legs sync,seq256,seq64,seq8]
+`--fast-topup-radius R` adds a column where the tree has vofm_* (include/vo_fast_mask.h): fast with cv::FAST's call under the same disc
+mask -- named fast+top.  The FAST legs beside it run with the record off.
+
+    python tools/detector_loop_bench.py [--tree DIR] [--detectors fast,shi_tomasi] [--topup-radius R] [--fast-topup-radius R] [--legs sync,seq256,seq64,seq8]
                                         [--runs 10] [--repeats 5] [--json out.json] [--md profiles/detector_loop.md]
 """
 import argparse
@@ -45,6 +48,7 @@ def main():
     ap.add_argument("--tree", default=ROOT)
     ap.add_argument("--detectors", default="fast,shi_tomasi")
     ap.add_argument("--topup-radius", type=int, default=None)
+    ap.add_argument("--fast-topup-radius", type=int, default=None)
     ap.add_argument("--legs", default="sync,seq256,seq64,seq8")
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
@@ -59,7 +63,10 @@ def main():
     detectors = [d for d in args.detectors.split(",") if d == "fast" or (d == "shi_tomasi" and has_det)]
     if args.topup_radius is not None and has_det and hasattr(_lib, "TOPUP_EXPORTS"):
         detectors.append("shi_tomasi+top")
-    top_kw = lambda det: dict(topup_radius=args.topup_radius) if det.endswith("+top") else {}
+    if args.fast_topup_radius is not None and "fast" in detectors and hasattr(_lib, "FAST_MASK_EXPORTS"):
+        detectors.insert(detectors.index("fast") + 1, "fast+top")
+    top_kw = lambda det: ({} if not det.endswith("+top") else dict(fast_topup_radius=args.fast_topup_radius) if det.startswith("fast") else
+                          dict(topup_radius=args.topup_radius))
     world = synth.StereoWorld(seed=20260925)
     lefts, rights, _, _ = world.render_sequence(Q + 1)
     P_l, P_r = world.proj_matrices()
@@ -95,7 +102,9 @@ def main():
             ctx.batch_set_detect_params(features_per_bucket=1)
             if has_det:
                 ctx.set_detector(det.split("+")[0])
-            if det.endswith("+top"):
+            if det == "fast+top":
+                ctx.set_fast_topup(radius=args.fast_topup_radius)
+            elif det.endswith("+top"):
                 ctx.set_topup(radius=args.topup_radius)
             ctx.seq_configure(S, W, H, 3, (args.repeats + 3) * args.runs + 600)
             ctx.batch_set_projection(P_l, P_r)

@@ -58,6 +58,9 @@ DETECTORS = {"fast": 0, "shi_tomasi": 1}  # VODET_FAST, VODET_SHI_TOMASI
 # include/vo_topup.h: the frame loop's top-up under a mask of the carried points, the ninth header
 TOPUP_EXPORTS = ("votop_default_params", "votop_set_params", "votop_get_params", "votop_get_mask")
 TOPUP_MODES = {"off": 0, "carried": 1}  # VOTOP_OFF, VOTOP_CARRIED
+# include/vo_fast_mask.h: cv::FAST under a mask, as a call and in the frame loop, the tenth header
+FAST_MASK_EXPORTS = ("vofm_detect", "vofm_replenish", "vofm_default_params", "vofm_set_params", "vofm_get_params", "vofm_get_mask")
+FAST_MASK_MODES = {"off": 0, "carried": 1}  # VOFM_OFF, VOFM_CARRIED
 FLAG_USE_INITIAL_FLOW = 4
 FLAG_GET_MIN_EIGENVALS = 8
 
@@ -134,6 +137,11 @@ class VoDetParams(C.Structure):
 
 class VoTopParams(C.Structure):
     """votop_params (include/vo_topup.h)"""
+    _fields_ = [("mode", C.c_int), ("radius", C.c_int)]
+
+
+class VoFmParams(C.Structure):
+    """vofm_params (include/vo_fast_mask.h)"""
     _fields_ = [("mode", C.c_int), ("radius", C.c_int)]
 
 
@@ -219,6 +227,16 @@ def load():
     lib.votop_get_mask.argtypes = [vp, i, vp, i]
     for name in TOPUP_EXPORTS[1:]:
         getattr(lib, name).restype = C.c_int
+    lib.vofm_detect.argtypes = [vp, vp, i, i, i, i, i, vp, i, vp, i, vp]
+    lib.vofm_replenish.argtypes = [vp, vp, i, i, i, i, i, vp, i, i, vp, i, vp]
+    lib.vofm_default_params.argtypes = [C.POINTER(VoFmParams)]
+    lib.vofm_default_params.restype = None
+    lib.vofm_set_params.argtypes = [vp, C.POINTER(VoFmParams)]
+    lib.vofm_get_params.argtypes = [vp, C.POINTER(VoFmParams)]
+    lib.vofm_get_mask.argtypes = [vp, i, vp, i]
+    for name in FAST_MASK_EXPORTS:
+        if name != "vofm_default_params":
+            getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib
 
@@ -755,6 +773,57 @@ class Context:
         """the (h, w) mask plane the last detect_bucket (frame 0) or VO_STAGE_DETECT built for `frame` (votop_get_mask)"""
         out = np.zeros((h, w), np.uint8)
         self._chk(self.lib.votop_get_mask(self.h, int(frame), _p(out), w))
+        return out
+
+    # ---- cv::FAST under a mask (include/vo_fast_mask.h) --------------------------------------
+    def _fm_fetch(self, call, cap):
+        pts = np.zeros((max(cap, 1), 2), np.float32)
+        n = C.c_int(0)
+        self._chk(call(_p(pts), cap, C.byref(n)))
+        if n.value > cap:   # (the count is the full one: once more with room for all of them)
+            return self._fm_fetch(call, n.value)
+        return pts[:n.value].copy()
+
+    def fast_detect_masked(self, img, mask, threshold=20, nonmax=True, cap=65536):
+        """FastFeatureDetector::create(threshold, nonmax)->detect(img, keypoints, mask) (vofm_detect): the corners cv::FAST finds on
+        the unmasked image whose mask byte is non-zero, row-major, (n, 2) float32.  mask: (h, w) uint8, a row-contiguous view is
+        passed as it is; None: fast_detect.  img is None: the kept left image"""
+        img, w, h, stride = self._corn_image(img)
+        if mask is None:
+            m, ms = None, 0
+        else:
+            (m,), ms = _imgs(mask)
+            if m.shape != (h, w):
+                raise ValueError("mask: (h, w) uint8 of the image's size")
+        return self._fm_fetch(lambda p, c, n: self.lib.vofm_detect(self.h, _pn(img), w, h, stride, int(threshold), int(bool(nonmax)), _pn(m), ms,
+                                                                   p, c, n), cap)
+
+    def fast_replenish(self, img, kept, radius=5, threshold=20, nonmax=True, cap=65536):
+        """the disc mask of `kept` (include/vo_corners_mask.h) built on the device and cv::FAST under it (vofm_replenish)"""
+        img, w, h, stride = self._corn_image(img)
+        kept = _f32(kept, (-1, 2))
+        return self._fm_fetch(lambda p, c, n: self.lib.vofm_replenish(self.h, _pn(img), w, h, stride, int(threshold), int(bool(nonmax)),
+                                                                      _p(kept) if len(kept) else None, len(kept), int(radius), p, c, n), cap)
+
+    def set_fast_topup(self, radius=5, mode="carried"):
+        """cv::FAST's mask in the frame loop (vofm_set_params, include/vo_fast_mask.h): under the FAST detector, new corners only
+        further than `radius` from every point a frame carries in.  mode "off": as without.  Context state: detect_bucket,
+        VO_STAGE_DETECT and the seq_* loop follow it; set it before seq_configure."""
+        if mode not in FAST_MASK_MODES:
+            raise ValueError("mode: one of %s" % ", ".join(sorted(FAST_MASK_MODES)))
+        prm = VoFmParams(FAST_MASK_MODES[mode], int(radius))
+        self._chk(self.lib.vofm_set_params(self.h, C.byref(prm)))
+
+    def get_fast_topup(self):
+        """the record in force (vofm_get_params), as the keyword arguments of set_fast_topup"""
+        prm = VoFmParams()
+        self._chk(self.lib.vofm_get_params(self.h, C.byref(prm)))
+        return dict(radius=prm.radius, mode={v: n for n, v in FAST_MASK_MODES.items()}[prm.mode])
+
+    def fast_topup_mask(self, frame, w, h):
+        """the (h, w) mask plane the last detect_bucket (frame 0) or VO_STAGE_DETECT built for `frame` (vofm_get_mask)"""
+        out = np.zeros((h, w), np.uint8)
+        self._chk(self.lib.vofm_get_mask(self.h, int(frame), _p(out), w))
         return out
 
     def detect_bucket(self, img, pts, ages, **detect_kw):

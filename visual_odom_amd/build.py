@@ -28,7 +28,7 @@ OBJ = os.path.join(CSRC, "_obj")
 SO = os.path.join(HERE, "libvo_hip.so")
 SOURCES = ["pyramid.hip", "fast.hip", "lk.hip", "post.hip", "pnp.hip", "essential.hip", "seq.hip", "ingest_fmt.hip", "rectify.hip", "capi.hip", "capi_run.hip",
            "capi_sched.hip", "capi_seq.hip", "capi_dropin.hip", "capi_flow.hip", "corners.hip", "capi_corners.hip", "capi_corners_mask.hip",
-           "capi_corners_response.hip", "capi_detector.hip", "capi_topup.hip"]
+           "capi_corners_response.hip", "capi_detector.hip", "capi_topup.hip", "capi_fast_mask.hip"]
 # the developer build: a wrapper in place of the product file it includes, and the entry points of its own
 DEV_WRAPPERS = {"pyramid.hip": "dev/pyramid_dev.hip", "fast.hip": "dev/fast_dev.hip", "lk.hip": "dev/lk_dev.hip", "pnp.hip": "dev/pnp_dev.hip"}
 DEV_SOURCES = [DEV_WRAPPERS.get(s, s) for s in SOURCES] + ["dev/capi_dev.hip"]
@@ -52,7 +52,7 @@ def build(force=False, verbose=False, dev=False):
             flags.append("-DVO_LK_ATTRS=" + os.environ["VO_LK_ATTRS"])
     headers = [os.path.join(d, f) for d in (CSRC, os.path.join(CSRC, "dev")) for f in os.listdir(d) if f.endswith(".h")]
     headers += [os.path.join(HERE, "..", "include", f) for f in ("vo_hip.h", "vo_flow.h", "vo_flow_win.h", "vo_flow_flags.h", "vo_corners.h", "vo_corners_mask.h",
-                                                          "vo_corners_response.h", "vo_detector.h", "vo_topup.h")]
+                                                          "vo_corners_response.h", "vo_detector.h", "vo_topup.h", "vo_fast_mask.h")]
     wrapped = {w: s for s, w in DEV_WRAPPERS.items()}
     objs, jobs = [], []
     for s in (DEV_SOURCES if dev else SOURCES):

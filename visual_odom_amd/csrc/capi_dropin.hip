@@ -336,6 +336,10 @@ int vo_detect_bucket(vo_ctx *c, const uint8_t *img, int w, int h, int stride, co
     if (shi_tomasi(c) && (ovf & 1))
         return fail(c, VO_ERR_OVERFLOW, "vo_detect_bucket: more goodFeaturesToTrack candidates than the context's corner-list capacity "
                                         "(max(4 x max_pts, 16384, max_w x max_h / 16)): nothing was written");
+    // (include/vo_fast_mask.h) under cv::FAST's mask the filter read a truncated unmasked list: nothing is written either
+    if (fastmask_on(c) && (ovf & 1))
+        return fail(c, VO_ERR_OVERFLOW, "vo_detect_bucket: more unmasked FAST corners than the context's corner-list capacity "
+                                        "(max(4 x max_pts, 16384, max_w x max_h / 16)): nothing was written");
     if (k > cap)
         return fail(c, VO_ERR_ARG, "vo_detect_bucket: bucketed set larger than the caller's capacity");
     const int kc = k < c->cap ? k : c->cap;

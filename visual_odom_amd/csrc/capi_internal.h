@@ -4,7 +4,7 @@
 // loop; capi_dropin.hip: the synchronous drop-in calls; capi_detector.hip: the frame loop's detector.  Round 4 split capi.hip (2 800 lines in one unit)
 // without changing behaviour.  Nothing declared here is exported: internal functions live in namespace vo_capi.
 #pragma once
-#include "../../include/vo_topup.h" // (brings vo_detector.h, vo_hip.h and the three corner headers)
+#include "../../include/vo_fast_mask.h" // (brings vo_topup.h, vo_detector.h, vo_hip.h and the three corner headers)
 #include "vo_kernels.h"
 #include "vo_dev_hooks.h"
 #include "vo_integrate.h"
@@ -360,6 +360,21 @@ struct vo_ctx {
         int ran = 0;                       // frames of the latest masked detection outside the lock-step loop (0: none)
         int cfg[3] = {0, 0, 0};            // n_images, w, h of the table it ran on
     } top;
+    // ---- cv::FAST under a mask (vofm_*, include/vo_fast_mask.h, capi_fast_mask.hip): a CHECKED record; one plane per frame with the
+    // table the kernels read them through, the unmasked list of an inline detection and the filtered list bucket_kernel's split form
+    // reads -- from `own`, taken by the first run with the record on or the first vofm_detect / vofm_replenish ----
+    struct FastMask {
+        vofm_params prm = {VOFM_OFF, 5};
+        int slots = 0;                     // frames the buffers below serve
+        size_t plane_stride = 0;           // bytes from one plane to the next (max_w x max_h, rounded up to 16)
+        uint8_t *d_planes = nullptr;       // [slots][plane_stride] rows tight (w bytes)
+        const uint8_t **d_table = nullptr; // [slots] d_planes + f * plane_stride
+        float2 *d_raw = nullptr;           // [slots][fcap] cv::FAST's unmasked list of an inline detection (the look-ahead's is Seq::d_corners)
+        int *d_nraw = nullptr;             // [slots]
+        float2 *d_filt = nullptr;          // [slots][fcap] the list under the mask
+        int ran = 0;                       // frames of the latest masked detection of the loop outside vo_seq_* (0: none)
+        int cfg[3] = {0, 0, 0};            // n_images, w, h of the table it ran on
+    } fm;
     // ---- the detector's masks (vocmask_*, include/vo_corners_mask.h, capi_corners_mask.hip): allocated by the first such call ----
     struct CornMask {
         bool ready = false;
@@ -588,6 +603,13 @@ inline bool shi_tomasi(const vo_ctx *c) { return c->det.detector == VODET_SHI_TO
 // masked route, and the lock-step loop's look-ahead is det_lookahead_maps (the map pass alone, into ring slot r's maps) with
 // det_launch(..., maps = that slot's) finishing it in the step
 inline bool topup_on(const vo_ctx *c) { return shi_tomasi(c) && c->top.prm.mode == VOTOP_CARRIED; }
+// cv::FAST's mask in the frame loop acts (include/vo_fast_mask.h): run_detect and vo_seq_configure take fm's buffers (fm_ensure) and
+// the FAST route becomes list, discs, filter, split bucketing (fm_finish behind the unmasked list, wherever it was made)
+inline bool fastmask_on(const vo_ctx *c) { return !shi_tomasi(c) && c->fm.prm.mode == VOFM_CARRIED; }
+int fm_ensure(vo_ctx *c, int frames); // (capi_fast_mask.hip) may drain the context: never inside a lock-step step
+// the discs of the detecting frames' carried points and the filter of raw [frames][fcap] / n_raw [frames] under them, into fm.d_filt
+// and d_nnew, on `stream`
+int fm_finish(vo_ctx *c, const int *d_detect, int frames, const float2 *raw, const int *n_raw, hipStream_t stream);
 int det_ensure(vo_ctx *c, int frames);
 int top_ensure(vo_ctx *c, int frames); // (capi_topup.hip) the planes and their table for `frames` frames; may drain the context
 int det_launch(vo_ctx *c, const vo::Quad *quads, const int *d_detect, int frames, float2 *corners, int *n_out, hipStream_t stream,

@@ -104,6 +104,12 @@ int run_detect(vo_ctx *c, const Run &R)
             if (rcr != VO_OK)
                 return rcr;
         }
+        const bool fmask = fastmask_on(c); // include/vo_fast_mask.h: cv::FAST's call under the disc mask of the carried points
+        if (fmask && !sq.on) {
+            rcr = fm_ensure(c, B);
+            if (rcr != VO_OK)
+                return rcr;
+        }
         // appendNewFeatures only when fewer than redetect_below features were carried in (visualOdometry.cpp:95)
         if (R.timed)
             VO_HIP_TRY(c, hipEventRecord(R.evs[stage_events(DET).start], trk));
@@ -118,7 +124,7 @@ int run_detect(vo_ctx *c, const Run &R)
                 if (r2 == rp || !ahead)
                     VO_HIP_TRY(c, sq.fast[r2].wait(trk));
             launch_seq_prepare(R.seq_active, c->d_ntracked, c->dprm.redetect_below, c->d_detect,
-                               ahead && !topup_on(c) ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, trk);
+                               ahead && !topup_on(c) && !fmask ? sq.d_ncorn + (size_t)rp * sq.S : nullptr, c->d_nnew, B, trk);
             c->detect_uploaded = false;
         } else {
             bool changed = false;
@@ -144,6 +150,21 @@ int run_detect(vo_ctx *c, const Run &R)
             if (rcd != VO_OK)
                 return rcd;
             launch_bucket(c->d_feat, c->corn.d_pts, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap, c->w, c->h, bs, fpb, c->d_pts_det[wset],
+                          c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active, c->d_overflow, B, trk);
+        } else if (fmask) {
+            // the unmasked list is the look-ahead's (ring slot rp; seq_prepare_kernel, given no counts, left d_nnew alone) or made
+            // here into the record's own list; then the discs of the carried points, the filter under them -- which writes d_nnew,
+            // 0 for a frame that does not detect again -- and the bucketing in its split form.  An unmasked list beyond fcap
+            // arrives as fcap + 1 corners and leaves as the overflow flag.
+            const float2 *raw = ahead ? sq.d_corners + (size_t)rp * sq.S * c->fcap : c->fm.d_raw;
+            const int *n_raw = ahead ? sq.d_ncorn + (size_t)rp * sq.S : c->fm.d_nraw;
+            if (!ahead)
+                launch_fast_corners(c->d_imgs, c->quads_cur, c->d_detect, B, c->w, c->h, t, c->dprm.fast_nonmax, c->d_nmsmask, c->d_rowcnt, c->d_rowoff,
+                                    nullptr, c->fm.d_nraw, c->fcap, c->fm.d_raw, trk);
+            int rcd = fm_finish(c, c->d_detect, B, raw, n_raw, trk);
+            if (rcd != VO_OK)
+                return rcd;
+            launch_bucket(c->d_feat, c->fm.d_filt, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap, c->w, c->h, bs, fpb, c->d_pts_det[wset],
                           c->d_ages_det[wset], c->d_npts_det[wset], cap, R.seq_active, c->d_overflow, B, trk);
         } else if (ahead) {
             launch_bucket(c->d_feat, sq.d_corners + (size_t)rp * sq.S * c->fcap, c->d_fages, c->d_ntracked, c->d_nnew, c->fcap,

@@ -67,7 +67,7 @@ TuneKey tune_key(const vo_ctx *c, int stages)
     // (bit 5: the frame loop's detector -- a schedule probed under FAST is neither reused nor overwritten by a Shi-Tomasi context;
     // bit 6: its top-up under a mask of the carried points, include/vo_topup.h, likewise)
     key.k[7] = (c->prm.mono_rotation ? 1 : 0) | ((stages & VO_STAGE_DETECT) ? 2 : 0) | (c->sync_call && !c->seq.on ? 16 : 0) | (shi_tomasi(c) ? 32 : 0) |
-               (topup_on(c) ? 64 : 0);
+               (topup_on(c) ? 64 : 0) | (fastmask_on(c) ? 128 : 0);
     return key;
 }
 

@@ -80,6 +80,11 @@ int vo_seq_configure(vo_ctx *c, int n_seq, int w, int h, int ring, int max_steps
         if (rc != VO_OK)
             return rc;
     }
+    if (fastmask_on(c)) { // (include/vo_fast_mask.h) the planes and the lists of cv::FAST's mask, one slot per sequence: here as well
+        rc = fm_ensure(c, n_seq);
+        if (rc != VO_OK)
+            return rc;
+    }
     c->tf_base = -1; // the ring owns the image table (with ring 2 and one sequence the configure above changed nothing)
     // ONE sequence: the loop's two chains of small kernels on disjoint halves of the compute units (capi.hip,
     // ensure_partitioned_streams); more sequences fill the chip and want all of it

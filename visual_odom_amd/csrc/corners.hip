@@ -666,6 +666,21 @@ hipError_t launch_corners_frames_map(const PyrImage *d_imgs, const Quad *d_quads
     return hipGetLastError();
 }
 
+hipError_t launch_corner_disc_frames(const int *d_detect, int n, int w, int h, const CornTopArgs &t, hipStream_t stream)
+{
+    if (n <= 0)
+        return hipSuccess;
+    // the planes' w h bytes each (plane_stride apart)
+    hipError_t e = hipMemset2DAsync(t.plane0, t.plane_stride, 0xFF, (size_t)w * h, (size_t)n, stream);
+    if (e != hipSuccess)
+        return e;
+    int kept = t.max_kept < t.fcap ? t.max_kept : t.fcap;
+    kept = kept > 0 ? kept : 1;
+    const int disc_x = (kept + CD_WAVES - 1) / CD_WAVES;
+    hipLaunchKernelGGL(corn_disc_frames_kernel, dim3(disc_x, n), dim3(CD_T), 0, stream, t.feat, t.fcap, t.n_tracked, d_detect, t.radius, t.planes, w, h, disc_x);
+    return hipGetLastError();
+}
+
 hipError_t launch_corners_frames_masked(const int *d_detect, int n, int w, int h, const CornArgs &a, const CornTopArgs &t, hipStream_t stream)
 {
     if (n <= 0)
@@ -673,14 +688,10 @@ hipError_t launch_corners_frames_masked(const int *d_detect, int n, int w, int h
     hipError_t e = hipMemsetAsync(a.max_key, 0, sizeof(unsigned) * (size_t)n, stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(a.ncand, 0, sizeof(int) * (size_t)n, stream);
-    if (e == hipSuccess) // the planes' w h bytes each (plane_stride apart)
-        e = hipMemset2DAsync(t.plane0, t.plane_stride, 0xFF, (size_t)w * h, (size_t)n, stream);
+    if (e == hipSuccess)
+        e = launch_corner_disc_frames(d_detect, n, w, h, t, stream);
     if (e != hipSuccess)
         return e;
-    int kept = t.max_kept < t.fcap ? t.max_kept : t.fcap;
-    kept = kept > 0 ? kept : 1;
-    const int disc_x = (kept + CD_WAVES - 1) / CD_WAVES;
-    hipLaunchKernelGGL(corn_disc_frames_kernel, dim3(disc_x, n), dim3(CD_T), 0, stream, t.feat, t.fcap, t.n_tracked, d_detect, t.radius, t.planes, w, h, disc_x);
     const int cells = w * h;
     int wgs = (cells + CX_PER_WG - 1) / CX_PER_WG;
     wgs = wgs < 1 ? 1 : wgs > 1024 ? 1024 : wgs;

@@ -24,7 +24,9 @@
 //   fast_rowscan_kernel  workgroup per frame: exclusive scan of the row counts
 //   fast_nms_write_kernel wavefront per 64 / segs image rows, lane per 64-pixel segment: (x, y) at rows_before + rank from the stored
 //                        ballots (row-major)
-//   bucket_kernel        workgroup per frame.  The sequential bucket fill is restated as order
+//   fast_mask_filter_kernel workgroup per frame: cv::FAST's mask argument (KeyPointsFilter::runByPixelsMask) as one order-preserving
+//                        compaction of the corner list under the frame's mask plane (include/vo_fast_mask.h)
+//   bucket_kernel       workgroup per frame.  The sequential bucket fill is restated as order
 //                        statistics: a bucket ends up holding (slot 0) its LAST eligible feature if
 //                        more than fpb are eligible, else its first; (slots 1..) its 2nd..fpb-th
 //                        eligible feature -- found with LDS atomicMin / atomicMax rounds -- then an
@@ -451,6 +453,62 @@ __global__ __launch_bounds__(256) void fast_rowscan_kernel(int *__restrict__ row
     }
 }
 
+// KeyPointsFilter::runByPixelsMask over the frames' corner lists (include/vo_fast_mask.h): FastFeatureDetector::detect(image, keypoints,
+// mask) is cv::FAST followed by that filter, so non-maximum suppression has run on the unmasked image and a corner survives iff
+// plane[y * pitch + x] != 0 -- x and y are the exact integers fast_nms_write_kernel put into the floats.  One workgroup per frame, of
+// 256 threads or (launches of a few frames: the kernel sits between FAST and bucket_kernel on the critical path of vo_detect_bucket and
+// of a one-sequence step, like bucket_kernel) of 1024, walks the list in chunks of its width.  A survivor's place is the running base
+// + the survivors of the chunk's lower wavefronts (their counts through LDS, summed in wavefront order) + its rank among its own
+// wavefront's (ballot + mbcnt): the order of the list is kept and no atomic takes part, so the result does not depend on timing.
+// in / out [B][cap]; n_in [B] may exceed cap (FAST counts what it could not store): then only the first cap entries exist, the list is
+// not cv::FAST's, and n_out becomes cap + 1, which bucket_kernel's split form reports as the frame's list overflow.  A frame that does
+// not detect again gets n_out = 0 and its output is left alone.
+constexpr int FM_MAX_WAVES = 16;
+
+__global__ __launch_bounds__(1024) void fast_mask_filter_kernel(const float2 *__restrict__ in, const int *__restrict__ n_in, int cap,
+                                                                const uint8_t *const *__restrict__ planes, int pitch,
+                                                                const int *__restrict__ detect /* or null = every frame */,
+                                                                float2 *__restrict__ out, int *__restrict__ n_out)
+{
+    __shared__ int s_wave[FM_MAX_WAVES];
+    const int frame = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = nthr >> 6;
+    if (detect && !detect[frame]) { // (uniform)
+        if (tid == 0)
+            n_out[frame] = 0;
+        return;
+    }
+    const int n_raw = n_in[frame], n = n_raw < cap ? n_raw : cap;
+    const float2 *__restrict__ I = in + (size_t)frame * cap;
+    float2 *__restrict__ O = out + (size_t)frame * cap;
+    const uint8_t *__restrict__ plane = planes[frame];
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += nthr) { // (uniform trip count: the ballots and the barriers need every lane)
+        const int i = i0 + tid;
+        float2 p = make_float2(0.f, 0.f);
+        bool keep = false;
+        if (i < n) {
+            p = I[i];
+            keep = plane[(size_t)(int)p.y * pitch + (int)p.x] != 0;
+        }
+        const unsigned long long m = VO_BALLOT(keep);
+        if (lane == 0)
+            s_wave[wv] = (int)VO_POPCLL(m);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int k = 0; k < nw; k++) {
+            const int t = s_wave[k];
+            before += k < wv ? t : 0;
+            total += t;
+        }
+        if (keep)
+            O[base + before + (int)VO_MBCNT(m, 0u, lane)] = p;
+        base += total;
+        __syncthreads(); // (s_wave is rewritten by the next chunk)
+    }
+    if (tid == 0)
+        n_out[frame] = n_raw > cap ? cap + 1 : base;
+}
+
 constexpr int BK_MAX_CELLS = 1024; // (rows/bucket + 1) * (cols/bucket + 1) of the ordinary grid: any features_per_bucket <= 8
 constexpr int BK_MAX_FPB = 8;
 constexpr int BK_CELL_CACHE = 8192; // list entries whose cell is kept in LDS between the passes (16 KB)
@@ -691,6 +749,15 @@ void launch_bucket(const float2 *d_feat, const float2 *d_corners, const int *d_a
     else // (bucket_grid_ok was the callers' check)
         hipLaunchKernelGGL(bucket_kernel<BK_FINE_CELLS>, dim3(n_frames), dim3(threads), 0, stream, d_feat, d_ages, d_ntracked, d_nnew, cap, h, w,
                            bucket_size, fpb, d_out_pts, d_out_ages, d_out_n, out_cap, d_active, d_overflow, d_corners);
+}
+
+void launch_fast_mask_filter(const float2 *d_in, const int *d_nin, int cap, const uint8_t *const *d_planes, int pitch, const int *d_detect,
+                             float2 *d_out, int *d_nout, int n_frames, hipStream_t stream)
+{
+    if (n_frames <= 0)
+        return;
+    const int threads = n_frames <= 4 ? 1024 : 256; // (launch_bucket's rule)
+    hipLaunchKernelGGL(fast_mask_filter_kernel, dim3(n_frames), dim3(threads), 0, stream, d_in, d_nin, cap, d_planes, pitch, d_detect, d_out, d_nout);
 }
 
 void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w,

@@ -88,6 +88,9 @@ hipError_t launch_corners_frames(const PyrImage *d_imgs, const Quad *d_quads, co
 //                                 a.masks (= the plane table, a.mask_pitch = w) and the select pass; max_key and ncand are zeroed first
 hipError_t launch_corners_frames_map(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n, int w, const CornArgs &a, hipStream_t stream);
 hipError_t launch_corners_frames_masked(const int *d_detect, int n, int w, int h, const CornArgs &a, const CornTopArgs &t, hipStream_t stream);
+// its first step alone -- 0xFF over the n planes and the discs of every detecting frame's carried points -- which cv::FAST's mask in
+// the frame loop (include/vo_fast_mask.h) shares with it
+hipError_t launch_corner_disc_frames(const int *d_detect, int n, int w, int h, const CornTopArgs &t, hipStream_t stream);
 // cv::cornerMinEigenVal(img, map, block_size, 3) or cv::cornerHarris(img, map, block_size, 3, k) of image `image` into map [h][w]
 // (tight); block_size 3 or 5
 void launch_corner_map(const PyrImage *d_imgs, int image, int w, int h, float *d_map, hipStream_t stream, int block_size = 3, int use_harris = 0,

@@ -176,6 +176,11 @@ void launch_detect_bucket(const PyrImage *d_imgs, const Quad *d_quads, const int
 void launch_fast_corners(const PyrImage *d_imgs, const Quad *d_quads, const int *d_detect, int n_frames, int w, int h,
                          int threshold, int nonmax, unsigned long long *d_nmsmask, int *d_rowcnt, int *d_rowoff,
                          const int *d_ntracked, int *d_nnew, int cap, float2 *d_out, hipStream_t stream);
+// cv::FAST's mask argument over corner lists launch_fast_corners wrote with a null d_ntracked (include/vo_fast_mask.h): frame f's
+// d_in[f][0 .. min(d_nin[f], cap)) filtered by d_planes[f] (rows `pitch` bytes apart, non-zero: allowed) into d_out[f], order kept,
+// the count into d_nout[f] -- 0 for a frame that does not detect, cap + 1 when d_nin[f] > cap (the list overflow of launch_bucket)
+void launch_fast_mask_filter(const float2 *d_in, const int *d_nin, int cap, const uint8_t *const *d_planes, int pitch, const int *d_detect,
+                             float2 *d_out, int *d_nout, int n_frames, hipStream_t stream);
 // grids the device bucketing takes: <= 8 per bucket; <= 1 024 buckets, or <= 4 096 with buckets x per-bucket <= 8 192 (fast.hip)
 bool bucket_grid_ok(int w, int h, int bucket_size, int fpb);
 void launch_bucket(const float2 *d_feat, const float2 *d_corners, const int *d_ages, const int *d_ntracked,

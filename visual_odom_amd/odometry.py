@@ -25,7 +25,7 @@ class StereoOdometry:
     frame) -- the slowest of the three since round 5 (tools/latency_mode.py: 1.10 / 0.81 / 0.75 ms per frame).  Same results."""
 
     def __init__(self, P_l, P_r, device=0, max_w=1241, max_h=376, max_pts=4096, ctx=None, streaming=False,
-                 mono_rotation=False, keep_pair=True, input_format=0, rectify=None, detector=None, corners=None, topup_radius=None,
+                 mono_rotation=False, keep_pair=True, input_format=0, rectify=None, detector=None, corners=None, topup_radius=None, fast_topup_radius=None,
                  **detect_kw):
         self.P_l = np.ascontiguousarray(P_l, np.float32).reshape(3, 4)
         self.P_r = np.ascontiguousarray(P_r, np.float32).reshape(3, 4)
@@ -54,6 +54,10 @@ class StereoOdometry:
         # (include/vo_topup.h; Context.set_topup).  None leaves the context's record as it is (a new context: off); False: off
         if topup_radius is not None:
             self.ctx.set_topup(**(dict(mode="off") if topup_radius is False else dict(radius=topup_radius)))
+        # fast_topup_radius = r: the same under the FAST detector -- cv::FAST's mask argument (include/vo_fast_mask.h;
+        # Context.set_fast_topup), with topup_radius' rules
+        if fast_topup_radius is not None:
+            self.ctx.set_fast_topup(**(dict(mode="off") if fast_topup_radius is False else dict(radius=fast_topup_radius)))
         self._n_pairs = 0
         # main.cpp:81-94
         self.points = np.zeros((0, 2), np.float32)   # currentVOFeatures.points
@@ -166,7 +170,7 @@ class MultiSequenceOdometry:
     and, when asked for, the trajectories."""
 
     def __init__(self, P_l, P_r, n_seq, width, height, device=0, max_pts=4096, ring=3, max_steps=1024, ctx=None,
-                 mono_rotation=False, input_format=0, rectify=None, detector=None, corners=None, topup_radius=None, **detect_kw):
+                 mono_rotation=False, input_format=0, rectify=None, detector=None, corners=None, topup_radius=None, fast_topup_radius=None, **detect_kw):
         self.ctx = ctx if ctx is not None else _lib.Context(device, width, height, max_pts, n_seq)
         self._own = ctx is None
         self.n_seq = n_seq
@@ -179,6 +183,8 @@ class MultiSequenceOdometry:
             self.ctx.set_detector(detector, **(corners or {}))   # vodet_set_params inside the loop is VO_ERR_STATE
         if topup_radius is not None:   # (see StereoOdometry) before configure as well: the loop takes the mask planes there
             self.ctx.set_topup(**(dict(mode="off") if topup_radius is False else dict(radius=topup_radius)))
+        if fast_topup_radius is not None:
+            self.ctx.set_fast_topup(**(dict(mode="off") if fast_topup_radius is False else dict(radius=fast_topup_radius)))
         self.ctx.seq_configure(n_seq, width, height, ring, max_steps)
         self.ctx.batch_set_projection(P_l, P_r)
 

@@ -136,6 +136,9 @@ def main(argv=None):
     ap.add_argument("--topup-radius", type=int, default=None,
                     help="with --detector shi_tomasi: new corners only further than this many pixels from every point a frame carries "
                          "in -- goodFeaturesToTrack under the disc mask of currentVOFeatures.points (include/vo_topup.h); default: no mask")
+    ap.add_argument("--fast-topup-radius", type=int, default=None,
+                    help="with --detector fast: new corners only further than this many pixels from every point a frame carries in -- "
+                         "cv::FAST under the disc mask of currentVOFeatures.points (include/vo_fast_mask.h); default: no mask")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--decode-threads", type=int, default=8,
                     help="image files of frame k + 1 are read and decoded by this many threads while step k is pushed and runs "
@@ -165,7 +168,7 @@ def main(argv=None):
     vo = odometry.MultiSequenceOdometry(P_l, P_r, S, w, h, device=args.device, ring=3, max_steps=args.max_frames + 1,
                                         mono_rotation=args.mono_rotation, features_per_bucket=args.features_per_bucket,
                                         input_format=_lib.FMT_RGB8 if rgb else _lib.FMT_GRAY8, rectify=rect, detector=args.detector,
-                                        topup_radius=args.topup_radius)
+                                        topup_radius=args.topup_radius, fast_topup_radius=args.fast_topup_radius)
     live = [True] * S
     n_read = [0] * S
     import time
